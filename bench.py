@@ -1,9 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- denoising steps/sec of the FMC hot path on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (`metric`, `value` in steps/s, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, plus the run's configuration).  Everything else
+below -- the CPU-oracle parity gate and `cpu_baseline`, the fp32 parity-mode sub-line, the 50-step pipeline loop, the roofline
+objects, the in-step kernel trace, the analytic FLOP figures, the autotune / dispatch report -- runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (the new latents and the U-Net's noise prediction) as
+DIR/<name>.npy in float32; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 One "step" = one denoising step of `CameraObjCtrlPipeline`: the full-width 3-D U-Net (SD-1.5 layout + AnimateDiff
 motion modules, 1.39 B params) forward at classifier-free-guidance batch 2 on a 16x320x512 clip with Camera
@@ -19,11 +26,11 @@ no WORLD_SIZE in the environment starts the N ranks itself (re-exec under `torch
 under an external launcher WORLD_SIZE must equal --gpus.  `n_gpus` in the JSON is the world size an RCCL all-reduce of
 ones returned, not an argument echo.
 
-Before anything is timed, ONE step of the benchmarked model is compared with the CPU oracle (same bf16-rounded weights,
+With --full, before anything is timed, ONE step of the benchmarked model is compared with the CPU oracle (same bf16-rounded weights,
 same noise / timestep / text / camera poses / object masks): `parity_rel_inf` in the JSON line.  The same oracle forward
 -- a CFG-batch-2 16x320x512 U-Net + CMC + OMC step on the host cores -- is the `cpu_baseline` sample.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- the dominant hand-written kernel (level-0 spatial self-attention, S=2560, d=40, 256 (batch,head)
                   pairs): algorithmic flops 4*B*H*S^2*d divided by its average launch duration measured here with
                   events on the launch stream; peak = 2.5 PFLOP/s dense bf16 MFMA (MI355X_MICROARCH.md);
@@ -1063,6 +1070,27 @@ def timed_region(step_fn, steps: int, warmup: int, world: int, sync) -> float:
     return elapsed
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, rank: int, world: int, arrays: dict) -> None:
+    """--dump-outputs: each tensor of `arrays` as path/<name>.npy (float64 stays float64, everything else float32); rank r > 0 writes
+    <name>_rank<r>.npy.  All files of the run together stay within DUMP_MAX_BYTES: a tensor larger than its share is replaced by a
+    fixed, seeded sample of its flattened elements (<name>.npy) and the sorted indices of that sample (<name>_index.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // (world * len(arrays))
+    suffix = f"_rank{rank}" if rank else ""
+    for name, t in arrays.items():
+        t = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() * t.element_size() > share:
+            n = share // (t.element_size() + 8)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+            np.save(os.path.join(path, f"{name}_index{suffix}.npy"), idx.numpy())
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.numpy())
+
+
 def dry_run_main(args):
     """Launcher / timing / JSON plumbing on CPU with the gloo backend and a stub step (no model, no kernels): what the 2-rank
     CPU test of this entry point runs.  Never a measurement: the line says `"dry_run": true`."""
@@ -1075,6 +1103,8 @@ def dry_run_main(args):
         x = torch.tanh(x @ x.t() / 64.0)
 
     elapsed = timed_region(step, args.steps, args.warmup, world, lambda: None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"x": x})
     if rank == 0:
         print(json.dumps({"metric": "DRY RUN (launcher / timing plumbing only)", "dry_run": True, "value": round(world * args.steps / elapsed, 4),
                           "unit": "stub steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1231,6 +1261,9 @@ def train_main(args):
 
     elapsed = timed_region(run, args.steps, args.warmup, world, torch.cuda.synchronize)
     assert torch.isfinite(loss).all()
+    if args.dump_outputs:                                    # the step's loss and the parameters it updated
+        dump_outputs(args.dump_outputs, rank, world, {"loss": loss.reshape(1),
+                                                      "trained_params": torch.cat([p.detach().reshape(-1).float() for p in trainable])})
     # every rank holds the same averaged gradients / parameters: the first trained tensor must agree bit for bit across ranks
     params_equal = None
     if world > 1:
@@ -1302,6 +1335,10 @@ def main():
     ap.add_argument("--no-in-step", action="store_true", help="skip the in-step kernel trace (a child run of this command under rocprofv3 --kernel-trace)")
     ap.add_argument("--trace-child", action="store_true", help="internal: the child run of the in-step trace (no oracle, no roofline loops, no trace)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo stub of the launcher + timing + JSON plumbing (tests)")
+    ap.add_argument("--full", action="store_true", help="everything besides the timed steps: CPU-oracle parity gate + cpu_baseline, fp32 parity-mode "
+                                                        "line, 50-step pipeline loop, roofline objects, in-step trace, FLOP / autotune / dispatch report")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32, "
+                                                                        f"at most {DUMP_MAX_BYTES >> 20} MB in all)")
     args = ap.parse_args()
     if args.dry_run:
         return dry_run_main(args)
@@ -1404,7 +1441,7 @@ def main():
         # does not reproduce the oracle never prints a throughput line; an oracle that throws takes the run down with it.  Runs at
         # N = 1 (where `cpu_baseline` is reported); at N > 1 no rank waits 45 s in a barrier for rank 0's CPU forward -- every rank's
         # kernels are the ones gated at N = 1, and the ranks check their outputs for finiteness.
-        if world == 1 and not args.no_cpu_baseline and not args.trace_child:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.trace_child:
             t_par = 801
             eps_gpu = unet_step(torch.cat([latents, latents]).to(dtype), t_par).float().cpu()
             eps_ref, cpu = oracle_step(unet, enc, ada, clip, text2, clip["latents"].float(), t_par, config=cfg, full=args.cpu_baseline_full)
@@ -1415,12 +1452,15 @@ def main():
                 raise SystemExit(f"bench.py: PARITY GATE FAILED -- rel-inf {parity:.3e} >= {parity_tol:g} against the CPU oracle "
                                  f"({args.dtype}, config {cfg}); nothing was timed")
 
+        last = {}
+
         def denoise_step(i):
             nonlocal latents
             t = ts[i % len(ts)]
             x = torch.cat([latents, latents]).to(dtype)
             eps = unet_step(x, t)
             latents = sched.step_cfg(eps, t, latents, args.guidance, True)
+            last["eps"] = eps
 
         ts = sched._timesteps_host
         text_kv_before = dict(L_.text_kv_calls)
@@ -1428,9 +1468,11 @@ def main():
         text_kv_in_loop = L_.text_kv_calls["computed"] - text_kv_before["computed"]
         assert text_kv_in_loop == 0, f"{text_kv_in_loop} text k | v projections ran inside the timed steps"
         assert torch.isfinite(latents).all(), "non-finite latents"
+        if args.dump_outputs:        # before anything else runs: the graph's output buffer holds the last timed step's eps
+            dump_outputs(args.dump_outputs, rank, world, {"latents": latents, "eps": last["eps"]})
 
         call_log, dispatch = [], None
-        if rank == 0 and not args.trace_child:
+        if rank == 0 and args.full and not args.trace_child:
             # one EAGER step of exactly what the graph replays (right behind the timed steps: the 50-step pipeline below installs its own per-clip
             # caches on the modules): which front-end calls went to an own kernel / the vendor arm / fell through as ineligible, and the order and
             # shapes of every GEMM-shaped launch (to assign the in-step trace's launches to shapes)
@@ -1459,7 +1501,7 @@ def main():
             dispatch = {k: {a: K.dispatch_calls[k][a] - d0[k][a] for a in v} for k, v in K.dispatch_calls.items()}
 
         loop50_s = None
-        if rank == 0 and not args.trace_child and not args.no_loop50:
+        if rank == 0 and args.full and not args.trace_child and not args.no_loop50:
             # the metric as the reference runs it: the configuration's own pipeline end to end -- `CameraObjCtrlPipeline.__call__`
             # (fmc/pipelines/pipeline_animation_cm_om.py:570-738: camera encoder once, then 50 DDIM steps at CFG batch 2 with the OMC features) for obj /
             # cam, `AnimationPipeline`'s plain loop for lora -- on this clip, latents out (VAE / CLIP are outside the path), graphs warm from a first call
@@ -1483,13 +1525,27 @@ def main():
             assert torch.isfinite(torch.as_tensor(out50.videos)).all()
 
     fp32_line = None
-    if rank == 0 and world == 1 and dtype == torch.bfloat16 and not args.trace_child and not args.no_fp32_line and not args.fp8_temporal:
+    if rank == 0 and world == 1 and dtype == torch.bfloat16 and args.full and not args.trace_child and not args.no_fp32_line and not args.fp8_temporal:
         fp32_line = fp32_parity_mode_line(args, cfg, device, (unet, enc, ada), clip, text2, eps_ref if parity is not None else None, 801)
         log(f"[rank 0] fp32 parity mode: {fp32_line['steps_per_s']} steps/s, rel-inf {fp32_line['parity_rel_inf']}")
     if rank == 0 and args.trace_child:
         print(json.dumps({"trace_child": True, "ms_per_step": round(elapsed / args.steps * 1e3, 3)}), flush=True)
         return
-    if rank == 0:
+    config = {"workload": CONFIGS[cfg]["workload"], "baseline_config": cfg,
+              "frames": FRAMES, "height": HEIGHT, "width": WIDTH, "guidance_scale": args.guidance,
+              "hip_graph": not args.no_graph, "fp8_temporal_attention": args.fp8_temporal,
+              "cfg_shared_prefix": bool(cfg_shared),
+              "parallelism": f"dp{world} (independent clips, no collective)"}
+    if rank == 0 and not args.full:
+        ms = elapsed / args.steps * 1e3
+        print(json.dumps({
+            "metric": CONFIGS[cfg]["metric"],
+            "value": round(world * args.steps / elapsed, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "config": config,
+            "parity_rel_inf": None, "parity_note": "not evaluated in a plain run (--full runs the CPU-oracle gate before timing)",
+            "conditioning_once_per_clip_ms": round(cond_ms, 2), "full": False}), flush=True)
+    elif rank == 0:
         bf = dtype == torch.bfloat16
         if getattr(args, "torch_profile", None):
             with torch.no_grad():
@@ -1525,12 +1581,7 @@ def main():
             "metric": CONFIGS[cfg]["metric"],
             "value": round(world * args.steps / elapsed, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": CONFIGS[cfg]["workload"], "baseline_config": cfg,
-                       "frames": FRAMES, "height": HEIGHT, "width": WIDTH, "guidance_scale": args.guidance,
-                       "hip_graph": not args.no_graph, "fp8_temporal_attention": args.fp8_temporal,
-                       "cfg_shared_prefix": bool(cfg_shared),
-                       "parallelism": f"dp{world} (independent clips, no collective)"},
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "config": config,
             "parity_rel_inf": parity, "parity_gate": parity_tol if parity is not None else None,
             "parity_note": ("max|eps_gpu - eps_oracle| / max|eps_oracle| for one CFG-batch-2 step (t = 801) of the benchmarked "
                             "model: same weights (bf16-rounded), noise, text, camera poses, object masks; oracle = fp32 CPU; the run aborts "
@@ -1563,11 +1614,12 @@ def main():
                                              "out), second call: graphs warm")
             out["ddim_50_step_loop_s"] = round(loop50_s, 3)
             out["ddim_50_step_loop_steps_per_s"] = round(50.0 / loop50_s, 3)
+        out["full"] = True
         print(json.dumps(out), flush=True)
-        if args.autotune_log:
-            with open(args.autotune_log, "w") as f:
-                for key, use, times, calls in sorted(K.autotune_report(), key=lambda r: -r[3] * min(r[2].values() or [0])):
-                    f.write(f"{key} -> arm {use}  calls {calls}  ms {times}\n")
+    if rank == 0 and args.autotune_log:
+        with open(args.autotune_log, "w") as f:
+            for key, use, times, calls in sorted(K.autotune_report(), key=lambda r: -r[3] * min(r[2].values() or [0])):
+                f.write(f"{key} -> arm {use}  calls {calls}  ms {times}\n")
     if world > 1:
         dist.destroy_process_group()
 

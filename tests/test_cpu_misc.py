@@ -386,14 +386,50 @@ print(json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fmc"), reason="build container only: needs the reference checkout")
-def test_install_as_fmc_overlays_the_reference_package():
+# names the stand-in checkout's own (not replaced) modules define: module -> names
+_KEPT_NAMES = {"data/dataset.py": ("ray_condition", "UnrealTrajVideoDataset"), "data/utils.py": ("create_absolute_matrix_from_ref_cam_list",),
+               "util.py": ("get_traj_features_v2",), "utils/util.py": ("setup_logger",)}
+
+
+def _write_reference_layout(root):
+    """A stand-in reference checkout under `root`: an `fmc` namespace package (no `__init__.py`, as in the reference) whose
+    hot-path modules raise when imported (the overlay must never load them), whose kept modules define `_KEPT_NAMES` with
+    placeholder bodies, and two trainer scripts whose top-level `from fmc... import ...` lines are generated from this
+    package's own API: every public class / function each replaced module exposes, plus the kept names."""
+    import importlib
+    import inspect
+    import synfmc_amd
+
+    def put(rel, text):
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+    hot = []
+    for sub in synfmc_amd._REPLACED:
+        put("fmc/" + sub.replace(".", "/") + ".py", f"raise ImportError('hot-path module fmc.{sub} of the reference was imported')\n")
+        mod = importlib.import_module(f"synfmc_amd.{sub}")
+        hot += [f"from fmc.{sub} import {n}\n" for n, o in sorted(vars(mod).items())
+                if not n.startswith("_") and (inspect.isclass(o) or inspect.isfunction(o)) and o.__module__.startswith("synfmc_amd.")]
+    kept = []
+    for rel, names in _KEPT_NAMES.items():
+        put("fmc/" + rel, "".join(f"class {n}:\n    pass\n\n\n" if n[0].isupper() else f"def {n}(*args, **kwargs):\n    return None\n\n\n"
+                                  for n in names))
+        kept += [f"from fmc.{rel[:-3].replace('/', '.')} import {n}\n" for n in names]
+    put("train_cam_obj_ctrl.py", "import os\n" + "".join(hot))
+    put("train_cam_ctrl.py", "import os\n" + "".join(kept))
+
+
+def test_install_as_fmc_overlays_the_reference_package(tmp_path):
     """`install_as_fmc(reference_root)`: every `from fmc... import ...` line of the two trainers resolves -- hot-path names
     to this package, dataset classes / logging / pose math to the reference's own modules, with `ray_condition` and
-    `get_traj_features_v2` patched into them.  Runs in a subprocess (it rewires `sys.modules`); only third-party packages
-    missing from this container are stubbed, no `fmc` module is."""
+    `get_traj_features_v2` patched into them.  Runs in a subprocess (it rewires `sys.modules`) against a stand-in checkout
+    with the reference's layout (`_write_reference_layout`); only third-party packages missing from this container are
+    stubbed, no `fmc` module is."""
     import json
-    out = subprocess.run([sys.executable, "-c", _OVERLAY_WORKER, ROOT, "/root/reference"], capture_output=True, text=True,
+    ref = str(tmp_path / "reference")
+    _write_reference_layout(ref)
+    out = subprocess.run([sys.executable, "-c", _OVERLAY_WORKER, ROOT, ref], capture_output=True, text=True,
                          timeout=300, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -402,7 +438,7 @@ def test_install_as_fmc_overlays_the_reference_package():
         assert r[k].startswith("synfmc_amd."), (k, r[k])
     for k in ("dataset_cls", "logger", "abs_matrix", "kept_reference_fn"):
         assert r[k].startswith("fmc."), (k, r[k])
-    assert r["dataset_file"].startswith("/root/reference/") and r["logger_file"].startswith("/root/reference/")
+    assert r["dataset_file"].startswith(ref + os.sep) and r["logger_file"].startswith(ref + os.sep)
     assert r["sched"][0] == "synfmc_amd.schedulers" and r["sched"][1] == 1 and abs(r["sched"][2] - 0.00085) < 1e-9
 
 
@@ -435,6 +471,38 @@ def test_bench_entry_spawns_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True,
                          text=True, env=dict(env, WORLD_SIZE="3", RANK="0"), timeout=120, cwd="/tmp")
     assert bad.returncode != 0 and "WORLD_SIZE=3" in (bad.stderr + bad.stdout)
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step computed as float32 .npy files; two runs with the same arguments
+    write identical arrays, and `--steps` is the number of timed steps the result line reports (dry-run entry: CPU stub step)."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(OMP_NUM_THREADS="1")
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run", "--steps", "5", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, env=env, timeout=300, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")][-1]
+        assert r["steps"] == 5 and r["warmup"] == 2 and r["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["x.npy"]
+        dumps.append(np.load(tmp_path / run / "x.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (64, 64) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """An output larger than its share of the 64 MB budget is written as a fixed, seeded sample plus the indices of that sample."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    t = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    bench.dump_outputs(str(tmp_path), 0, 1, {"big": t, "small": torch.ones(3, dtype=torch.float64)})
+    big, idx, small = (np.load(tmp_path / f) for f in ("big.npy", "big_index.npy", "small.npy"))
+    assert big.nbytes + idx.nbytes <= 4096 // 2 and big.dtype == np.float32 and small.dtype == np.float64
+    assert np.array_equal(big, t.numpy().reshape(-1)[idx]) and np.all(np.diff(idx) > 0)
+    bench.dump_outputs(str(tmp_path / "again"), 0, 1, {"big": t, "small": torch.ones(3, dtype=torch.float64)})
+    assert np.array_equal(np.load(tmp_path / "again" / "big_index.npy"), idx)
 
 
 def test_parity_mode_arm_decoding_reaches_the_160x320_kernels():

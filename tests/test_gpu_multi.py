@@ -31,7 +31,7 @@ def _bench(*extra, timeout=1500):
 
 def test_bench_infer_two_ranks_rccl():
     _need_two_gpus()
-    line = _bench("--steps", "3", "--warmup", "1")
+    line = _bench("--steps", "3", "--warmup", "1", "--full")
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0
     assert line["parity_rel_inf"] is None and "N > 1" in line["parity_note"]       # nobody idles behind rank 0's CPU oracle
     assert line["config"]["parallelism"].startswith("dp2")
