@@ -544,6 +544,34 @@ int fmc_nhwc_to_cmajor_padded(const void* src, void* dst, int n_img, int H, int 
                               int shifts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Weight gradient of a token matrix (csrc/lora_wgrad.hip): the gradients of the trainable LoRA factors of the spatial attention
+ * (FMC stage 1 and stage 3 with `train_image_lora`), dU = s dY^T P and dD = s Q^T X, as reductions over the tokens of a batch
+ * with both operands row-major.  Per problem:
+ *     out[n][k] = alpha * sum_{m < M} a[m][n] * b[m][k]            (accumulate == 0)
+ *     out[n][k] = out[n][k] + alpha * sum_{m < M} a[m][n] * b[m][k] (accumulate != 0)
+ *   a bf16 [M, N] rows `lda` apart, b bf16 [M, K] rows `ldb` apart (often column slices of a fused [M, 3C] tensor), out fp32 [N, K]
+ *   rows `ldo` apart.  M >= 1, N % 16 == K % 16 == 0, lda >= N, ldb >= K, ldo >= K; lda % 8 == ldb % 8 == 0, ldo % 4 == 0 and
+ *   16-byte aligned pointers (FMC_E_ALIGN otherwise).  fp32 accumulate on v_mfma_f32_32x32x16_bf16, operands staged row-major into
+ *   LDS and read transposed with ds_read_b64_tr_b16.
+ *   One launch takes 1 .. 8 problems.  Long reductions are split over several workgroups by a rule that depends on (M, N, K) alone;
+ *   their fp32 partials go to `workspace` (caller-owned, 16-byte aligned, at least the bytes `fmc_linear_wgrad_workspace_bytes`
+ *   returns for the same list; NULL when that is 0) and a second kernel sums them in a fixed order: results are bit-reproducible,
+ *   and a problem gives the same bits in any group.  (`hip_ops.linear_wgrad`)
+ * fmc_linear_wgrad_workspace_bytes: the workspace the list needs, or -1 (with the error message set) when the list is invalid.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct fmc_wgrad_problem {
+    const void* a;
+    const void* b;
+    float* out;
+    int64_t M, lda, ldb, ldo;
+    int N, K;
+    float alpha;
+    int accumulate;
+} fmc_wgrad_problem;
+int64_t fmc_linear_wgrad_workspace_bytes(const fmc_wgrad_problem* problems, int n_problems);
+int fmc_linear_wgrad_bf16(const fmc_wgrad_problem* problems, int n_problems, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The fused temporal attention block of the motion modules at the 40x64 level (round 4; csrc/temporal_block.hip).
  * Replaces, for one attention block of `TemporalTransformerBlock.forward` (fmc/models/motion_module.py:287-300) as driven by
  * `TemporalSelfAttention.forward` (:349-389) and `PoseAdaptorAttnProcessor.forward` / `AttnProcessor.__call__`

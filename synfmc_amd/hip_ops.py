@@ -1410,11 +1410,11 @@ def linear4_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
 def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, alpha: float = 1.0, geglu: bool = False,
                 tile: int = 0, split_k: int = 1, x2: Optional[torch.Tensor] = None,
-                residual2: Optional[torch.Tensor] = None) -> torch.Tensor:
+                residual2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`alpha * (x @ weight^T + bias) + residual [+ residual2]` (or the GEGLU gate, see fmc_linear_bf16) on the bf16 MFMA kernel.
     x `[..., K]`, weight `[N, K]`; residual has the output's shape.  `tile` may also be an autotune arm id
     (`tile + 16 * log2(split_k)`).  `x2 [..., K2]`: the A operand is the concat `[x, x2]` (weight `[N, K + K2]`),
-    never materialised."""
+    never materialised.  `out`: a 2-D `[M, N]` view (e.g. a column slice of a wider tensor) to write instead of a new tensor."""
     tile, split_k = _decode_arm(tile, split_k)
     _dev(x, weight, bias, residual, x2)
     N, Kd = weight.shape
@@ -1431,7 +1431,12 @@ def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
         k_split = x.shape[-1]
         assert M2 == M and k_split + x2.shape[-1] == Kd
     n_out = N // 2 if geglu else N
-    out = torch.empty(*x.shape[:-1], n_out, dtype=x.dtype, device=x.device)
+    ldo = n_out
+    if out is None:
+        out = torch.empty(*x.shape[:-1], n_out, dtype=x.dtype, device=x.device)
+    else:
+        assert out.dtype == x.dtype and out.shape[-1] == n_out and _rows2d(out)[0] == M and tile != 18
+        ldo = _rows2d(out)[1]
     ldres = 0
     if residual is not None:
         assert residual.shape == out.shape
@@ -1441,7 +1446,7 @@ def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     ws, ws_bytes = _splitk_workspace(x.device, split_k, M, N)
     _log_call("own_linear", (M, N, Kd, "geglu" if geglu else f"t{tile}", (residual is not None) + (residual2 is not None)), 2.0 * M * N * Kd)
     _lib.check(_lib.load().fmc_linear_bf16(x.data_ptr(), weight.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N,
-                                           Kd, ldx, ldres, n_out, float(alpha), int(geglu), int(tile), int(split_k),
+                                           Kd, ldx, ldres, ldo, float(alpha), int(geglu), int(tile), int(split_k),
                                            ws, ws_bytes, _p(x2), ldx2, k_split, _p(residual2), _stream()),
                "fmc_linear_bf16")
     return out
@@ -2695,3 +2700,206 @@ class _Conv3x3Trainable(torch.autograd.Function):
 
 def conv3x3_trainable(x, weight, bias=None):
     return _Conv3x3Trainable.apply(x, weight, bias)
+
+
+# --------------------------------------------------------------------------------------------
+# trainable LoRA on frozen projections (FMC stage 1; stage 3 with `train_image_lora`)
+# --------------------------------------------------------------------------------------------
+import ctypes as _ct
+
+
+class WgradProblem(_ct.Structure):
+    """`fmc_wgrad_problem` of include/fmc_hip.h."""
+    _fields_ = [("a", _ct.c_void_p), ("b", _ct.c_void_p), ("out", _ct.c_void_p), ("M", _ct.c_int64), ("lda", _ct.c_int64),
+                ("ldb", _ct.c_int64), ("ldo", _ct.c_int64), ("N", _ct.c_int), ("K", _ct.c_int), ("alpha", _ct.c_float), ("accumulate", _ct.c_int)]
+
+
+_wgrad_ws = {}
+
+
+def linear_wgrad_group(problems):
+    """One `fmc_linear_wgrad_bf16` launch for up to 8 problems `(a [M, N], b [M, K], alpha, out, accumulate)`:
+    `out [N, K] (fp32) = alpha * a^T b (+ out)`.  a / b are bf16 device tensors, contiguous or 2-D row-strided views (column
+    slices of a fused tensor); `out=None` allocates.  Returns the list of outputs.  fp32 operands (the parity mode) take an fp32
+    matmul instead; CPU tensors raise."""
+    outs, descs = [], []
+    for a, b, alpha, out, acc in problems:
+        _dev(a, b, out)
+        (M, lda), (Mb, ldb) = _rows2d(a), _rows2d(b)
+        N, Kd = a.shape[-1], b.shape[-1]
+        assert M == Mb, "linear_wgrad: a and b must have the same rows"
+        if out is None:
+            out = torch.empty(N, Kd, dtype=torch.float32, device=a.device)
+            acc = False
+        assert out.dtype == torch.float32 and out.ndim == 2 and out.shape == (N, Kd) and out.stride(1) == 1
+        outs.append(out)
+        if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+            g = torch.matmul(a.reshape(M, N).t().float(), b.reshape(M, Kd).float())
+            out.add_(g, alpha=alpha) if acc else torch.mul(g, alpha, out=out)
+            continue
+        descs.append(WgradProblem(a.data_ptr(), b.data_ptr(), out.data_ptr(), M, lda, ldb, out.stride(0), N, Kd, float(alpha), int(bool(acc))))
+    if not descs:
+        return outs
+    lib = _lib.load()
+    arr = (WgradProblem * len(descs))(*descs)
+    need = lib.fmc_linear_wgrad_workspace_bytes(arr, len(descs))
+    if need < 0:
+        _lib.check(-1, "fmc_linear_wgrad_bf16")
+    ws, ws_bytes = None, 0
+    if need > 0:
+        dev = outs[0].device
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+        buf = _wgrad_ws.get(key)
+        if buf is None or buf.numel() * 4 < need:
+            if buf is not None:
+                _ws_retired.append(buf)        # a captured HIP graph may have baked its address
+            buf = torch.empty(need // 4 + 1024, dtype=torch.float32, device=dev)
+            _wgrad_ws[key] = buf
+        ws, ws_bytes = buf.data_ptr(), buf.numel() * 4
+    _log_call("lora_wgrad", tuple((d.M, d.N, d.K) for d in descs), sum(2.0 * d.M * d.N * d.K for d in descs))
+    _lib.check(lib.fmc_linear_wgrad_bf16(arr, len(descs), ws, ws_bytes, _stream()), "fmc_linear_wgrad_bf16")
+    return outs
+
+
+def linear_wgrad(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0, out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    """`alpha * a^T b` (+ out), fp32 `[N, K]`, for token matrices a `[M, N]`, b `[M, K]` (see `linear_wgrad_group`)."""
+    return linear_wgrad_group([(a, b, alpha, out, accumulate)])[0]
+
+
+def _lora_gemm(x, weight, bias=None, residual=None, x2=None, out=None):
+    """`[x | x2] @ weight^T + bias + residual` for the LoRA projections: the bf16 GEMM of this library (kernel-chosen tile; `out` may be a
+    column slice of a fused output), fp32 storage (parity mode, host tests) in plain torch ops."""
+    if x.dtype == torch.bfloat16 and x.is_cuda:
+        return linear_bf16(x, weight, bias, residual, x2=x2, out=out)
+    xin = x if x2 is None else torch.cat([x, x2], dim=-1)
+    y = torch.nn.functional.linear(xin, weight, bias)
+    if residual is not None:
+        y = y + residual
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def lora_pad_rank(r: int, dtype) -> int:
+    """Width of P = x D^T inside the fused GEMMs: the bf16 kernel's reduction comes in 64-wide k-tiles, so the rank is zero-padded to
+    the next multiple of 64 (exact: padded columns of P and of U are zero).  fp32 storage keeps the rank."""
+    return (r + 63) // 64 * 64 if dtype == torch.bfloat16 else r
+
+
+def lora_group_weights(weights, downs, ups, scales, dtype, cache: Optional[dict] = None):
+    """The derived weights of one group of LoRA projections that share an input (q | k | v of self attention, k | v of the text, or one
+    projection): with r' = `lora_pad_rank(r)`,
+        d_stack [G r', Cin]       = [D_1; ...; D_G] (each padded to r' rows)             -> P = x d_stack^T
+        w_fwd_i [N_i, Cin + r']   = [W_i | s_i U_i]                                       -> y_i = [x | P_i] w_fwd_i^T
+        u_t_i   [r', N_i]         = U_i^T                                                 -> Q_i = dY_i U_i
+        w_bwd   [Cin, sum N + G r'] = [W_1^T ... W_G^T | s_1 D_1^T ... s_G D_G^T]        -> dX = [dY | Q] w_bwd^T
+    in `dtype`, rebuilt only when a source changes (`_version`): once per optimizer step."""
+    key = tuple((t.data_ptr(), t._version) for t in list(weights) + list(downs) + list(ups)) + tuple(float(s) for s in scales) + (dtype,)
+    if cache is not None and cache.get("key") == key:
+        return cache["w"]
+    r = downs[0].shape[0]
+    rp = lora_pad_rank(r, dtype)
+    cin = weights[0].shape[1]
+    dev = weights[0].device
+    with torch.no_grad():
+        d_stack = torch.zeros(len(downs) * rp, cin, dtype=dtype, device=dev)
+        w_fwd, u_t, d_scaled = [], [], torch.zeros(len(downs) * rp, cin, dtype=torch.float32, device=dev)
+        for i, (w, d, u, s) in enumerate(zip(weights, downs, ups, scales)):
+            d_stack[i * rp: i * rp + r] = d
+            d_scaled[i * rp: i * rp + r] = d.float() * s
+            wf = torch.zeros(w.shape[0], cin + rp, dtype=dtype, device=dev)
+            wf[:, :cin] = w
+            wf[:, cin: cin + r] = u.float() * s
+            w_fwd.append(wf)
+            ut = torch.zeros(rp, w.shape[0], dtype=dtype, device=dev)
+            ut[:r] = u.t()
+            u_t.append(ut)
+        w_bwd = torch.cat([torch.cat([w.to(dtype) for w in weights], dim=0), d_scaled.to(dtype)], dim=0).t().contiguous()
+    out = dict(d_stack=d_stack, w_fwd=w_fwd, u_t=u_t, w_bwd=w_bwd, r=r, rp=rp)
+    if cache is not None:
+        cache["key"], cache["w"] = key, out
+    return out
+
+
+class _LoRALinear(torch.autograd.Function):
+    """`y = [x W_i^T + s_i U_i D_i x]_i + b + residual` for a group of frozen projections W_i sharing the input x, with trainable LoRA
+    factors D_i [r, Cin] / U_i [N_i, r] (fp32 masters).  The LoRA branch stays inside the fp32 accumulation of the projection GEMM:
+        forward   P = x D_stack^T;  y_i = [x | P_i] [W_i | s_i U_i]^T  (+ bias, residual in the epilogue)
+        backward  Q_i = dY_i U_i;   dX = [dY | Q] [W^T | s D^T]^T;   dU_i = s_i dY_i^T P_i;   dD_i = s_i Q_i^T X
+    (a merged bf16 weight W + s U D would lose every update below half an ulp of W).  The two weight-gradient reductions of the group
+    are ONE `fmc_linear_wgrad_bf16` launch."""
+
+    @staticmethod
+    def forward(ctx, x, bias, residual, spec, *factors):
+        G = len(spec["weights"])
+        downs, ups = factors[:G], factors[G:]
+        w = lora_group_weights(spec["weights"], downs, ups, spec["scales"], x.dtype, spec.get("cache"))
+        cin = x.shape[-1]
+        x2d = x if (x.ndim == 2 and not x.is_contiguous()) else x.reshape(-1, cin)     # (a 2-D row-strided view is read in place)
+        M = x2d.shape[0]
+        rp = w["rp"]
+        with torch.no_grad():
+            P = _lora_gemm(x2d, w["d_stack"])                                          # [M, G r']
+            ns = [wi.shape[0] for wi in spec["weights"]]
+            res2d = None if residual is None else residual.reshape(M, sum(ns))
+            if G == 1:
+                y = _lora_gemm(x2d, w["w_fwd"][0], bias, res2d, x2=P)
+            else:
+                assert bias is None and residual is None
+                y = torch.empty(M, sum(ns), dtype=x.dtype, device=x.device)
+                off = 0
+                for i in range(G):
+                    _lora_gemm(x2d, w["w_fwd"][i], x2=P[:, i * rp:(i + 1) * rp], out=y[:, off: off + ns[i]])
+                    off += ns[i]
+        ctx.save_for_backward(x2d, P)
+        ctx.spec, ctx.w, ctx.ns, ctx.x_shape = spec, w, ns, x.shape
+        ctx.has_res = residual is not None and residual.requires_grad
+        ctx.factor_dtypes = [f.dtype for f in factors]
+        return y.view(*x.shape[:-1], sum(ns))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, P = ctx.saved_tensors
+        w, ns, spec = ctx.w, ctx.ns, ctx.spec
+        G, r, rp = len(ns), w["r"], w["rp"]
+        M = x2d.shape[0]
+        dy2 = dy.reshape(M, sum(ns)) if dy.is_contiguous() else dy.contiguous().view(M, sum(ns))
+        if dy2.dtype != x2d.dtype:
+            dy2 = dy2.to(x2d.dtype)
+        with torch.no_grad():
+            Q = torch.empty(M, G * rp, dtype=x2d.dtype, device=x2d.device)
+            off = 0
+            for i in range(G):
+                _lora_gemm(dy2[:, off: off + ns[i]], w["u_t"][i], out=Q[:, i * rp:(i + 1) * rp])
+                off += ns[i]
+            dx = None
+            if ctx.needs_input_grad[0]:
+                dx = _lora_gemm(dy2, w["w_bwd"], x2=Q).view(ctx.x_shape)
+            scales = spec["scales"]
+            probs, off = [], 0
+            for i in range(G):                                                  # dU_i = s_i dY_i^T P_i
+                probs.append((dy2[:, off: off + ns[i]], P[:, i * rp: i * rp + r], scales[i], None, False))
+                off += ns[i]
+            if all(s == scales[0] for s in scales):                             # dD = s Q^T X, one problem for the stacked factors
+                probs.append((Q, x2d, scales[0], None, False))
+            else:
+                probs += [(Q[:, i * rp:(i + 1) * rp], x2d, scales[i], None, False) for i in range(G)]
+            g = linear_wgrad_group(probs)
+            dus = g[:G]
+            if len(g) == G + 1:
+                dds = [g[G][i * rp: i * rp + r] for i in range(G)]
+            else:
+                dds = [t[:r] for t in g[G:]]
+        grads = [t.to(dt) for t, dt in zip(dds + dus, ctx.factor_dtypes)]
+        return (dx, None, dy if ctx.has_res else None, None, *grads)
+
+
+def lora_linear(x: torch.Tensor, weights, downs, ups, scales, bias: Optional[torch.Tensor] = None,
+                residual: Optional[torch.Tensor] = None, cache: Optional[dict] = None) -> torch.Tensor:
+    """The group of LoRA projections `[x W_i^T + s_i up_i(down_i(x))]_i` (concatenated along the last dim) + bias + residual, trainable
+    in `downs` / `ups`, differentiable in x and the residual; `weights` are the frozen base weights (see `_LoRALinear`).  `cache`: a dict
+    the caller keeps, for the derived bf16 weights of this group."""
+    spec = dict(weights=list(weights), scales=[float(s) for s in scales], cache=cache)
+    return _LoRALinear.apply(x, bias, residual, spec, *downs, *ups)

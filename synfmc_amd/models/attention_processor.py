@@ -128,14 +128,45 @@ class LoRAAttnProcessor(nn.Module):
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  pose_feature=None, scale=None, temporal: bool = False, _residual=None):
-        _require_frozen(self)
         attn.prepare_attention_mask(attention_mask, 0, 0)
         s = resolve_lora_scale(self, scale)
         shape4 = hidden_states.shape if (hidden_states.ndim == 4 and not temporal) else None
         x = _tok(hidden_states) if not temporal else hidden_states
-        out = _attention_core(attn, x, encoder_hidden_states, temporal, lora=self, lora_scale=s,
-                              residual=_fusable(attn, _residual, shape4), text_context=encoder_hidden_states is not None)
+        if _lora_trains(self):
+            out = _lora_train_core(attn, self, x, encoder_hidden_states, temporal, s, _fusable(attn, _residual, shape4))
+        else:
+            out = _attention_core(attn, x, encoder_hidden_states, temporal, lora=self, lora_scale=s,
+                                  residual=_fusable(attn, _residual, shape4), text_context=encoder_hidden_states is not None)
         return _finish(attn, out, hidden_states, shape4)
+
+
+def _lora_trains(proc: nn.Module) -> bool:
+    return torch.is_grad_enabled() and any(p.requires_grad for n, p in proc.named_parameters() if "_lora" in n)
+
+
+def _lora_train_core(attn, lora, q_in, kv_in, temporal: bool, s: float, residual=None):
+    """The attention of a processor whose LoRA trains (FMC stage 1; stage 3 with `train_image_lora`): the same chain as `_attention_core`,
+    with every projection an un-merged `hip_ops.lora_linear` group -- q | k | v of self attention share one input, k | v of the text
+    another -- so the LoRA branch rides in the fp32 accumulation of the projection GEMMs and its factor gradients come out of
+    `fmc_linear_wgrad_bf16`.  The base weights stay frozen (`Attention.fused_weights` refuses a LoRA on trainable ones)."""
+    assert not any(p.requires_grad for p in (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_out[0].weight)), \
+        "a LoRA on trainable base weights is not a configuration the reference uses"
+    cache = lora.__dict__.setdefault("_train_cache", {})
+    layers = [lora.to_q_lora, lora.to_k_lora, lora.to_v_lora, lora.to_out_lora]
+    scale = [s * (l.network_alpha / l.rank if l.network_alpha is not None else 1.0) for l in layers]
+
+    def group(x, idx, weights, name, bias=None, res=None):
+        return K.lora_linear(x, weights, [layers[i].down.weight for i in idx], [layers[i].up.weight for i in idx], [scale[i] for i in idx],
+                             bias=bias, residual=res, cache=cache.setdefault(name, {}))
+    if kv_in is None:
+        qkv = group(q_in, (0, 1, 2), [attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], "qkv")
+        o = K.self_attention_qkv(qkv, attn.heads, attn.scale, temporal)
+    else:
+        assert not temporal
+        q = group(q_in, (0,), [attn.to_q.weight], "q")
+        kv = group(_tok(kv_in), (1, 2), [attn.to_k.weight, attn.to_v.weight], "kv")
+        o = K.cross_attention_q_kv(q, kv, attn.heads, attn.scale)
+    return group(o, (3,), [attn.to_out[0].weight], "out", bias=attn.to_out[0].bias, res=residual)
 
 
 _NO_SCALE = object()
@@ -152,10 +183,10 @@ def resolve_lora_scale(proc, scale=_NO_SCALE) -> float:
 
 
 def _require_frozen(proc: nn.Module) -> None:
-    if torch.is_grad_enabled() and any(p.requires_grad for n, p in proc.named_parameters() if "_lora" in n):
+    if _lora_trains(proc):
         raise NotImplementedError(
-            "the gfx950 path merges LoRA into the projection weights; training the LoRA itself (FMC stage 1, a 2-D "
-            "U-Net, out of scope) is not supported -- call `.requires_grad_(False)` on the LoRA layers")
+            "the motion-module LoRA (LORAPoseAdaptorAttnProcessor) is merged into the projection weights; training it is not supported "
+            "-- call `.requires_grad_(False)` on its LoRA layers (the spatial Domain LoRA of LoRAAttnProcessor trains)")
 
 
 class _PoseMerge:

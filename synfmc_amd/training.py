@@ -297,15 +297,18 @@ def optimizer_update(trainable: Iterable[torch.nn.Parameter], optimizer, reducer
 
 def stage3_training_step(pose_adaptor, omcm, noise_scheduler, optimizer, reducer: Optional[GradAllReducer], latents,
                          noise, timesteps, encoder_hidden_states, plucker_embedding, traj_features_fn, obj_masks,
-                         sd_loss_weight=0.3, mask_loss_weight=1.0, max_grad_norm=1.0):
+                         sd_loss_weight=0.3, mask_loss_weight=1.0, max_grad_norm=1.0, lora_params=None):
     """One OMC-stage optimisation step (train_cam_obj_ctrl.py:802-943 minus data loading, VAE and CLIP).
 
     `traj_features_fn()` must run the (trainable) Adapter, e.g. `lambda: get_traj_features_v2(infos, masks, omcm, ...)`.
-    Returns the loss value (a 0-d tensor)."""
+    `lora_params` (`train_image_lora`, :397-406): the Domain-LoRA parameters trained along (`lora_trainable_parameters`); their
+    gradients are clipped as a group of their own (:924-927).  Returns the loss value (a 0-d tensor)."""
     loss = stage3_forward_backward(pose_adaptor, noise_scheduler, latents, noise, timesteps, encoder_hidden_states,
                                    plucker_embedding, traj_features_fn, obj_masks, sd_loss_weight, mask_loss_weight)
     if reducer is not None:
         reducer.finish()
+    if lora_params is not None:
+        torch.nn.utils.clip_grad_norm_([p for p in lora_params if p.requires_grad and p.grad is not None], max_grad_norm)
     optimizer_update(omcm.parameters(), optimizer, reducer, max_grad_norm)
     return loss
 
@@ -327,6 +330,51 @@ def stage2_training_step(pose_adaptor, trainable: Iterable[torch.nn.Parameter], 
     model_pred = pose_adaptor(noisy_latents, timesteps, encoder_hidden_states=encoder_hidden_states,
                               pose_embedding=plucker_embedding)
     loss = masked_mse_loss(model_pred, noise, obj_masks, sd_loss_weight, mask_loss_weight, invert=True)
+    loss.backward()
+    if reducer is not None:
+        reducer.finish()
+    optimizer_update(trainable, optimizer, reducer, max_grad_norm)
+    return loss.detach()
+
+
+# ---- FMC stage 1: the Domain LoRA (train_image_lora.py) --------------------------------------------------------------------
+def _spatial_lora_parameters(unet):
+    return [(f"{name}.{k}", p) for name, proc in unet.attn_processors.items() if isinstance(proc, torch.nn.Module)
+            for k, p in proc.named_parameters() if "_lora." in k]
+
+
+def lora_trainable_parameters(unet) -> List[torch.nn.Parameter]:
+    """The Domain-LoRA factors of the spatial attention processors (`LoRAAttnProcessor`, attn1 / attn2 of every transformer block;
+    train_image_lora.py:170-180): turned into fp32 master parameters that require grad, and returned.  Nothing else changes: the
+    motion-module LoRA and every other parameter keep their dtype and `requires_grad`."""
+    params = []
+    for _, p in _spatial_lora_parameters(unet):
+        if p.dtype != torch.float32:
+            p.data = p.data.float()
+        p.requires_grad_(True)
+        params.append(p)
+    if not params:
+        raise ValueError("the U-Net has no spatial LoRA processors (set_image_layer_lora / add_spatial_lora)")
+    return params
+
+
+def lora_state_dict(unet) -> dict:
+    """The Domain-LoRA checkpoint in the key format of the reference's `AttnProcsLayers(unet.attn_processors).state_dict()`
+    (train_image_lora.py:178, :392), e.g. `down_blocks.0.attentions.0.transformer_blocks.0.attn1.processor.to_q_lora.down.weight`:
+    it loads into the stage-2 / stage-3 U-Nets with `load_state_dict(..., strict=False)` and no unexpected keys
+    (train_cam_obj_ctrl.py:253-261)."""
+    return {name: p.detach().clone() for name, p in _spatial_lora_parameters(unet)}
+
+
+def stage1_training_step(unet, trainable: Iterable[torch.nn.Parameter], noise_scheduler, optimizer, reducer: Optional[GradAllReducer],
+                         latents, noise, timesteps, encoder_hidden_states, max_grad_norm=1.0):
+    """One Domain-LoRA optimisation step (train_image_lora.py:320-381 minus data loading, VAE and CLIP): `add_noise`, the
+    epsilon-target MSE in fp32, clip, step, zero.  latents / noise `[B, 4, h, w]`, timesteps `[B]`, encoder_hidden_states `[B, 77, D]`.
+    The images run as clips of one frame through the 3-D U-Net built without motion modules (`unet_kwargs(..., motion=False)`,
+    loadable with `from_pretrained_2d`): per frame the arithmetic of the reference's `UNet2DConditionModel`.  Returns the loss."""
+    noisy_latents = noise_scheduler.add_noise(latents, noise, timesteps)
+    model_pred = unet(noisy_latents.unsqueeze(2), timesteps, encoder_hidden_states).sample.squeeze(2)
+    loss = F.mse_loss(model_pred.float(), noise.float(), reduction="mean")
     loss.backward()
     if reducer is not None:
         reducer.finish()
