@@ -64,7 +64,7 @@ int64_t fmc_groupnorm_workspace_bytes(int N, int C, int G);
 int fmc_groupnorm_silu_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats,
                            void* workspace, int N, int HW, int C, int G, float eps, int act, int dtype,
                            const void* x2, int C1, void* stream);
-/* dX of the above (frozen gamma/beta: the only case on the FMC training path).
+/* dX of the above (frozen gamma/beta; fmc_groupnorm_silu_bwd_params below also returns their gradients).
  *   dy, x, dx : [N, HW, C]; stats from the forward; act as in the forward. */
 int fmc_groupnorm_silu_bwd(const void* dy, const void* x, void* dx, const float* gamma, const float* beta,
                            const float* stats, void* workspace, int N, int HW, int C, int G, int act,
@@ -479,6 +479,25 @@ int fmc_layernorm_bwd_add(const void* dy, const void* x, const float* gamma, voi
                           int64_t M, int C, float eps, int dtype, void* stream);
 int fmc_groupnorm_silu_bwd_add(const void* dy, const void* x, void* dx, const float* gamma, const float* beta, const float* stats,
                                void* workspace, int N, int HW, int C, int G, int act, const void* addend, int dtype, void* stream);
+/* GroupNorm(+SiLU) backward WITH the affine gradients (the motion modules' `norm` under `train_mm`, train_cam_ctrl.py:289-302).  With
+ * z = gamma * xh + beta, xh = (x - mean) * rstd, dz = dy * act'(z):
+ *     dgamma[c] = sum_{n, s} dz * xh,   dbeta[c] = sum_{n, s} dz          (fp32 [C]; accumulate != 0 adds to what is there)
+ *   dx : as fmc_groupnorm_silu_bwd_add (same addend, SAME BITS), or NULL: the dX pass is skipped (a norm whose input needs no gradient).
+ *   The statistics pass of the dX-only backward also emits per-(sample, split, channel) partials of (dz, dz * xh) from the registers
+ *   it already holds -- x and dy are read once, as there -- and a second kernel sums them in a fixed order: bit-reproducible.
+ *   workspace: fp32 scratch of fmc_groupnorm_silu_bwd_params_workspace_bytes(N, HW, C, G) bytes, 16-byte aligned.  bf16 / fp32. */
+int64_t fmc_groupnorm_silu_bwd_params_workspace_bytes(int N, int HW, int C, int G);
+int fmc_groupnorm_silu_bwd_params(const void* dy, const void* x, void* dx, float* dgamma, float* dbeta, const float* gamma,
+                                  const float* beta, const float* stats, const void* addend, int accumulate, void* workspace,
+                                  int N, int HW, int C, int G, int act, int dtype, void* stream);
+/* Column sum of a token matrix (bias gradients of trainable projections):
+ *     out[n] = alpha * sum_{m < M} x[m][n]   (+ out[n] when accumulate != 0),   out fp32 [N]
+ *   x bf16 / fp32 [M, N] with rows `ld` >= N elements apart (a column slice of a wider tensor is fine), no alignment requirement.
+ *   The rows are split over workgroups by a rule that depends on (M, N) alone; the fp32 partials go to `workspace`
+ *   (fmc_column_sum_workspace_bytes(M, N) bytes) and a second kernel sums them in a fixed order: bit-reproducible. */
+int64_t fmc_column_sum_workspace_bytes(int64_t M, int N);
+int fmc_column_sum(const void* x, float* out, int64_t M, int N, int64_t ld, float alpha, int accumulate, void* workspace, int dtype,
+                   void* stream);
 /* dX [M, 2*Cff] of fmc_geglu_fwd from dy [M, Cff] and the forward input x. */
 int fmc_geglu_bwd(const void* dy, const void* x, void* dx, int64_t M, int Cff, int dtype, void* stream);
 /* dQ, dK, dV of fmc_spatial_attn_fwd.  o / lse are the forward's outputs, d_o has o's strides, dvec is a

@@ -52,12 +52,16 @@ __device__ __forceinline__ float dsilu_f(float z) {
 // pass 1: per (sample, split, group) partial sums.  MODE 0: (sum x, sum x^2).
 // MODE 1 (backward): with z = a*x+b, dxh = dy*act'(z)*gamma, xh = (x-mean)*rstd:
 //                    (sum dxh, sum dxh*xh).
+// MODE 2 (backward with affine gradients): the MODE 1 group partials, same bits (MODE 1's fused multiply-adds written out: see the
+//                    loop; the GPU tests compare the dX bits with the dX-only backward's), and per (sample, split, CHANNEL) with
+//                    dz = dy*act'(z): (sum dz, sum dz*xh) -> cpart [N][splits][C][2], from the same registers (x, dy read once).
 // --------------------------------------------------------------------------------------------
 template <typename T, int MODE>
 __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ gamma,
                                   const float* __restrict__ beta, const float* __restrict__ stats,
                                   float* __restrict__ part, int HW, int C, int G, int tpr, int rpi,
-                                  int rows_per_split, int act, const T* __restrict__ x2 = nullptr, int C1 = 0) {
+                                  int rows_per_split, int act, const T* __restrict__ x2 = nullptr, int C1 = 0,
+                                  float* __restrict__ cpart = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][rpi][C]
     const int n = blockIdx.y, s = blockIdx.x, nsplit = gridDim.x;
     const int tid = threadIdx.x;
@@ -69,7 +73,7 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
     if (row1 > HW) row1 = HW;
 
     float aco[8], bco[8], mu[8], rs[8], gm[8];
-    if (MODE == 1) {
+    if (MODE >= 1) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             int c = c0 + i, g = c / cpg;
@@ -80,9 +84,9 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
             bco[i] = beta[c] - mu[i] * aco[i];
         }
     }
-    float s1[8], s2[8];
+    float s1[8], s2[8], t1[8], t2[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s1[i] = s2[i] = 0.f;
+    for (int i = 0; i < 8; ++i) s1[i] = s2[i] = t1[i] = t2[i] = 0.f;
     // two-source input (channels [0, C1) from x, [C1, C) from x2): the channel concat of the up blocks is never written
     int xs = C;
     const T* xb = x + (size_t)n * HW * C + c0;
@@ -90,7 +94,7 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
         xs = c0 < C1 ? C1 : C - C1;
         xb = c0 < C1 ? x + (size_t)n * HW * C1 + c0 : x2 + (size_t)n * HW * (C - C1) + (c0 - C1);
     }
-    const T* dyb = (MODE == 1) ? dy + (size_t)n * HW * C + c0 : nullptr;
+    const T* dyb = (MODE >= 1) ? dy + (size_t)n * HW * C + c0 : nullptr;
     if (MODE == 0) {
         for (int r = row0 + rsub; r < row1; r += GN_U * rpi) {    // GN_U rows per trip, all loads first
             float v4[GN_U][8];
@@ -107,7 +111,7 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
             }
         }
     }
-    for (int r = row0 + rsub; MODE == 1 && r < row1; r += rpi) {
+    for (int r = row0 + rsub; MODE >= 1 && r < row1; r += rpi) {
         float v[8];
         Vec8<T>::load(xb + (size_t)r * C, v);
         if (MODE == 0) {
@@ -122,8 +126,18 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
                 float dz = act ? d[i] * dsilu_f(z) : d[i];
                 float dxh = dz * gm[i];
                 float xh = (v[i] - mu[i]) * rs[i];
-                s1[i] += dxh;
-                s2[i] += dxh * xh;
+                if constexpr (MODE == 2) {
+                    // MODE 1's rounding spelled out, so that dX from these group sums has the dX-only backward's bits: the
+                    // compiler contracts MODE 1's sums to s1 = fma(dz, gamma, s1) and s2 = fma(rn(dz * gamma), xh, s2), but left to
+                    // itself pairs MODE 2's into unfused packed multiplies and adds
+                    s1[i] = __builtin_fmaf(dz, gm[i], s1[i]);
+                    s2[i] = __builtin_fmaf(dxh, xh, s2[i]);
+                    t1[i] += dz;
+                    t2[i] = __builtin_fmaf(dz, xh, t2[i]);
+                } else {
+                    s1[i] += dxh;
+                    s2[i] += dxh * xh;
+                }
             }
         }
     }
@@ -149,6 +163,114 @@ __global__ void gn_partial_kernel(const T* __restrict__ x, const T* __restrict__
         p[0] = a;
         p[1] = b;
     }
+    if constexpr (MODE == 2) {           // the per-channel totals of (dz, dz*xh) through the same LDS planes, once the groups are out
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            l1[rsub * C + c0 + i] = t1[i];
+            l2[rsub * C + c0 + i] = t2[i];
+        }
+        __syncthreads();
+        for (int c = tid; c < C; c += blockDim.x) {
+            float a = 0.f, b = 0.f;
+            for (int r = 0; r < rpi; ++r) { a += l1[r * C + c]; b += l2[r * C + c]; }
+            float* p = cpart + (((size_t)n * nsplit + s) * C + c) * 2;
+            p[0] = a;
+            p[1] = b;
+        }
+    }
+}
+
+// affine gradients: dbeta[c] = sum over (sample, split) of cpart[.][.][c][0], dgamma[c] = ... [1]; one thread per channel walks the
+// partials in a fixed order (bit-reproducible), in fp64
+__global__ __launch_bounds__(256) void gn_param_combine_kernel(const float* __restrict__ cpart, float* __restrict__ dgamma,
+                                                                float* __restrict__ dbeta, int nparts, int C, int accumulate) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < nparts; ++k) {
+        const float* p = cpart + ((size_t)k * C + c) * 2;
+        a += (double)p[0];
+        b += (double)p[1];
+    }
+    dbeta[c] = accumulate ? dbeta[c] + (float)a : (float)a;
+    dgamma[c] = accumulate ? dgamma[c] + (float)b : (float)b;
+}
+
+// --------------------------------------------------------------------------------------------
+// column sum of a row-strided token matrix (bias gradients): out[n] = alpha * sum_m x[m][n] (+ out[n]).  Workgroup = 64 columns x
+// 4 row lanes over one split of the rows; each split writes fp32 partials [splits][N], a second kernel sums them in split order.
+// --------------------------------------------------------------------------------------------
+constexpr int CSUM_COLS = 64, CSUM_LANES = 4, CSUM_U = 4, CSUM_MAX_SPLIT = 256;
+
+struct CsumGeom {
+    int splits;
+    int64_t rows_per_split;
+};
+
+CsumGeom csum_geom(int64_t M, int N) {
+    CsumGeom g;
+    const int64_t cb = (N + CSUM_COLS - 1) / CSUM_COLS;
+    int64_t want = (1024 + cb - 1) / cb;                                 // ~1024 workgroups
+    const int64_t most = (M + 127) / 128;                                // >= 128 rows (32 per thread) per workgroup
+    if (want > most) want = most;
+    if (want > CSUM_MAX_SPLIT) want = CSUM_MAX_SPLIT;
+    if (want < 1) want = 1;
+    g.rows_per_split = (M + want - 1) / want;
+    g.splits = (int)((M + g.rows_per_split - 1) / g.rows_per_split);     // no empty split
+    return g;
+}
+
+template <typename T>
+__device__ __forceinline__ float ld_elem(const T* p);
+template <>
+__device__ __forceinline__ float ld_elem<bf16_t>(const bf16_t* p) { return bf2f(*p); }
+template <>
+__device__ __forceinline__ float ld_elem<float>(const float* p) { return *p; }
+
+template <typename T>
+__global__ __launch_bounds__(CSUM_COLS * CSUM_LANES) void column_sum_partial_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t M,
+                                                                                    int N, int64_t ld, int64_t rows_per_split) {
+    __shared__ float sh[CSUM_LANES][CSUM_COLS];
+    const int col = threadIdx.x % CSUM_COLS, lane = threadIdx.x / CSUM_COLS;
+    const int n = blockIdx.x * CSUM_COLS + col, s = blockIdx.y;
+    const int64_t r0 = (int64_t)s * rows_per_split;
+    int64_t r1 = r0 + rows_per_split;
+    if (r1 > M) r1 = M;
+    float acc = 0.f;
+    if (n < N) {
+        const T* xc = x + n;
+        for (int64_t r = r0 + lane; r < r1; r += CSUM_U * CSUM_LANES) {     // CSUM_U rows per trip, loads first (clamped, branch-free)
+            float v[CSUM_U];
+#pragma unroll
+            for (int u = 0; u < CSUM_U; ++u) {
+                const int64_t rr = r + u * CSUM_LANES;
+                v[u] = ld_elem<T>(xc + (rr < r1 ? rr : r1 - 1) * ld);
+            }
+#pragma unroll
+            for (int u = 0; u < CSUM_U; ++u) acc += (r + u * CSUM_LANES) < r1 ? v[u] : 0.f;
+        }
+    }
+    sh[lane][col] = acc;
+    __syncthreads();
+    if (lane == 0 && n < N) {
+        float t = sh[0][col];
+#pragma unroll
+        for (int l = 1; l < CSUM_LANES; ++l) t += sh[l][col];
+        part[(size_t)s * N + n] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void column_sum_combine_kernel(const float* __restrict__ part, float* __restrict__ out, int splits, int N,
+                                                                 float alpha, int accumulate) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    double a = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < splits; ++k) a += (double)part[(size_t)k * N + n];
+    const float v = (float)((double)alpha * a);
+    out[n] = accumulate ? out[n] + v : v;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1115,6 +1237,72 @@ extern "C" int fmc_groupnorm_silu_bwd(const void* dy, const void* x, void* dx, c
                                       const float* stats, void* workspace, int N, int HW, int C, int G, int act,
                                       int dtype, void* stream) {
     return fmc_groupnorm_silu_bwd_add(dy, x, dx, gamma, beta, stats, workspace, N, HW, C, G, act, nullptr, dtype, stream);
+}
+
+// the group partials of fmc_groupnorm_silu_bwd_add, then the per-(sample, split, channel) affine partials
+extern "C" int64_t fmc_groupnorm_silu_bwd_params_workspace_bytes(int N, int HW, int C, int G) {
+    if (N <= 0 || HW <= 0 || C <= 0 || C % 8 || C > 8 * 512 || G <= 0) return -1;
+    return fmc_groupnorm_workspace_bytes(N, C, G) + (int64_t)N * gn_geom(HW, C).split * C * 2 * (int64_t)sizeof(float);
+}
+
+extern "C" int fmc_groupnorm_silu_bwd_params(const void* dy, const void* x, void* dx, float* dgamma, float* dbeta, const float* gamma,
+                                             const float* beta, const float* stats, const void* addend, int accumulate, void* workspace,
+                                             int N, int HW, int C, int G, int act, int dtype, void* stream) {
+    if (int rc = gn_check(x, dx ? dx : x, N, HW, C, G, dtype)) return rc;
+    if (!dy || !gamma || !beta || !stats || !workspace || !dgamma || !dbeta)
+        FMC_FAIL(FMC_E_NULL, "groupnorm_bwd_params: NULL argument");
+    if (!fmc_aligned16(dy) || (addend && !fmc_aligned16(addend)) || !fmc_aligned16(workspace))
+        FMC_FAIL(FMC_E_ALIGN, "groupnorm_bwd_params: dy / addend / workspace must be 16-byte aligned");
+    if (addend && !dx) FMC_FAIL(FMC_E_NULL, "groupnorm_bwd_params: an addend needs dx");
+    GnGeom g = gn_geom(HW, C);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(g.split, N), block(g.block);
+    size_t lds = (size_t)2 * g.rpi * C * sizeof(float);
+    float* part = (float*)workspace;
+    float* cpart = part + (size_t)fmc_groupnorm_workspace_bytes(N, C, G) / sizeof(float);
+    // one statistics pass (x and dy read once) writes the group partials -- the dX-only backward's bits -- and the channel partials; the
+    // dX pass behind it consumes the former exactly as in fmc_groupnorm_silu_bwd_add
+    if (dtype == FMC_BF16) {
+        hipLaunchKernelGGL((gn_partial_kernel<bf16_t, 2>), grid, block, lds, st, (const bf16_t*)x, (const bf16_t*)dy,
+                           gamma, beta, stats, part, HW, C, G, g.tpr, g.rpi, g.rows_per_split, act, (const bf16_t*)nullptr, 0, cpart);
+        if (dx)
+            hipLaunchKernelGGL((gn_apply_bwd_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, gamma, beta,
+                               stats, part, HW, C, G, g.tpr, g.rpi, g.rows_per_split, act, (const bf16_t*)addend);
+    } else {
+        hipLaunchKernelGGL((gn_partial_kernel<float, 2>), grid, block, lds, st, (const float*)x, (const float*)dy, gamma,
+                           beta, stats, part, HW, C, G, g.tpr, g.rpi, g.rows_per_split, act, (const float*)nullptr, 0, cpart);
+        if (dx)
+            hipLaunchKernelGGL((gn_apply_bwd_kernel<float>), grid, block, 0, st, (const float*)dy, (const float*)x, (float*)dx, gamma, beta,
+                               stats, part, HW, C, G, g.tpr, g.rpi, g.rows_per_split, act, (const float*)addend);
+    }
+    hipLaunchKernelGGL(gn_param_combine_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)cpart, dgamma, dbeta, N * g.split, C,
+                       accumulate);
+    FMC_CHECK_LAUNCH("fmc_groupnorm_silu_bwd_params");
+    return 0;
+}
+
+extern "C" int64_t fmc_column_sum_workspace_bytes(int64_t M, int N) {
+    if (M <= 0 || N <= 0) return -1;
+    return (int64_t)csum_geom(M, N).splits * N * (int64_t)sizeof(float);
+}
+
+extern "C" int fmc_column_sum(const void* x, float* out, int64_t M, int N, int64_t ld, float alpha, int accumulate, void* workspace, int dtype,
+                              void* stream) {
+    if (!x || !out || !workspace) FMC_FAIL(FMC_E_NULL, "column_sum: NULL argument");
+    if (M <= 0 || N <= 0 || ld < N)
+        FMC_FAIL(FMC_E_SHAPE, "column_sum: need M >= 1, N >= 1, ld >= N (M=%lld N=%d ld=%lld)", (long long)M, N, (long long)ld);
+    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "column_sum: dtype %d", dtype);
+    CsumGeom g = csum_geom(M, N);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    dim3 grid((N + CSUM_COLS - 1) / CSUM_COLS, g.splits), block(CSUM_COLS * CSUM_LANES);
+    if (dtype == FMC_BF16)
+        hipLaunchKernelGGL((column_sum_partial_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, part, M, N, ld, g.rows_per_split);
+    else
+        hipLaunchKernelGGL((column_sum_partial_kernel<float>), grid, block, 0, st, (const float*)x, part, M, N, ld, g.rows_per_split);
+    hipLaunchKernelGGL(column_sum_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, st, (const float*)part, out, g.splits, N, alpha, accumulate);
+    FMC_CHECK_LAUNCH("fmc_column_sum");
+    return 0;
 }
 
 template <typename T, int NCH, int R>

@@ -130,7 +130,7 @@ class _GroupNormSiLU(torch.autograd.Function):
     def backward(ctx, dy):
         x, gamma, beta, stats = ctx.saved_tensors
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise NotImplementedError("fmc_groupnorm_silu_bwd computes dX only (gamma/beta are frozen on the FMC path)")
+            return (*_gn_param_backward(ctx, dy, None), None, None, None)
         dy = dy.contiguous()
         N, S, C = x.shape
         lib = _lib.load()
@@ -142,10 +142,39 @@ class _GroupNormSiLU(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
+def groupnorm_silu_bwd_params(dy, x, gamma, beta, stats, groups: int, act: bool, want_dx: bool = True, addend=None,
+                              dgamma=None, dbeta=None, accumulate: bool = False):
+    """(dX or None, dgamma, dbeta) of GroupNorm(+SiLU) over `[N, S, C]` tokens (`fmc_groupnorm_silu_bwd_params`): dX as
+    `fmc_groupnorm_silu_bwd_add` computes it (`addend` added), the affine gradients in fp32 `[C]` (written into `dgamma` / `dbeta`
+    when given, added to them with `accumulate`).  `want_dx=False` skips the dX pass."""
+    _dev(dy, x, gamma, beta, stats, addend)
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    assert x.is_contiguous() and dy.shape == x.shape and dy.dtype == x.dtype
+    assert (dgamma is None) == (dbeta is None), "pass both dgamma and dbeta or neither"
+    N, S, C = x.shape
+    lib = _lib.load()
+    dx = torch.empty_like(x) if want_dx else None
+    if dgamma is None:
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        accumulate = False
+    ws = _workspace(x.device, lib.fmc_groupnorm_silu_bwd_params_workspace_bytes(N, S, C, groups))
+    _lib.check(lib.fmc_groupnorm_silu_bwd_params(dy.data_ptr(), x.data_ptr(), _p(dx), dgamma.data_ptr(), dbeta.data_ptr(), gamma.data_ptr(),
+                                                 beta.data_ptr(), stats.data_ptr(), _p(addend), int(accumulate), ws.data_ptr(), N, S, C, groups,
+                                                 int(act), _dt(x), _stream()), "fmc_groupnorm_silu_bwd_params")
+    return dx, dgamma, dbeta
+
+
+def _gn_param_backward(ctx, dy, addend):
+    """The norm's gamma / beta train: (dX or None, dgamma, dbeta) from one statistics pass (+ the dX pass when x needs a gradient)."""
+    x, gamma, beta, stats = ctx.saved_tensors
+    dx, dg, db = groupnorm_silu_bwd_params(dy, x, gamma, beta, stats, ctx.groups, ctx.act,
+                                           want_dx=ctx.needs_input_grad[0] or addend is not None, addend=addend)
+    return dx, (dg.to(gamma.dtype) if ctx.needs_input_grad[1] else None), (db.to(beta.dtype) if ctx.needs_input_grad[2] else None)
+
+
 def _gn_backward(ctx, dy, addend):
     x, gamma, beta, stats = ctx.saved_tensors
-    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-        raise NotImplementedError("fmc_groupnorm_silu_bwd computes dX only (gamma/beta are frozen on the FMC path)")
     dy = dy.contiguous()
     N, S, C = x.shape
     lib = _lib.load()
@@ -177,11 +206,14 @@ class _GroupNormSiLUSkip(torch.autograd.Function):
         add = None
         if d_skip is not None:
             add = d_skip if d_skip.is_contiguous() else d_skip.contiguous()
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:          # trainable gamma / beta: the skip gradient rides in the same dX pass
+            return (*_gn_param_backward(ctx, dy, add), None, None, None)
         return _gn_backward(ctx, dy, add), None, None, None, None, None
 
 
 def groupnorm_silu_skip(x, gamma, beta, groups: int, eps: float, act: bool):
-    """(x for the skip connection, GroupNorm(+SiLU)(x)) -- one autograd node when x needs a gradient, the plain pair otherwise."""
+    """(x for the skip connection, GroupNorm(+SiLU)(x)) -- one autograd node when x needs a gradient, the plain pair otherwise.
+    Trainable gamma / beta (`train_mm`) get their gradients from either (`fmc_groupnorm_silu_bwd_params`)."""
     if torch.is_grad_enabled() and x.requires_grad and x.is_cuda and x.is_contiguous():
         return _GroupNormSiLUSkip.apply(x, gamma, beta, groups, eps, act)
     return x, groupnorm_silu(x, gamma, beta, groups, eps, act)
@@ -194,7 +226,7 @@ def groupnorm_silu(x, gamma, beta, groups: int, eps: float, act: bool, x2=None, 
     if (gn_tag is not None and x2 is None and groups == 32 and gn_tag[1] == x.shape[-1] and gn_tag[0].shape[0] == x.shape[0]
             and gn_tag[0].shape[1] <= 64 and not torch.is_grad_enabled()):       # (any split of the pixels: 160-row tiles, the halo conv's 10 x 32 tiles)
         return groupnorm_apply(x, gamma, beta, groups, eps, act, gn_tag[0])
-    if torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad)):
+    if torch.is_grad_enabled() and (x.requires_grad or (x2 is not None and x2.requires_grad) or gamma.requires_grad or beta.requires_grad):
         if x2 is not None:
             x = torch.cat([x, x2], dim=-1)
         return _GroupNormSiLU.apply(x, gamma, beta, groups, eps, act)
@@ -2634,6 +2666,68 @@ class _LinearFrozen(torch.autograd.Function):
 def linear_frozen(x, weight, bias=None, residual=None, alpha: float = 1.0):
     """`alpha * (x @ W^T + b) + residual` with frozen W, b; differentiable w.r.t. x and the residual."""
     return _LinearFrozen.apply(x, weight, bias, residual, alpha)
+
+
+def column_sum(x: torch.Tensor, alpha: float = 1.0, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """`alpha * x.sum(rows)` (+ out) in fp32 `[N]` for a bf16 / fp32 token matrix `[..., N]` (contiguous, or a 2-D row-strided view):
+    `fmc_column_sum`, bit-reproducible.  The bias gradient of a trainable projection."""
+    _dev(x, out)
+    M, ld = _rows2d(x)
+    N = x.shape[-1]
+    if out is None:
+        out, accumulate = torch.empty(N, dtype=torch.float32, device=x.device), False
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == N
+    lib = _lib.load()
+    ws = _workspace(x.device, lib.fmc_column_sum_workspace_bytes(M, N))
+    _lib.check(lib.fmc_column_sum(x.data_ptr(), out.data_ptr(), M, N, ld, float(alpha), int(accumulate), ws.data_ptr(), _dt(x), _stream()),
+               "fmc_column_sum")
+    return out
+
+
+class _LinearTrainable(torch.autograd.Function):
+    """`x W^T + b + residual` whose W and b train (the motion modules' proj_in / proj_out under `train_mm`).  `w_run` / `b_run` are what
+    the kernels read: for fp32 masters under bf16 activations their bf16 shadows (`layers.bf16_param`), else the parameters themselves.
+        forward   y = linear(x, w_run, b_run, residual)                     (the projection GEMMs of `linear`)
+        backward  dX = dY W (`linear_backward_data`);  dW = dY^T X (`linear_wgrad`, straight into fp32);  db = colsum(dY) (`column_sum`)
+    Gradients come back in each parameter's dtype; the residual's is dY."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, w_run, b_run):
+        with torch.no_grad():
+            y = linear(x, w_run, b_run, residual)
+        ctx.save_for_backward(x, w_run)
+        ctx.has_res = residual is not None and residual.requires_grad
+        ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_run = ctx.saved_tensors
+        dy = dy if dy.dtype == x.dtype else dy.to(x.dtype)
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        N, Kd = w_run.shape
+        dy2 = dy.view(-1, N)
+        x2 = x if (x.ndim == 2 and not x.is_contiguous()) else x.reshape(-1, Kd)
+        dx = dw = db = None
+        with torch.no_grad():
+            if ctx.needs_input_grad[0]:
+                dx = linear_backward_data(dy, w_run).view(x.shape)
+            if ctx.needs_input_grad[1]:
+                dw = linear_wgrad(dy2, x2).to(ctx.dtypes[0])
+            if ctx.needs_input_grad[2]:
+                db = column_sum(dy2).to(ctx.dtypes[1])
+        return dx, dw, db, (dy if ctx.has_res else None), None, None
+
+
+def linear_trainable(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                     w_run: Optional[torch.Tensor] = None, b_run: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`x @ weight^T + bias + residual`, differentiable in x, weight, bias and the residual, on this library's kernels (see
+    `_LinearTrainable`).  `w_run` / `b_run`: the weight / bias in x's dtype (cached bf16 shadows of fp32 masters); default: a cast per call."""
+    if w_run is None:
+        w_run = weight.detach() if weight.dtype == x.dtype else weight.detach().to(x.dtype)
+    if b_run is None and bias is not None:
+        b_run = bias.detach() if bias.dtype == x.dtype else bias.detach().to(x.dtype)
+    return _LinearTrainable.apply(x, weight, bias, residual, w_run, b_run)
 
 
 def conv3x3_weight_grad(x_nhwc: torch.Tensor, dy_nhwc: torch.Tensor) -> torch.Tensor:

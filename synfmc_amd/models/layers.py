@@ -58,6 +58,30 @@ def f32_param(mod: nn.Module, name: str) -> torch.Tensor:
     return hit[1]
 
 
+def bf16_param(mod: nn.Module, name: str, rounded_f32: bool = False) -> torch.Tensor:
+    """bf16 shadow of an fp32 master parameter (`train_mm`: the motion modules' proj_in / proj_out), what the bf16 kernels read.  Cached
+    on the module and refreshed IN PLACE (`copy_`) when the master's version moves: the copy bumps the shadow's own version, so every
+    derived-weight cache keyed on (data_ptr, _version) -- the GroupNorm fold, the ff_tail fold, the tile-major packs, W^T -- rebuilds.  (A
+    newly allocated shadow could land on a freed one's address with version 0 and hit those caches with stale weights.)  A parameter
+    that is not fp32 is returned as it is.  `rounded_f32`: the shadow's values as fp32 (a norm's gamma / beta, which the kernels take in
+    fp32: an fp32-master model then computes what the same model stored in bf16 computes)."""
+    p = getattr(mod, name)
+    if p is None or p.dtype != torch.float32:
+        return p if (p is None or not rounded_f32) else f32_param(mod, name)
+    cache = mod.__dict__.setdefault("_bf16_shadow", {})
+    hit = cache.get(name)
+    if hit is None or hit[1].shape != p.shape or hit[1].device != p.device:
+        hit = [None, torch.empty(p.shape, dtype=torch.bfloat16, device=p.device), torch.empty(p.shape, dtype=torch.float32, device=p.device)]
+        cache[name] = hit
+    key = (p.data_ptr(), p._version)
+    if hit[0] != key:
+        with torch.no_grad():
+            hit[1].copy_(p.detach())
+            hit[2].copy_(hit[1])
+        hit[0] = key
+    return hit[2] if rounded_f32 else hit[1]
+
+
 class GroupNorm(nn.GroupNorm):
     """nn.GroupNorm on a `[N, C, h, w]` tensor, optionally fused with SiLU (`fmc_groupnorm_silu_fwd`)."""
 

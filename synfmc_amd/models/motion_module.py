@@ -325,11 +325,21 @@ class TemporalTransformer3DModel(nn.Module):
         if not t.is_contiguous():
             t = t.contiguous()
         residual = t.view(b * f, h * w, c)
-        from .layers import NORM_SKIP
+        from .layers import NORM_SKIP, bf16_param
+        # `train_mm` (training.motion_module_trainable_parameters): norm / proj_in / proj_out are fp32 masters; the bf16 kernels read the
+        # projections through their bf16 shadows, with and without a gradient
+        shadow = residual.dtype == torch.bfloat16
+        wt = (lambda mod, name: bf16_param(mod, name) if shadow else getattr(mod, name))
+        w_in, b_in, w_out, b_out = wt(self.proj_in, "weight"), wt(self.proj_in, "bias"), wt(self.proj_out, "weight"), wt(self.proj_out, "bias")
+        # (a frozen or no-grad norm reads its gamma / beta bf16-rounded too: an fp32-master model computes what the bf16-stored one does)
+        gnp = (lambda name: bf16_param(self.norm, name, rounded_f32=True) if shadow else f32_param(self.norm, name))
+        if torch.is_grad_enabled() and any(p.requires_grad for p in (self.norm.weight, self.norm.bias, self.proj_in.weight, self.proj_in.bias,
+                                                                       self.proj_out.weight, self.proj_out.bias)):
+            return self._forward_train_mm(residual, b, f, h, w, c, w_in, b_in, w_out, b_out, encoder_hidden_states, attention_mask,
+                                          cross_attention_kwargs)
         if NORM_SKIP and torch.is_grad_enabled() and residual.requires_grad and residual.is_cuda:
             # the norm and the `+ residual` of proj_out as one autograd node (hip_ops.groupnorm_silu_skip)
-            residual, x = K.groupnorm_silu_skip(residual, f32_param(self.norm, "weight"), f32_param(self.norm, "bias"),
-                                                self.norm.num_groups, self.norm.eps, False)
+            residual, x = K.groupnorm_silu_skip(residual, gnp("weight"), gnp("bias"), self.norm.num_groups, self.norm.eps, False)
         else:
             x = None
         blk0 = self.transformer_blocks[0]
@@ -342,25 +352,41 @@ class TemporalTransformer3DModel(nn.Module):
             enc0 = blk0.attention_blocks[0].pos_encoder
             ln0 = blk0.norms[0].ln_spec() if enc0 is None else blk0.norms[0].ln_spec(enc0.table(), h * w, f)
         tag = getattr(hidden_states, "_fmc_gn", None)
-        if x is None and K.gn_fold_ok(residual, tag, self.norm.num_groups, self.proj_in.weight, ln0):
+        if x is None and K.gn_fold_ok(residual, tag, self.norm.num_groups, w_in, ln0):
             # the norm folded into per-image weights of proj_in: the normalised tensor is neither written nor read (hip_ops.linear_gnfold)
-            x = K.linear_gnfold(residual, tag, f32_param(self.norm, "weight"), f32_param(self.norm, "bias"), self.norm.num_groups, self.norm.eps,
-                                self.proj_in.weight, self.proj_in.bias, ln0)
+            x = K.linear_gnfold(residual, tag, gnp("weight"), gnp("bias"), self.norm.num_groups, self.norm.eps, w_in, b_in, ln0)
         else:
             if x is None:
-                x = K.groupnorm_silu(residual, f32_param(self.norm, "weight"), f32_param(self.norm, "bias"),
-                                     self.norm.num_groups, self.norm.eps, False, gn_tag=tag)
-            x = linear_op(x, self.proj_in.weight, self.proj_in.bias, ln=ln0)
+                x = K.groupnorm_silu(residual, gnp("weight"), gnp("bias"), self.norm.num_groups, self.norm.eps, False, gn_tag=tag)
+            x = linear_op(x, w_in, b_in, ln=ln0)
         x = K.carry_ln(x, x.view(b, f, h * w, -1))
         last = len(self.transformer_blocks) - 1
         for bi, block in enumerate(self.transformer_blocks):
             x = block(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask,
                       cross_attention_kwargs=cross_attention_kwargs,
                       # (the last block's feed-forward may take proj_out + residual into its own last launch: hip_ops.ff_tail)
-                      **({"tail": (self.proj_out.weight, self.proj_out.bias, residual, h * w)} if (bi == last and not torch.is_grad_enabled()) else {}))
+                      **({"tail": (w_out, b_out, residual, h * w)} if (bi == last and not torch.is_grad_enabled()) else {}))
         if not getattr(x, "_fmc_tail", False):
-            x = linear_op(x.view(b * f, h * w, -1), self.proj_out.weight, self.proj_out.bias, residual, gn_hw=h * w)
+            x = linear_op(x.view(b * f, h * w, -1), w_out, b_out, residual, gn_hw=h * w)
         return K.carry_gn(x, x.view(b, f, h, w, c).permute(0, 4, 1, 2, 3))   # (the next ResNet block / conv_norm_out opens with a GroupNorm)
+
+    def _forward_train_mm(self, residual, b, f, h, w, c, w_in, b_in, w_out, b_out, encoder_hidden_states, attention_mask,
+                          cross_attention_kwargs):
+        """Under a gradient with trainable norm / proj_in / proj_out (`train_mm`): the norm returns its affine gradients
+        (`fmc_groupnorm_silu_bwd_params`, also when the input needs none: the first motion module), the projections run on
+        `hip_ops.linear_trainable` (dW / db straight into the fp32 masters' dtype)."""
+        from .layers import NORM_SKIP
+        gamma, beta = f32_param(self.norm, "weight"), f32_param(self.norm, "bias")
+        if NORM_SKIP and residual.requires_grad and residual.is_cuda:
+            residual, x = K.groupnorm_silu_skip(residual, gamma, beta, self.norm.num_groups, self.norm.eps, False)
+        else:
+            x = K.groupnorm_silu(residual, gamma, beta, self.norm.num_groups, self.norm.eps, False)
+        x = K.linear_trainable(x, self.proj_in.weight, self.proj_in.bias, w_run=w_in, b_run=b_in)
+        x = x.view(b, f, h * w, -1)
+        for block in self.transformer_blocks:
+            x = block(x, encoder_hidden_states=encoder_hidden_states, attention_mask=attention_mask, cross_attention_kwargs=cross_attention_kwargs)
+        x = K.linear_trainable(x.reshape(b * f, h * w, -1), self.proj_out.weight, self.proj_out.bias, residual, w_run=w_out, b_run=b_out)
+        return x.view(b, f, h, w, c).permute(0, 4, 1, 2, 3)
 
 
 class VanillaTemporalModule(nn.Module):

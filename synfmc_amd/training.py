@@ -295,20 +295,31 @@ def optimizer_update(trainable: Iterable[torch.nn.Parameter], optimizer, reducer
         optimizer.zero_grad(set_to_none=True)
 
 
+def stage3_clip_groups(omcm, lora_params=None, mm_params=None) -> List[List[torch.nn.Parameter]]:
+    """The parameter groups stage 3 clips, each to `max_grad_norm` on its own (train_cam_obj_ctrl.py:921-927): the Adapter; with
+    `train_image_lora` every U-Net parameter that requires grad -- the Domain LoRA and, with `train_mm` too, the motion-module
+    parameters -- as ONE group.  With `train_mm` alone the motion-module gradients are not clipped at all."""
+    groups = [[p for p in omcm.parameters() if p.requires_grad]]
+    if lora_params is not None:
+        groups.append([p for p in list(lora_params) + list(mm_params or []) if p.requires_grad])
+    return groups
+
+
 def stage3_training_step(pose_adaptor, omcm, noise_scheduler, optimizer, reducer: Optional[GradAllReducer], latents,
                          noise, timesteps, encoder_hidden_states, plucker_embedding, traj_features_fn, obj_masks,
-                         sd_loss_weight=0.3, mask_loss_weight=1.0, max_grad_norm=1.0, lora_params=None):
+                         sd_loss_weight=0.3, mask_loss_weight=1.0, max_grad_norm=1.0, lora_params=None, mm_params=None):
     """One OMC-stage optimisation step (train_cam_obj_ctrl.py:802-943 minus data loading, VAE and CLIP).
 
     `traj_features_fn()` must run the (trainable) Adapter, e.g. `lambda: get_traj_features_v2(infos, masks, omcm, ...)`.
-    `lora_params` (`train_image_lora`, :397-406): the Domain-LoRA parameters trained along (`lora_trainable_parameters`); their
-    gradients are clipped as a group of their own (:924-927).  Returns the loss value (a 0-d tensor)."""
+    `lora_params` (`train_image_lora`, :397-406): the Domain-LoRA parameters trained along (`lora_trainable_parameters`).
+    `mm_params` (`train_mm`, :367-384): the motion-module parameters trained along (`motion_module_trainable_parameters`).  Clipping
+    follows `stage3_clip_groups`.  Returns the loss value (a 0-d tensor)."""
     loss = stage3_forward_backward(pose_adaptor, noise_scheduler, latents, noise, timesteps, encoder_hidden_states,
                                    plucker_embedding, traj_features_fn, obj_masks, sd_loss_weight, mask_loss_weight)
     if reducer is not None:
         reducer.finish()
-    if lora_params is not None:
-        torch.nn.utils.clip_grad_norm_([p for p in lora_params if p.requires_grad and p.grad is not None], max_grad_norm)
+    for group in stage3_clip_groups(omcm, lora_params, mm_params)[1:]:
+        torch.nn.utils.clip_grad_norm_([p for p in group if p.grad is not None], max_grad_norm)
     optimizer_update(omcm.parameters(), optimizer, reducer, max_grad_norm)
     return loss
 
@@ -380,3 +391,40 @@ def stage1_training_step(unet, trainable: Iterable[torch.nn.Parameter], noise_sc
         reducer.finish()
     optimizer_update(trainable, optimizer, reducer, max_grad_norm)
     return loss.detach()
+
+
+# ---- `train_mm`: the motion modules' norm / proj_in / proj_out (train_cam_ctrl.py:289-305, train_cam_obj_ctrl.py:367-384) ----------
+def _motion_module_parameters(unet):
+    """(name, parameter) exactly as the reference selects them: for every `TemporalTransformer3DModel` the prefixes `<module>.norm`,
+    `<module>.proj_in`, `<module>.proj_out`, and every U-Net parameter whose name CONTAINS one of them (a substring rule)."""
+    prefixes = []
+    for name, module in unet.named_modules():
+        if module.__class__.__name__ == "TemporalTransformer3DModel":
+            prefixes += [f"{name}.norm", f"{name}.proj_in", f"{name}.proj_out"]
+    out = []
+    for name, p in unet.named_parameters():
+        if any(pre in name for pre in prefixes):
+            out.append((name, p))
+    return out
+
+
+def motion_module_trainable_parameters(unet) -> List[torch.nn.Parameter]:
+    """The `train_mm` parameters (20 motion modules x 6 tensors at the SD-1.5 configs): turned into fp32 master parameters that require
+    grad, and returned.  The bf16 kernels read the projections through bf16 shadows (`layers.bf16_param`), so AdamW updates below half a
+    bf16 ulp of a weight accumulate in the master instead of being rounded away.  Nothing else changes."""
+    params = []
+    for _, p in _motion_module_parameters(unet):
+        if p.dtype != torch.float32:
+            p.data = p.data.float()
+        p.requires_grad_(True)
+        params.append(p)
+    if not params:
+        raise ValueError("the U-Net has no motion modules (TemporalTransformer3DModel)")
+    return params
+
+
+def motion_module_state_dict(unet) -> dict:
+    """The `train_mm` checkpoint: `...temporal_transformer.{norm,proj_in,proj_out}.{weight,bias}` keys, loadable into the U-Net with
+    `load_state_dict(..., strict=False)` and no unexpected keys.  (The reference's `mm_state_dict`, train_cam_ctrl.py:679-681, compares
+    state-dict keys with module names and therefore saves an empty dict; this writes what it evidently intends.)"""
+    return {name: p.detach().clone() for name, p in _motion_module_parameters(unet)}
