@@ -431,6 +431,23 @@ int fmc_conv3x3_halo4_tiles(int n_img, int H, int W, int Cout, int wide);
 int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb, const void* residual,
                            void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x,
                            float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes, int wide, void* stream);
+/* Phase mode of the nearest-2x upsample convolutions (inference, frozen filter).  conv3x3(upsample2x(src)) is four 2x2-tap convolutions of src, one
+ * per output parity (py, px): out[2i+py, 2j+px] = sum_{a,b} Wf[py][px][a][b] . src[i+py-1+a, j+px-1+b], src zero-padded by one pixel, with
+ * Wf[0][.][0] = w[0], Wf[0][.][1] = w[1] + w[2], Wf[1][.][0] = w[0] + w[1], Wf[1][.][1] = w[2] over the filter's rows (columns likewise with px, b):
+ * 4 taps per output instead of 9.  fmc_conv3x3_upfold_pack_weight folds the bf16 filter [Cout][3][3][Cin] (sums in fp32, rounded to bf16 once) into
+ * the consuming kernel's sub-tile order, `dst` = fmc_conv3x3_upfold_packed_bytes = 16 / 9 of the filter; tile_channels = 160 for
+ * fmc_conv3x3_halo_fold_bf16 and the wide halo4 form, 80 for the 4-wave halo4 form.  The *_fold_bf16 launches take the SOURCE size Hs x Ws (halo:
+ * Ws % 32 == 0; halo4: Ws % 8 == 0), write out [n_img, 2 Hs, 2 Ws, Cout] with bias in the epilogue (no temb / residual / GroupNorm operand path /
+ * split-K), and leave gn_partials [n_img, 4 * tiles (row blocks) per SOURCE image, 32, 2] of the rounded outputs.  Results differ from
+ * upsample2x = 1 of the launches above only by the one re-rounding of the folded filter; those stay the path for training and raw filters. */
+int64_t fmc_conv3x3_upfold_packed_bytes(int Cin, int Cout);
+int fmc_conv3x3_upfold_pack_weight(const void* w, void* dst, int Cin, int Cout, int tile_channels, void* stream);
+int fmc_conv3x3_halo_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout);
+int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
+                               float* gn_partials, void* stream);
+int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide);
+int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
+                                float* gn_partials, int wide, void* stream);
 int fmc_groupnorm_coef(const float* partials, int part_splits, const float* gamma, const float* beta, float* coef, float* stats, int N, int HW,
                        int C, int G, float eps, void* stream);
 

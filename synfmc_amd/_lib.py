@@ -77,6 +77,12 @@ SIGNATURES = {
     "fmc_conv3x3_halo4_tiles": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "fmc_conv3x3_halo4_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                        c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "fmc_conv3x3_upfold_packed_bytes": (c_int64, [c_int, c_int]),
+    "fmc_conv3x3_upfold_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_halo_fold_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fmc_conv3x3_halo4_fold_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "fmc_linear4_supported": (c_int, [c_int64, c_int, c_int, c_int64]),
     "fmc_vendor_linear_candidates": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int]),
     "fmc_vendor_linear_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p,

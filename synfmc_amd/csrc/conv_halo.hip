@@ -42,6 +42,7 @@ struct CHParams {
     const bf16_t* w;                        // packed filter, see fmc_conv3x3_halo_pack_weight
     const bf16_t* bias; const bf16_t* temb; const bf16_t* res; bf16_t* out;
     int n_img, H, W, cin, cout, ups;        // H, W = OUTPUT size; ups: x is [n_img, H/2, W/2, .] read through a nearest 2x upsample
+                                            // (phase mode: H, W = SOURCE size, the output is [n_img, 2 H, 2 W, cout]; tiles_n = 4 * cout / 160)
     int64_t temb_ld; int temb_div;
     const float* gn_coef; int gn_act;       // [n_img, cin, 2] (scale, shift) or NULL; gn_act: SiLU behind the affine map
     float* gn_part;                         // [n_img, tiles_y * tiles_x, 32, 2] partial (sum, sum of squares) of the ROUNDED outputs, or NULL
@@ -56,9 +57,18 @@ __device__ __forceinline__ float silu_fast(float z) { return z * __builtin_amdgc
 // halo staging pieces issued / written in sub-tile i of a chunk (18 sub-tiles): piece j is requested at LOAD(2 j) and written at LOAD(2 j + 3)
 constexpr int nh(int i) { return (i >= 0 && i <= 12 && (i & 1) == 0) ? 1 : 0; }
 
+// phase mode (PH): halo pieces requested in sub-tile i of a chunk of 8 sub-tiles: pieces 2 i, 2 i + 1 at LOAD(i), i = 0 .. 3, written at LOAD(i + 3)
+constexpr int nhp(int i) { return (i >= 0 && i <= 3) ? (i < 3 ? 2 : 1) : 0; }
+
 // GN: 0 = plain convolution, 1 = operand silu(x * scale + shift), 2 = operand x * scale + shift (compile-time: the normalisation has to sit in
 // the SAME basic block as the MFMAs it is interleaved with)
-template <int GN>
+//
+// PH: the PHASE MODE of the nearest-2x upsample convolutions.  A 3x3 convolution of a nearest-2x-upsampled image is four 2x2-tap convolutions of
+// the source image, one per output parity (py, px):  out[2 i + py, 2 j + px] = sum_{a, b in {0, 1}} Wf[py][px][a][b] . src[i + py - 1 + a, j + px - 1 + b]
+// (source zero-padded by one pixel; Wf = sums of the filter's rows / columns, fmc_conv3x3_halo_fold_pack_weight).  The kernel then tiles the
+// SOURCE pixels (the halo is that of a plain convolution at source resolution), the channel-tile index becomes (phase, channel tile), a 64-channel
+// chunk is 4 taps x 2 k-halves = 8 sub-tiles instead of 18 (2.25 x fewer MFMAs for the same outputs), and the epilogue stores pixel-shuffled.
+template <int GN, bool PH = false>
 __global__ __launch_bounds__(512, 2)
 void conv_halo_kernel(const CHParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -81,8 +91,11 @@ void conv_halo_kernel(const CHParams P) {
     const int tpi = P.tiles_y * P.tiles_x;
     const int img = tile_p / tpi, tin = tile_p - img * tpi;
     const int y0 = (tin / P.tiles_x) * TH, x0 = (tin % P.tiles_x) * TW;
-    const int n0 = tile_n * BN;
-    const int nchunk = P.cin >> 6, nsub = nchunk * 18;
+    constexpr int NS = PH ? 8 : 18;                          // sub-tiles per 64-channel chunk
+    const int tn1 = P.cout / BN;
+    const int phase = PH ? tile_n / tn1 : 0, py = phase >> 1, px_ = phase & 1;      // (PH: W tiles are [phase][channel tile])
+    const int n0 = (tile_n - phase * tn1) * BN;
+    const int nchunk = P.cin >> 6, nsub = nchunk * NS;
 
     // ---- halo staging: my seven (pixel, channel group) pieces --------------------------------------------------------------------------
     // block b = 8 j + wave holds halo pixels 8 b .. 8 b + 7 x 8 channel groups; lane = 8 g + p takes pixel p, channel group (p + g) & 7: the eight
@@ -173,7 +186,7 @@ void conv_halo_kernel(const CHParams P) {
 #pragma unroll
     for (int mb = 0; mb < 5; ++mb) {
         const int idx = wr * 80 + mb * 16 + l15, ty = idx >> 5, tx = idx & 31;
-        afrag[mb] = kq * PLANE + (ty * HWID + tx) * 16;
+        afrag[mb] = kq * PLANE + (ty * HWID + tx) * 16 + (PH ? (py * HWID + px_) * 16 : 0);      // (PH: tap (a, b) of phase (py, px) reads halo pixel + (py + a, px + b))
     }
 
     // ---- prologue: halo chunk 0, GroupNorm coefficients of chunks 0 and 1 ---------------------------------------------------------------------
@@ -210,8 +223,53 @@ void conv_halo_kernel(const CHParams P) {
         int cbuf = 0;                                        // halo (and coefficient) buffer of the chunk being multiplied
         float coef_next = 0.f;
         u32x4 hpk = {0u, 0u, 0u, 0u};
+        u32x4 hregp[3][2];                                   // (PH) staged pieces in flight
         for (int c = 0; c < nchunk; ++c) {
             const int abase = cbuf * HALO, nbuf = cbuf ^ 1;
+            if constexpr (PH) {
+                // the same phases with 8 sub-tiles per chunk: the seven halo pieces of the next chunk are requested two at a time in sub-tiles 0 .. 3 and
+                // written (untransformed: GN == 0) three sub-tiles later, the last ones at LOAD(6) -- one barrier pair ahead of the next chunk's first read
+                static_assert(!PH || GN == 0, "the phase mode has no GroupNorm operand path");
+                auto subp = [&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    constexpr int tap = i >> 1, hk = i & 1, ta = tap >> 1, tb = tap & 1;
+                    constexpr int aimm = hk * 4 * PLANE + (ta * HWID + tb) * 16;
+                    if constexpr (nhp(i - 3) >= 1) halo_store(2 * (i - 3), nbuf, hregp[(i - 3) % 3][0]);
+                    if constexpr (nhp(i - 3) == 2) halo_store(2 * (i - 3) + 1, nbuf, hregp[(i - 3) % 3][1]);
+                    {
+                        const unsigned char* Wp = smem_raw + wfrag + rd_slot * WSUB;
+#pragma unroll
+                        for (int nb = 0; nb < 5; ++nb) wf[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Wp + nb * 1024));
+#pragma unroll
+                        for (int mb = 0; mb < 5; ++mb)
+                            af[mb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem_raw + abase + afrag[mb] + aimm));
+                        rd_slot = rd_slot + 1 == NBW ? 0 : rd_slot + 1;
+                    }
+                    if constexpr (nhp(i) >= 1) halo_load(2 * i, c + 1, hregp[i % 3][0]);
+                    if constexpr (nhp(i) == 2) halo_load(2 * i + 1, c + 1, hregp[i % 3][1]);
+                    w_issue(cls);
+                    {   // W sub-tile s + 1 (requested two LOADs ago) and everything older -- the halo pieces of LOAD(i - 2) among it -- has landed
+                        constexpr int extra = nhp(i - 1) + nhp(i);
+                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NW + extra) : "memory");
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                    for (int mb = 0; mb < 5; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < 5; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nb], af[mb], acc[mb][nb], 0, 0, 0);
+                    __builtin_amdgcn_s_setprio(0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                subp(IC<0>{}); subp(IC<1>{}); subp(IC<2>{}); subp(IC<3>{}); subp(IC<4>{}); subp(IC<5>{}); subp(IC<6>{}); subp(IC<7>{});
+                cbuf = nbuf;
+                continue;
+            }
             auto sub = [&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int tap = i >> 1, hk = i & 1, ky = tap / 3, kx = tap % 3;
@@ -280,7 +338,10 @@ void conv_halo_kernel(const CHParams P) {
     bf16_t* Os = reinterpret_cast<bf16_t*>(smem_raw);        // [320][OP] = 107,520 B
     constexpr int CPR = BN / 8;                              // 20 sixteen-byte chunks per row
     const int vrows = min(TH, P.H - y0) * TW;                // (rows of a tile that hangs over the image's last row are not stored)
-    auto row_pixel = [&](int r) -> int64_t { return ((int64_t)img * P.H + y0 + (r >> 5)) * P.W + x0 + (r & 31); };
+    auto row_pixel = [&](int r) -> int64_t {
+        if constexpr (PH) return ((int64_t)img * (2 * P.H) + 2 * (y0 + (r >> 5)) + py) * (2 * P.W) + 2 * (x0 + (r & 31)) + px_;      // pixel shuffle
+        return ((int64_t)img * P.H + y0 + (r >> 5)) * P.W + x0 + (r & 31);
+    };
     {   // bias and time-embedding words of my five channel blocks: all requested before the first is used (one branch per block put each load behind its
         // own s_waitcnt vmcnt(0): ten dependent round trips)
         u32x2 bt[5], tt[5];
@@ -374,7 +435,8 @@ void conv_halo_kernel(const CHParams P) {
         if (tid < GT) {
             float a = 0.f, b = 0.f;
             for (int k = 0; k < RP; ++k) { a += red[2 * (tid + k * GT)]; b += red[2 * (tid + k * GT) + 1]; }
-            float* dst = P.gn_part + (((int64_t)img * tpi + tin) * 32 + (n0 / cpg + tid)) * 2;
+            // (PH: one split per (source tile, phase))
+            float* dst = P.gn_part + ((PH ? ((int64_t)img * tpi + tin) * 4 + phase : (int64_t)img * tpi + tin) * 32 + (n0 / cpg + tid)) * 2;
             dst[0] = a;
             dst[1] = b;
         }
@@ -397,6 +459,36 @@ __global__ __launch_bounds__(256) void conv_halo_pack_kernel(const bf16_t* __res
         const int lc = p ^ (3 * ((row >> 3) & 1));
         const int64_t src = (((int64_t)(nt * BN + row) * 9 + tap) * cin + ch64 * 64 + hk * 32 + lc * 8);
         *reinterpret_cast<u32x4*>(dst + id * 8) = *reinterpret_cast<const u32x4*>(w + src);
+    }
+}
+
+// ---- phase-mode filter: fold + pack in one pass.  [Cout][3][3][Cin] -> [4 phases (py, px)][Cout / BN][Cin / 64][4 taps (a, b)][2 halves][BN rows][32],
+// chunk-swizzled as above.  Wf[py][px][a][b] = sum of w[ky][kx] over ky in R(py, a), kx in R(px, b) with R(0, 0) = {0}, R(0, 1) = {1, 2},
+// R(1, 0) = {0, 1}, R(1, 1) = {2}: the filter rows / columns that fall on the same source pixel.  Summed in fp32 (fixed order), rounded to bf16 once. ----
+__global__ __launch_bounds__(256) void conv_upfold_pack_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ dst, int cout, int cin, int BN) {
+    const int64_t total = (int64_t)cout * 16 * cin / 8;     // 16-byte chunks
+    const int nchunk = cin >> 6, tn1 = cout / BN;
+    for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (int64_t)gridDim.x * blockDim.x) {
+        int64_t t = id;
+        const int p = (int)(t & 3); t >>= 2;
+        const int row = (int)(t % BN); t /= BN;
+        const int hk = (int)(t & 1); t >>= 1;
+        const int tap = (int)(t & 3); t >>= 2;
+        const int ch64 = (int)(t % nchunk); t /= nchunk;
+        const int nt = (int)(t % tn1), phase = (int)(t / tn1);
+        const int py = phase >> 1, px = phase & 1, ta = tap >> 1, tb = tap & 1;
+        const int ky0 = py == 0 ? ta : 2 * ta, ky1 = py == 0 ? 2 * ta : ta + 1;      // rows ky0 .. ky1 of the filter
+        const int kx0 = px == 0 ? tb : 2 * tb, kx1 = px == 0 ? 2 * tb : tb + 1;
+        const int lc = p ^ (3 * ((row >> 3) & 1));
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                float f[8];
+                Vec8<bf16_t>::unpack(Vec8<bf16_t>::load_raw(w + (((int64_t)(nt * BN + row) * 9 + ky * 3 + kx) * cin + ch64 * 64 + hk * 32 + lc * 8)), f);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] += f[k];
+            }
+        Vec8<bf16_t>::store(dst + id * 8, v);
     }
 }
 
@@ -493,6 +585,58 @@ extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, co
     else if (gn_act) hipLaunchKernelGGL(conv_halo_kernel<1>, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     else hipLaunchKernelGGL(conv_halo_kernel<2>, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_bf16");
+    return 0;
+}
+
+// ---- phase mode of the nearest-2x upsample convolutions (see conv_halo_kernel) ------------------------------------------------------------------
+extern "C" int64_t fmc_conv3x3_upfold_packed_bytes(int Cin, int Cout) { return (int64_t)Cout * 16 * Cin * 2; }
+
+extern "C" int fmc_conv3x3_upfold_pack_weight(const void* w, void* dst, int Cin, int Cout, int tile_channels, void* stream) {
+    if (!w || !dst) FMC_FAIL(FMC_E_NULL, "conv3x3_upfold_pack_weight: NULL pointer");
+    if ((tile_channels != 80 && tile_channels != 160) || Cin % 64 || Cout % tile_channels)
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_upfold_pack_weight: tile_channels 80 / 160, Cin %% 64, Cout %% tile_channels (Cin=%d Cout=%d tile=%d)", Cin, Cout, tile_channels);
+    if (!fmc_aligned16(w) || !fmc_aligned16(dst)) FMC_FAIL(FMC_E_ALIGN, "conv3x3_upfold_pack_weight: pointers must be 16-byte aligned");
+    const int64_t chunks = (int64_t)Cout * 16 * Cin / 8;
+    const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
+    hipLaunchKernelGGL(conv_upfold_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w, (bf16_t*)dst, Cout, Cin, tile_channels);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_upfold_pack_weight");
+    return 0;
+}
+
+extern "C" int fmc_conv3x3_halo_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout) {
+    if (!fmc_conv3x3_halo_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0)) return 0;      // the source-resolution convolution's own conditions
+    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
+    return 1;
+}
+
+extern "C" int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                          int Cout, float* gn_partials, void* stream) {
+    if (!x || !w_folded || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo_fold: NULL x / w / out");
+    if (!fmc_conv3x3_halo_fold_supported(n_img, Hs, Ws, Cin, Cout))
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_fold: needs Ws %% 32 == 0, Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
+                 n_img, Hs, Ws, Cin, Cout);
+    if (!fmc_aligned16(x) || !fmc_aligned16(w_folded) || !fmc_aligned16(out) || (bias && (reinterpret_cast<uintptr_t>(bias) & 7)))
+        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo_fold: x / w / out must be 16-byte aligned, bias 8-byte aligned");
+    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_fold: the statistics epilogue needs Cout %% 64 == 0 and 160 %% (Cout / 32) == 0 (Cout=%d)", Cout);
+    CHParams P;
+    P.x = (const bf16_t*)x; P.x2 = nullptr; P.c1 = Cin;
+    P.w = (const bf16_t*)w_folded; P.bias = (const bf16_t*)bias; P.temb = nullptr; P.res = nullptr; P.out = (bf16_t*)out;
+    P.n_img = n_img; P.H = Hs; P.W = Ws; P.cin = Cin; P.cout = Cout; P.ups = 0;
+    P.temb_ld = 0; P.temb_div = 1;
+    P.gn_coef = nullptr; P.gn_act = 0; P.gn_part = gn_partials;
+    P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = Ws / TW; P.tiles_n = 4 * (Cout / BN);
+    P.x_bytes = (int64_t)n_img * Hs * Ws * Cin * 2; P.x2_bytes = 0;
+    P.w_bytes = (int64_t)Cout * 16 * Cin * 2;
+    static FmcPerDeviceFlag raised;
+    if (!raised) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        raised = true;
+    }
+    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
+    hipLaunchKernelGGL((conv_halo_kernel<0, true>), dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_bf16");
     return 0;
 }
 

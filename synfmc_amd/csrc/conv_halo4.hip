@@ -52,7 +52,7 @@ struct C4Params {
     const bf16_t* x; const bf16_t* x2; int c1;              // as conv_halo.hip: two-source input, channels [0, c1) from x
     const bf16_t* w;                                        // fmc_conv3x3_halo4_pack_weight: [Cout / 80][Cin / 64][9][2][80 rows][32], chunk-swizzled
     const bf16_t* bias; const bf16_t* temb; const bf16_t* res; bf16_t* out;
-    int n_img, H, W, cin, cout, ups;
+    int n_img, H, W, cin, cout, ups;                        // (phase mode: H, W = SOURCE size, the output is [n_img, 2 H, 2 W, cout]; tiles_n = 4 * cout / BN)
     int64_t temb_ld; int temb_div;
     float* gn_part;                                         // [n_img, tiles_y, 32, 2] partial sums of the rounded outputs (one split per row block), or NULL
     int tiles_y, tiles_x, tiles_p, tiles_n;                 // row blocks per image column / per image row, pixel tiles, channel tiles
@@ -66,12 +66,18 @@ template <int I> using IC = std::integral_constant<int, I>;
 
 // halo pieces requested in sub-tile i of a chunk (requested at LOAD(i), written at LOAD(i + 3)): PPS = 2 per sub-tile where a thread has more than
 // 12 pieces per chunk (4 waves), else one (8 waves: fewer staging registers in flight)
-template <int NPIECE> constexpr int pps() { return NPIECE > 12 ? 2 : 1; }
-template <int NPIECE> constexpr int nh(int i) {
-    return (i >= 0 && pps<NPIECE>() * i < NPIECE) ? (pps<NPIECE>() == 2 && 2 * i + 1 < NPIECE ? 2 : 1) : 0;
+// Phase mode (PH, see below: 8 sub-tiles per chunk): every piece is requested in sub-tiles 0 .. 3, so that the last is written at LOAD(6), one
+// barrier ahead of the next chunk's first fragment read at LOAD(7): PPS = NPIECE / 4 rounded up (2 .. 5).
+template <int NPIECE, bool PH> constexpr int pps() { return PH ? (NPIECE + 3) / 4 : (NPIECE > 12 ? 2 : 1); }
+template <int NPIECE, bool PH> constexpr int nh(int i) {
+    constexpr int S = pps<NPIECE, PH>();
+    return (i >= 0 && S * i < NPIECE) ? (NPIECE - S * i < S ? NPIECE - S * i : S) : 0;
 }
 
-template <int TW, int NWV>
+// PH: the PHASE MODE of the nearest-2x upsample convolutions, as in conv_halo_kernel (conv_halo.hip): the tile is 320 SOURCE pixels, the channel-tile
+// index is (phase (py, px), channel tile), a chunk is 4 taps x 2 k-halves = 8 sub-tiles of the folded filter (fmc_conv3x3_upfold_pack_weight), and the
+// epilogue stores out[2 i + py, 2 j + px].  No split-K, temb or residual there.
+template <int TW, int NWV, bool PH = false>
 __global__ __launch_bounds__(64 * NWV, NWV / 4)
 void conv_halo4_kernel(const C4Params P) {
     using G = Geo<TW, NWV>;
@@ -110,11 +116,14 @@ void conv_halo4_kernel(const C4Params P) {
             tile_n = lin - tile_p * P.tiles_n;
         }
     }
-    const int n0 = tile_n * BN;
+    constexpr int NS = PH ? 8 : 18;                          // sub-tiles per 64-channel chunk
+    const int tn1 = P.cout / BN;
+    const int phase = PH ? tile_n / tn1 : 0, py = phase >> 1, px_ = phase & 1;
+    const int n0 = (tile_n - phase * tn1) * BN;
     const int nchunk_all = P.cin >> 6;
     const int per = (nchunk_all + P.splits - 1) / P.splits;
     const int ck0 = split * per, nchunk = max(0, min(nchunk_all, ck0 + per) - ck0);      // my chunks ck0 .. ck0 + nchunk - 1
-    const int nsub = max(nchunk, 1) * 18;
+    const int nsub = max(nchunk, 1) * NS;
     const int tpi = P.tiles_y * P.tiles_x;                   // row blocks per image: block rb = (image rb / tpi, rows ((rb % tpi) / tiles_x) TH .., columns ((rb % tpi) % tiles_x) TW ..)
     const int rb0 = tile_p * NB, rb_total = P.n_img * tpi;   // my row blocks rb0 .. rb0 + NB - 1
 
@@ -156,7 +165,7 @@ void conv_halo4_kernel(const C4Params P) {
 
     // ---- W stream: piece p = KiB p of the 5-KiB sub-tile block; wave w issues piece w, wave 0 also piece 4 --------------------------------------------
     const unsigned w_vo0 = (unsigned)(lane * 16 + wave * 1024);
-    const int w_base = (tile_n * nchunk_all + ck0) * 18 * WSUB;       // my first sub-tile inside the channel tile's block
+    const int w_base = (tile_n * nchunk_all + ck0) * NS * WSUB;       // my first sub-tile inside the channel tile's block
     int iss_soff = w_base, iss_left = nsub, iss_slot = 0;
     auto w_issue = [&](auto cls) {
         unsigned char* dst = smem_raw + OFF_W + iss_slot * WSUB + wave * 1024;
@@ -176,7 +185,7 @@ void conv_halo4_kernel(const C4Params P) {
 #pragma unroll
     for (int mb = 0; mb < 5; ++mb) {
         const int idx = wp * 80 + mb * 16 + l15, blk = idx / RB, r = idx - blk * RB, ty = r / TW, tx = r - ty * TW;
-        afrag[mb] = kq * PLANE + (blk * HB + ty * HW_ + tx) * 16;
+        afrag[mb] = kq * PLANE + (blk * HB + ty * HW_ + tx) * 16 + (PH ? (py * HW_ + px_) * 16 : 0);      // (PH: tap (a, b) reads halo pixel + (py + a, px + b))
     }
 
     // ---- prologue: halo chunk 0 ------------------------------------------------------------------------------------------------------------------------------
@@ -191,7 +200,7 @@ void conv_halo4_kernel(const C4Params P) {
 
     auto main_loop = [&](auto cls) {
         constexpr int NW = decltype(cls)::value ? 2 : 1;
-        constexpr int PPS = pps<NPIECE>();
+        constexpr int PPS = pps<NPIECE, PH>();
         u32x4 hreg[3][PPS];                                  // staged pieces in flight: requested at LOAD(i), written at LOAD(i + 3)
         // W sub-tiles 0 .. DW - 1 in flight; sub-tile 0 retired, published, its fragments (and chunk 0's halo) read into set 0
         w_issue(cls); w_issue(cls); w_issue(cls);
@@ -218,13 +227,13 @@ void conv_halo4_kernel(const C4Params P) {
         for (int c = 0; c < nchunk; ++c) {
             const int abase = cbuf * HALO, nbuf = cbuf ^ 1;
             auto sub = [&](auto ic) {
-                constexpr int i = decltype(ic)::value;       // sub-tile s = 18 c + i: multiplied here; sub-tile s + 1's fragments are read here
-                constexpr int n1 = (i + 1) % 18, tap1 = n1 >> 1, hk1 = n1 & 1;
-                constexpr int aimm1 = hk1 * 4 * PLANE + ((tap1 / 3) * HW_ + (tap1 % 3)) * 16;
+                constexpr int i = decltype(ic)::value;       // sub-tile s = NS c + i: multiplied here; sub-tile s + 1's fragments are read here
+                constexpr int n1 = (i + 1) % NS, tap1 = n1 >> 1, hk1 = n1 & 1;
+                constexpr int aimm1 = hk1 * 4 * PLANE + (PH ? (tap1 >> 1) * HW_ + (tap1 & 1) : (tap1 / 3) * HW_ + (tap1 % 3)) * 16;
                 // A. counted wait: my pieces of W sub-tile s + 1 (requested at LOAD(s + 1 - DW), behind that phase's halo requests) and everything
                 //    older have landed; what I issued since may stay in flight: DW - 2 W requests and the halo pieces of those phases
                 {
-                    constexpr int extra = nh<NPIECE>(i - 1) + (DW == 4 ? nh<NPIECE>(i - 2) : 0);
+                    constexpr int extra = nh<NPIECE, PH>(i - 1) + (DW == 4 ? nh<NPIECE, PH>(i - 2) : 0);
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DW - 2) * NW + extra) : "memory");
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -232,13 +241,13 @@ void conv_halo4_kernel(const C4Params P) {
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 // C. the staged halo pieces requested three sub-tiles ago (retired by wait A) go to the NEXT chunk's buffer
-                if constexpr (nh<NPIECE>(i - 3) >= 1) halo_store(PPS * (i - 3), nbuf, hreg[(i - 3) % 3][0]);
-                if constexpr (nh<NPIECE>(i - 3) == 2) halo_store(PPS * (i - 3) + 1, nbuf, hreg[(i - 3) % 3][PPS - 1]);
+#pragma unroll
+                for (int k = 0; k < nh<NPIECE, PH>(i - 3); ++k) halo_store(PPS * (i - 3) + k, nbuf, hreg[(i + 15) % 3][k]);
                 // D. sub-tile s + 1's fragments into the other register set (the first sub-tile of the next chunk reads the buffer just filled)
-                read_frags((i + 1) & 1, i == 17 ? nbuf * HALO : abase, aimm1);
+                read_frags((i + 1) & 1, i == NS - 1 ? nbuf * HALO : abase, aimm1);
                 // E. requests: two halo pieces of the next chunk, then W sub-tile s + DW (into the slot sub-tile s - 1 was read from)
-                if constexpr (nh<NPIECE>(i) >= 1) hreg[i % 3][0] = halo_load(PPS * i, c + 1);
-                if constexpr (nh<NPIECE>(i) == 2) hreg[i % 3][PPS - 1] = halo_load(PPS * i + 1, c + 1);
+#pragma unroll
+                for (int k = 0; k < nh<NPIECE, PH>(i); ++k) hreg[i % 3][k] = halo_load(PPS * i + k, c + 1);
                 w_issue(cls);
                 // F. 25 MFMAs of sub-tile s, with C - E in their issue shadow: a 16x16x32 MFMA occupies the matrix pipe for 16 cycles and the issue
                 //    port for 4 -- the fragment reads, the staging store / loads and the W request (all independent of this sub-tile's operands) go out
@@ -249,8 +258,9 @@ void conv_halo4_kernel(const C4Params P) {
                     for (int nb = 0; nb < 5; ++nb)
                         acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i & 1][nb], af[i & 1][mb], acc[mb][nb], 0, 0, 0);
                 if constexpr (INTERLEAVE) {
+                    constexpr int NST = PH ? PPS : 2, NRQ = PH ? PPS + 2 : 4;
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) {                // staging stores first (their data is oldest), one per matrix instruction
+                    for (int k = 0; k < NST; ++k) {              // staging stores first (their data is oldest), one per matrix instruction
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
                     }
@@ -260,17 +270,20 @@ void conv_halo4_kernel(const C4Params P) {
                         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     }
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {                // halo requests and the W request(s)
+                    for (int k = 0; k < NRQ; ++k) {              // halo requests and the W request(s)
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 9, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 25 - 10 - NST - NRQ, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
             sub(IC<0>{}); sub(IC<1>{}); sub(IC<2>{}); sub(IC<3>{}); sub(IC<4>{}); sub(IC<5>{});
-            sub(IC<6>{}); sub(IC<7>{}); sub(IC<8>{}); sub(IC<9>{}); sub(IC<10>{}); sub(IC<11>{});
-            sub(IC<12>{}); sub(IC<13>{}); sub(IC<14>{}); sub(IC<15>{}); sub(IC<16>{}); sub(IC<17>{});
+            sub(IC<6>{}); sub(IC<7>{});
+            if constexpr (!PH) {
+                sub(IC<8>{}); sub(IC<9>{}); sub(IC<10>{}); sub(IC<11>{});
+                sub(IC<12>{}); sub(IC<13>{}); sub(IC<14>{}); sub(IC<15>{}); sub(IC<16>{}); sub(IC<17>{});
+            }
             cbuf = nbuf;
         }
     };
@@ -280,7 +293,7 @@ void conv_halo4_kernel(const C4Params P) {
 
     // ---- epilogue: bias / temb in registers, residual through the staging tile, whole-row 16-byte stores ------------------------------------------------
     // my outputs: acc[mb][nb][j] = (tile pixel 80 wave + 16 mb + l15, tile channel 16 nb + 4 kq + j)
-    if (P.splits > 1) {                                      // raw fp32 partial sums of my chunks: the finishing pass owns the epilogue
+    if (!PH && P.splits > 1) {                               // raw fp32 partial sums of my chunks: the finishing pass owns the epilogue
         const int64_t mtot = (int64_t)P.n_img * P.H * P.W;
 #pragma unroll
         for (int mb = 0; mb < 5; ++mb) {
@@ -302,6 +315,7 @@ void conv_halo4_kernel(const C4Params P) {
         const int blk = r / RB, q = r - blk * RB, ty = q / TW, tx = q - ty * TW;
         const int rb = rb0 + blk, img = rb / tpi, rin = rb - img * tpi, yb = rin / P.tiles_x, xb = rin - yb * P.tiles_x, y = yb * TH + ty;
         ok = rb < rb_total && y < P.H;
+        if constexpr (PH) return ((int64_t)img * (2 * P.H) + 2 * y + py) * (2 * P.W) + 2 * (xb * TW + tx) + px_;      // pixel shuffle
         return ((int64_t)img * P.H + y) * P.W + xb * TW + tx;
     };
     {   // bias and time-embedding words of my outputs: every load of a kind issued before the first is used (one `if (P.temb)` per accumulator block put
@@ -409,7 +423,8 @@ void conv_halo4_kernel(const C4Params P) {
             if (tid < GT) {
                 float a = 0.f, b = 0.f;
                 for (int k = 0; k < RP; ++k) { a += red[2 * (tid + k * GT)]; b += red[2 * (tid + k * GT) + 1]; }
-                float* dst = P.gn_part + (((int64_t)img * tpi + sp) * 32 + (n0 / cpg + tid)) * 2;
+                // (PH: one split per (source row block, phase))
+                float* dst = P.gn_part + ((PH ? ((int64_t)img * tpi + sp) * 4 + phase : (int64_t)img * tpi + sp) * 32 + (n0 / cpg + tid)) * 2;
                 dst[0] = a;
                 dst[1] = b;
             }
@@ -477,7 +492,7 @@ __global__ __launch_bounds__(256) void conv_halo4_finish_kernel(const C4Params P
     }
 }
 
-template <int TW, int NWV> int launch_c4(C4Params& P, hipStream_t st) {
+template <int TW, int NWV, bool PH = false> int launch_c4(C4Params& P, hipStream_t st) {
     using G = Geo<TW, NWV>;
     P.tiles_y = (P.H + G::TH - 1) / G::TH;
     P.tiles_x = P.W / TW;
@@ -497,10 +512,10 @@ template <int TW, int NWV> int launch_c4(C4Params& P, hipStream_t st) {
     }
     static FmcPerDeviceFlag raised;
     if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo4_kernel<TW, NWV>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo4_kernel<TW, NWV, PH>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
         raised = true;
     }
-    hipLaunchKernelGGL((conv_halo4_kernel<TW, NWV>), dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
+    hipLaunchKernelGGL((conv_halo4_kernel<TW, NWV, PH>), dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
     if (P.splits > 1) {
         const int64_t chunks = (int64_t)P.n_img * P.H * P.W * (P.cout / 8);
         const unsigned grid = (unsigned)((chunks + 255) / 256 < 2048 ? (chunks + 255) / 256 : 2048);
@@ -588,5 +603,42 @@ extern "C" int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, c
     else if (wide) launch_c4<16, 8>(P, st);
     else launch_c4<16, 4>(P, st);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_bf16");
+    return 0;
+}
+
+// ---- phase mode of the nearest-2x upsample convolutions on the small feature maps (see conv_halo4_kernel).  Hs, Ws = SOURCE size; w_folded =
+// fmc_conv3x3_upfold_pack_weight(filter, tile_channels = 160 if wide else 80) ---------------------------------------------------------------------
+extern "C" int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
+    if (!fmc_conv3x3_halo4_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0, wide)) return 0;      // the source-resolution convolution's own conditions
+    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
+    return 1;
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                           int Cout, float* gn_partials, int wide, void* stream) {
+    const int BN = wide ? 160 : 80;
+    if (!x || !w_folded || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo4_fold: NULL x / w / out");
+    if (!fmc_conv3x3_halo4_fold_supported(n_img, Hs, Ws, Cin, Cout, wide))
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_fold: needs Ws %% 8 == 0 (wide: %% 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
+                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d)", BN, n_img, Hs, Ws, Cin, Cout);
+    if (!fmc_aligned16(x) || !fmc_aligned16(w_folded) || !fmc_aligned16(out) || (bias && (reinterpret_cast<uintptr_t>(bias) & 7)))
+        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo4_fold: x / w / out must be 16-byte aligned, bias 8-byte aligned");
+    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_fold: the statistics epilogue needs Cout %% 64 == 0 and %d %% (Cout / 32) == 0 (Cout=%d)", BN, Cout);
+    C4Params P;
+    P.x = (const bf16_t*)x; P.x2 = nullptr; P.c1 = Cin;
+    P.w = (const bf16_t*)w_folded; P.bias = (const bf16_t*)bias; P.temb = nullptr; P.res = nullptr; P.out = (bf16_t*)out;
+    P.n_img = n_img; P.H = Hs; P.W = Ws; P.cin = Cin; P.cout = Cout; P.ups = 0;
+    P.temb_ld = 0; P.temb_div = 1;
+    P.gn_part = gn_partials; P.tiles_n = 4 * (Cout / BN);
+    P.splits = 1; P.ws = nullptr;
+    P.x_bytes = (int64_t)n_img * Hs * Ws * Cin * 2; P.x2_bytes = 0;
+    P.w_bytes = (int64_t)Cout * 16 * Cin * 2;
+    hipStream_t st = (hipStream_t)stream;
+    if (c4_tw(Ws) == 8) launch_c4<8, 4, true>(P, st);
+    else if (wide) launch_c4<16, 8, true>(P, st);
+    else launch_c4<16, 4, true>(P, st);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_fold_bf16");
     return 0;
 }

@@ -2019,6 +2019,117 @@ def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=
     return (out, part) if emit_gn else out
 
 
+# ---- the nearest-2x upsample convolutions in PHASE MODE (inference): conv3x3(upsample2x(src)) = four 2x2-tap convolutions of src, one per output
+# parity, on a filter folded once per weight version (include/fmc_hip.h: fmc_conv3x3_upfold_pack_weight) -- 4 taps per output instead of 9 ----
+UPS_FOLD = os.environ.get("FMC_UPS_FOLD", "1") != "0"             # A/B switch: 0 = the 9-tap launch with the upsample in the halo addressing
+UPS_FOLD_MIN_WS = int(os.environ.get("FMC_UPS_FOLD_MIN_WS", "8"))     # narrowest SOURCE image that takes the folded path (per-site A/B: 16 keeps the 5x8 -> 10x16 site on 9 taps)
+UPS_FOLD_WIDE = os.environ.get("FMC_UPS_FOLD_WIDE", "0") == "1"   # the 8-wave (160-channel) form of conv_halo4 for sources narrower than 32 pixels
+
+
+def upsample_fold_weights(weight: torch.Tensor) -> torch.Tensor:
+    """`[Cout, Cin, 3, 3]` -> `Wf[py, px, a, b, Cout, Cin]` with
+    `conv3x3(nearest2x(src))[2i+py, 2j+px] = sum_{a,b} Wf[py,px,a,b] . src_padded_by_1[i+py+a, j+px+b]`: the filter rows (columns) that read the same
+    source pixel are summed -- parity 0: a=0 <- w[0], a=1 <- w[1]+w[2]; parity 1: a=0 <- w[0]+w[1], a=1 <- w[2].  In the dtype of `weight` (the
+    device routine sums in fp32 and rounds to bf16 once); the reference the kernels' fold is checked against."""
+    rows = (((0,), (1, 2)), ((0, 1), (2,)))
+    cout, cin = weight.shape[:2]
+    wf = weight.new_zeros(2, 2, 2, 2, cout, cin)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    for ky in rows[py][a]:
+                        for kx in rows[px][b]:
+                            wf[py, px, a, b] += weight[:, :, ky, kx]
+    return wf
+
+
+def conv3x3_upfold_reference(x_nchw: torch.Tensor, wf: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The phase decomposition itself in plain tensor ops (any device / dtype): `x [N, Cin, Hs, Ws]`, `wf` from `upsample_fold_weights` ->
+    `[N, Cout, 2 Hs, 2 Ws]`."""
+    import torch.nn.functional as F
+    n, _, hs, ws = x_nchw.shape
+    cout = wf.shape[4]
+    xp = F.pad(x_nchw, (1, 1, 1, 1))
+    out = x_nchw.new_zeros(n, cout, 2 * hs, 2 * ws)
+    for py in range(2):
+        for px in range(2):
+            k = wf[py, px].permute(2, 3, 0, 1)                # [Cout, Cin, 2, 2]
+            out[:, :, py::2, px::2] = F.conv2d(xp[:, :, py:py + hs + 1, px:px + ws + 1], k)
+    return out if bias is None else out + bias[None, :, None, None]
+
+
+def conv3x3_upfold_arm(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[str]:
+    """Which phase-mode launch takes the upsample convolution of `n` source images `hs x ws`: "halo" (10 x 32 source tiles, csrc/conv_halo.hip),
+    "halo4" / "halo4w" (320 source pixels of whole row blocks, csrc/conv_halo4.hip), or None (the 9-tap path keeps the shape)."""
+    if not (UPS_FOLD and CONV_HALO) or ws < UPS_FOLD_MIN_WS:
+        return None
+    L = _lib.load()
+    if (L.fmc_conv3x3_halo_fold_supported(n, hs, ws, cin, cout)
+            and n * L.fmc_conv3x3_halo_tiles_per_image(hs, ws) * 4 * (cout // 160) >= CONV_HALO_MIN_TILES):
+        return "halo"
+    if not CONV_HALO4:
+        return None
+    wide = UPS_FOLD_WIDE and bool(L.fmc_conv3x3_halo4_fold_supported(n, hs, ws, cin, cout, 1))
+    if (L.fmc_conv3x3_halo4_fold_supported(n, hs, ws, cin, cout, int(wide))
+            and 4 * L.fmc_conv3x3_halo4_tiles(n, hs, ws, cout, int(wide)) >= CONV_HALO_MIN_TILES):
+        return "halo4w" if wide else "halo4"
+    return None
+
+
+def _w_upfold_packed(weight_cl: torch.Tensor, tile_channels: int) -> torch.Tensor:
+    """Channels-last 3x3 filter -> the folded 4 x 2x2-tap filter in the phase-mode kernels' sub-tile order (16 / 9 of the filter's bytes), cached on
+    the weight per version like the other packs."""
+    cache = _owner_cache(weight_cl, "_fmc_wtm")
+    key = ("upfold%d" % tile_channels, weight_cl.storage_offset(), tuple(weight_cl.shape), tuple(weight_cl.stride()), weight_cl._version)
+    hit = cache.get(key)
+    if hit is None:
+        cout, cin = weight_cl.shape[:2]
+        assert weight_cl.is_contiguous(memory_format=torch.channels_last)
+        hit = torch.empty(cout * 16 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(_lib.load().fmc_conv3x3_upfold_pack_weight(weight_cl.data_ptr(), hit.data_ptr(), cin, cout, tile_channels, _stream()),
+                   "fmc_conv3x3_upfold_pack_weight")
+        cache[key] = hit
+    return hit
+
+
+def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emit_gn: bool = False, arm: Optional[str] = None):
+    """`conv3x3(nearest2x(x)) + bias` in phase mode: x `[N, Hs, Ws, Cin]` channels-last bf16, the RAW filter `[Cout, Cin, 3, 3]` channels-last (folded
+    and packed once per weight version) -> out `[N, 2 Hs, 2 Ws, Cout]`, or `(out, partials [N, splits, 32, 2])` with `emit_gn`.  Inference only:
+    the fold is not the filter the weight gradient belongs to.  A shape no phase-mode launch takes is an error (ask `conv3x3_upfold_arm`)."""
+    _dev(x_nhwc, weight_cl, bias)
+    n, hs, ws, cin = x_nhwc.shape
+    cout = weight_cl.shape[0]
+    assert x_nhwc.is_contiguous() and x_nhwc.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16 and weight_cl.shape[1] == cin
+    assert not (torch.is_grad_enabled() and (x_nhwc.requires_grad or weight_cl.requires_grad)), "conv3x3_upfold: inference only"
+    if arm is None:
+        arm = conv3x3_upfold_arm(n, hs, ws, cin, cout)
+    if arm not in ("halo", "halo4", "halo4w"):
+        raise ValueError(f"conv3x3_upfold: no phase-mode launch for n={n} {hs}x{ws} {cin}->{cout} (arm {arm})")
+    L = _lib.load()
+    out = torch.empty(n, 2 * hs, 2 * ws, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
+    shape, flops = (n, 2 * hs, 2 * ws, cin, cout, True), 2.0 * n * 4 * hs * ws * cout * 9 * cin      # (the algorithmic, 9-tap flops: useful-work rates)
+    conv_halo_calls["upfold"] = conv_halo_calls.get("upfold", 0) + 1
+    if arm == "halo":
+        wp = _w_upfold_packed(weight_cl, 160)
+        part = torch.empty(n, 4 * L.fmc_conv3x3_halo_tiles_per_image(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+        conv_halo_calls["conv"] += 1
+        if call_log is not None:
+            call_log.append(("conv_halo", shape, flops))
+        _lib.check(L.fmc_conv3x3_halo_fold_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), _stream()),
+                   "fmc_conv3x3_halo_fold_bf16")
+    else:
+        wide = arm == "halo4w"
+        wp = _w_upfold_packed(weight_cl, 160 if wide else 80)
+        part = torch.empty(n, 4 * L.fmc_conv3x3_halo4_row_blocks_per_image(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+        conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
+        if call_log is not None:
+            call_log.append(("conv_halo4", shape, flops))
+        _lib.check(L.fmc_conv3x3_halo4_fold_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), int(wide),
+                                                 _stream()), "fmc_conv3x3_halo4_fold_bf16")
+    return (out, part) if emit_gn else out
+
+
 # --------------------------------------------------------------------------------------------
 # fp32-storage ("parity") mode of the two GEMMs: split-bf16 x3 operands on the same gfx950 kernels, fp32 epilogue
 # (include/fmc_hip.h: fmc_split_bf16x3 / fmc_linear_x3_f32 / fmc_conv3x3_x3_f32).  FMC_F32_GEMM=0 sends fp32 projections /
@@ -2525,6 +2636,21 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
     stride2 = tuple(stride) == (2, 2)
     if stride2:
         h, w = h // 2, w // 2
+    # the upsample convolutions at inference: four 2x2-tap convolutions of the source on the folded filter (4 taps per output instead of 9)
+    if upsample and temb is None and r is None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16:
+        arm = conv3x3_upfold_arm(n, h // 2, w // 2, cin, cout)
+        if arm is not None:
+            bn = 80 if arm == "halo4" else 160
+            want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and bn % (cout // 32) == 0 and (arm == "halo" or h * w >= GN_MIN_HW))
+            dispatch_calls["conv3x3"]["own"] += 1
+            y = conv3x3_upfold(x, weight_cl, bias, emit_gn=want, arm=arm)
+            if want:
+                y, part = y
+                gn_epilogue_calls["emitted"] += 1
+                y = y.permute(0, 3, 1, 2)
+                y._fmc_gn = (part, cout)
+                return y
+            return y.permute(0, 3, 1, 2)
     # the halo-resident kernel (csrc/conv_halo.hip): 1.75 - 1.95 x the ring kernels wherever its 10 x 32 pixel x 160 channel tiles fill the chip
     # (tools/scratch/r05/bench_halo.py); every such convolution also leaves the statistics of the GroupNorm that consumes its output
     if (CONV_HALO and not stride2 and (temb is None or temb.stride(1) == 1) and conv3x3_halo_supported(n, h, w, cin, cin, cout, upsample)
