@@ -665,6 +665,68 @@ int fmc_geglu320_ln_bf16(const void* h, void* out, const float* ln_gamma, const 
  * its first four tiles (tools/scratch/r04/probe_tb.py); NULL switches the stamps off (default). */
 int fmc_temporal_block_set_debug(void* buf);
 
+/* ---------------------------------------------------------------------------------------------
+ * The parameter update of the training step (csrc/optim.hip): gradient clipping per group, AdamW, the bf16 shadows of the fp32 masters
+ * and the zeroing of the gradients, for MANY tensors in two passes.  Replaces `clip_grad_norm_` + `optimizer.step()` +
+ * `optimizer.zero_grad()` of the reference's trainers (train_cam_obj_ctrl.py:917-943, train_cam_ctrl.py:647-665,
+ * train_image_lora.py:365-381; torch.optim.AdamW with amsgrad = maximize = False).  (`hip_ops.optim_grad_norm`, `hip_ops.optim_adamw_step`,
+ * `training.FusedAdamW`)
+ *
+ * The caller owns two tables in DEVICE memory (plus a host copy to have them checked once) and a workspace:
+ *   fmc_optim_tensor, one per tensor: p, g, m, v fp32 [n]; p, m, v 16-byte aligned, g 4-byte aligned (a gradient is usually a view into a
+ *     flat bucket; it is read and zeroed in 16-byte accesses all the same).  shadow_bf16 (bf16 [n]) / shadow_f32 (fp32 [n]), 16-byte
+ *     aligned or NULL: receive the NEW p rounded to nearest even to bf16, and that value widened.  step: the tensor's fp32 step counter.
+ *     clip_group: index of the group whose norm clips g, -1 = not clipped.  hyper_group: index of its hyper-parameter record.
+ *     flags: FMC_OPTIM_ZERO_GRAD = g is zeroed after use.
+ *   fmc_optim_chunk, one per workgroup: (tensor, chunk) = elements [chunk * E, min(n, (chunk + 1) * E)) of that tensor,
+ *     E = fmc_optim_chunk_elems() (8192).  Every chunk of every tensor appears exactly once, in any order.
+ *   hyper: fp32 [n_hyper][8] device records {lr, beta1, beta2, eps, weight_decay, max_grad_norm, 1 - beta1, 1 - beta2} (the last two
+ *     rounded from double by the host: 1 - (float)0.999 is 5e-5 off).  The kernels read them from memory: a captured graph replays with
+ *     whatever the host copied there last.  A clip group takes max_grad_norm from the record of its first tensor in map order.
+ *   workspace: fmc_optim_workspace_bytes(...) bytes, 16-byte aligned.  After pass 1 its first n_clip_groups floats are the groups'
+ *     gradient norms and the n_clip_groups floats from float index round_up(n_clip_groups, 4) the coefficients: readable by the host
+ *     after its own synchronisation (logging).
+ * fmc_optim_check_tables: HOST-side check of host copies of the two tables (no device access): NULL p / g / m / v / step -> FMC_E_NULL, a
+ *   misaligned p / m / v / shadow -> FMC_E_ALIGN, a group index out of range or a map that does not cover every chunk exactly once ->
+ *   FMC_E_SHAPE.  The launches below cannot read device tables; they check their own arguments and rely on this call for the tables.
+ * fmc_optim_grad_norm (pass 1, always before pass 2): per-chunk fp32 tree sums of g^2 (depth 13 over the squares), added per clip group
+ *   in a fixed order in fp64: norm = sqrt(sum), coefficient = min(1, max_grad_norm / (norm + 1e-6)) -- `clip_grad_norm_` with
+ *   error_if_nonfinite=False; a non-finite norm propagates as there.  The same small kernel advances the step counter of EVERY tensor of
+ *   the table and writes its bias corrections 1 - beta1^t and sqrt(1 - beta2^t), computed in fp64 once per tensor.  No atomics: equal
+ *   inputs give equal bits.  With n_clip_groups == 0 only the counters and corrections are written.
+ * fmc_optim_adamw_step (pass 2, one launch), per element in fp32, gc = g * coefficient[clip_group]:
+ *     p <- p (1 - lr wd);  m <- m + (gc - m)(1 - beta1);  v <- beta2 v + (1 - beta2) gc^2;
+ *     p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  then the shadows and g <- 0 where asked.
+ *   HBM bound: 16 bytes read and 12 (+2 +4 +4) written per element; pass 1 reads 4.
+ * ------------------------------------------------------------------------------------------- */
+enum { FMC_OPTIM_ZERO_GRAD = 1 };
+typedef struct fmc_optim_tensor {
+    float* p;
+    float* g;
+    float* m;
+    float* v;
+    uint16_t* shadow_bf16;
+    float* shadow_f32;
+    float* step;
+    int64_t n;
+    int32_t clip_group;
+    int32_t hyper_group;
+    int32_t flags;
+    int32_t reserved;
+} fmc_optim_tensor;
+typedef struct fmc_optim_chunk {
+    int32_t tensor;
+    int32_t chunk;
+} fmc_optim_chunk;
+int fmc_optim_chunk_elems(void);
+int64_t fmc_optim_workspace_bytes(int n_tensors, int n_chunks, int n_clip_groups);
+int fmc_optim_check_tables(const fmc_optim_tensor* h_tensors, int n_tensors, const fmc_optim_chunk* h_chunks, int n_chunks, int n_hyper,
+                           int n_clip_groups);
+int fmc_optim_grad_norm(const fmc_optim_tensor* tensors, int n_tensors, const fmc_optim_chunk* chunks, int n_chunks, const float* hyper,
+                        int n_hyper, int n_clip_groups, void* workspace, int64_t workspace_bytes, void* stream);
+int fmc_optim_adamw_step(const fmc_optim_tensor* tensors, int n_tensors, const fmc_optim_chunk* chunks, int n_chunks, const float* hyper,
+                         int n_hyper, int n_clip_groups, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,11 @@ SIGNATURES = {
     "fmc_nhwc_to_cmajor_padded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p]),
     "fmc_linear_wgrad_workspace_bytes": (c_int64, [c_void_p, c_int]),
     "fmc_linear_wgrad_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "fmc_optim_chunk_elems": (c_int, []),
+    "fmc_optim_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "fmc_optim_check_tables": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
+    "fmc_optim_grad_norm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "fmc_optim_adamw_step": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "fmc_temporal_block_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fmc_temporal_block_set_debug": (c_int, [c_void_p]),

@@ -3123,3 +3123,103 @@ def lora_linear(x: torch.Tensor, weights, downs, ups, scales, bias: Optional[tor
     the caller keeps, for the derived bf16 weights of this group."""
     spec = dict(weights=list(weights), scales=[float(s) for s in scales], cache=cache)
     return _LoRALinear.apply(x, bias, residual, spec, *downs, *ups)
+
+
+# --------------------------------------------------------------------------------------------
+# The parameter update: clip per group + AdamW + bf16 shadows + gradient zeroing (csrc/optim.hip)
+# --------------------------------------------------------------------------------------------
+OPTIM_CHUNK = 8192                  # elements per workgroup; checked against fmc_optim_chunk_elems() when a device plan is built
+OPTIM_ZERO_GRAD = 1
+OPTIM_HYPER = 8                     # floats per record: lr, beta1, beta2, eps, weight_decay, max_grad_norm, 1 - beta1, 1 - beta2
+
+
+class OptimTensor(_ct.Structure):
+    """`fmc_optim_tensor` of include/fmc_hip.h."""
+    _fields_ = [("p", _ct.c_void_p), ("g", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p), ("shadow_bf16", _ct.c_void_p),
+                ("shadow_f32", _ct.c_void_p), ("step", _ct.c_void_p), ("n", _ct.c_int64), ("clip_group", _ct.c_int32),
+                ("hyper_group", _ct.c_int32), ("flags", _ct.c_int32), ("reserved", _ct.c_int32)]
+
+
+def _round4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def optim_check_tables(table, chunks, n_hyper: int, n_clip_groups: int) -> None:
+    """`fmc_optim_check_tables` on HOST copies of the two tables (int64 `[n, 10]`, int32 `[n_chunks, 2]` CPU tensors): raises what the
+    ABI reports -- a NULL or misaligned pointer, a group index out of range, a chunk map that does not cover its tensors."""
+    assert table.dtype == torch.int64 and chunks.dtype == torch.int32 and not table.is_cuda and not chunks.is_cuda
+    table, chunks = table.contiguous(), chunks.contiguous()
+    rc = _lib.load().fmc_optim_check_tables(table.data_ptr(), table.shape[0], chunks.data_ptr(), chunks.shape[0], n_hyper, n_clip_groups)
+    _lib.check(rc, "fmc_optim_check_tables")
+
+
+class OptimPlan:
+    """What one fused update works on: the torch tensors (so that they stay alive), the two device tables built from them, the
+    hyper-parameter records and the workspace.  `entries`: dicts with `p, g, m, v, step` (fp32 tensors; `step` 0-d), `shadow_bf16`,
+    `shadow_f32` (tensors or None), `clip_group` (-1: not clipped), `hyper_group`, `zero` (bool).  `hyper`: the fp32 `[n_hyper, 8]` records
+    on the tensors' device, refreshed by the owner.  On a device the tables pass `fmc_optim_check_tables` before they are uploaded."""
+
+    def __init__(self, entries, n_clip_groups: int, hyper: torch.Tensor):
+        assert entries, "OptimPlan: no tensors"
+        self.entries, self.n_clip_groups, self.hyper = list(entries), int(n_clip_groups), hyper
+        dev = self.entries[0]["p"].device
+        assert hyper.dtype == torch.float32 and hyper.ndim == 2 and hyper.shape[1] == OPTIM_HYPER and hyper.is_contiguous() and hyper.device == dev
+        rows, cmap = [], []
+        for i, e in enumerate(self.entries):
+            for k in ("p", "g", "m", "v", "step"):
+                t = e[k]
+                if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+                    raise TypeError(f"OptimPlan: {k} of tensor {i} must be a contiguous fp32 tensor on {dev} (got {t.dtype}, {t.device})")
+            n = e["p"].numel()
+            if not (e["g"].numel() == e["m"].numel() == e["v"].numel() == n) or e["step"].numel() != 1:
+                raise ValueError(f"OptimPlan: p, g, m, v of tensor {i} differ in size, or step is not one element")
+            sb, sf = e.get("shadow_bf16"), e.get("shadow_f32")
+            if sb is not None and (sb.dtype != torch.bfloat16 or sb.numel() != n or not sb.is_contiguous() or sb.device != dev):
+                raise TypeError(f"OptimPlan: shadow_bf16 of tensor {i} must be a contiguous bf16 tensor of p's size")
+            if sf is not None and (sf.dtype != torch.float32 or sf.numel() != n or not sf.is_contiguous() or sf.device != dev):
+                raise TypeError(f"OptimPlan: shadow_f32 of tensor {i} must be a contiguous fp32 tensor of p's size")
+            flags_groups = (int(e["clip_group"]) & 0xffffffff) | (int(e["hyper_group"]) << 32)
+            rows.append([e["p"].data_ptr(), e["g"].data_ptr(), e["m"].data_ptr(), e["v"].data_ptr(), sb.data_ptr() if sb is not None else 0,
+                         sf.data_ptr() if sf is not None else 0, e["step"].data_ptr(), n, flags_groups, OPTIM_ZERO_GRAD if e.get("zero") else 0])
+            cmap += [(i, c) for c in range((n + OPTIM_CHUNK - 1) // OPTIM_CHUNK)]
+        table = torch.tensor(rows, dtype=torch.int64)
+        chunks = torch.tensor(cmap, dtype=torch.int32)
+        assert table.shape[1] * 8 == _ct.sizeof(OptimTensor)
+        self.n_tensors, self.n_chunks, self.n_hyper = len(rows), len(cmap), hyper.shape[0]
+        G = self.n_clip_groups
+        self.coef_off = _round4(G)
+        self.bc_off = self.coef_off + _round4(G)
+        self.partials_off = self.bc_off + _round4(2 * self.n_tensors)
+        ws_floats = self.partials_off + _round4(self.n_chunks)
+        if dev.type == "cuda":
+            lib = _lib.load()
+            assert lib.fmc_optim_chunk_elems() == OPTIM_CHUNK
+            assert lib.fmc_optim_workspace_bytes(self.n_tensors, self.n_chunks, G) == ws_floats * 4
+            optim_check_tables(table, chunks, self.n_hyper, G)
+        self.table, self.chunks = table.to(dev), chunks.to(dev)
+        self.workspace = torch.zeros(ws_floats, dtype=torch.float32, device=dev)
+        self.norms = self.workspace[:G]                                       # per clip group, valid after optim_grad_norm
+        self.coefs = self.workspace[self.coef_off: self.coef_off + G]
+        self.bias_corrections = self.workspace[self.bc_off: self.bc_off + 2 * self.n_tensors].view(self.n_tensors, 2)
+        self.elements = sum(e["p"].numel() for e in self.entries)
+
+    def _args(self):
+        return (self.table.data_ptr(), self.n_tensors, self.chunks.data_ptr(), self.n_chunks, self.hyper.data_ptr(), self.n_hyper,
+                self.n_clip_groups, self.workspace.data_ptr(), self.workspace.numel() * 4, _stream())
+
+
+def optim_grad_norm(plan: OptimPlan) -> torch.Tensor:
+    """Pass 1 of the fused update (`fmc_optim_grad_norm`): per clip group the gradient norm and the clip coefficient into the plan's
+    workspace, every tensor's step counter advanced and its bias corrections written.  Returns `plan.norms` (a device tensor; nothing
+    synchronises).  CPU tensors raise."""
+    _dev(plan.table, plan.hyper, plan.workspace)
+    _lib.check(_lib.load().fmc_optim_grad_norm(*plan._args()), "fmc_optim_grad_norm")
+    return plan.norms
+
+
+def optim_adamw_step(plan: OptimPlan) -> None:
+    """Pass 2 (`fmc_optim_adamw_step`), after `optim_grad_norm` on the same plan: AdamW on the clipped gradients, the bf16 shadows, the
+    zeroing -- one launch for every tensor.  The kernel writes through raw pointers: bumping the tensors' version counters is the
+    caller's job (`training.FusedAdamW` does it).  CPU tensors raise."""
+    _dev(plan.table, plan.hyper, plan.workspace)
+    _lib.check(_lib.load().fmc_optim_adamw_step(*plan._args()), "fmc_optim_adamw_step")

@@ -82,6 +82,32 @@ def bf16_param(mod: nn.Module, name: str, rounded_f32: bool = False) -> torch.Te
     return hit[2] if rounded_f32 else hit[1]
 
 
+def bf16_shadow_owners(model: nn.Module, params) -> dict:
+    """`id(parameter) -> (module, name)` for those of `params` that a module of `model` owns directly: where `bf16_param` would keep
+    their shadows.  (For an optimizer that refreshes the shadows itself, `training.FusedAdamW.attach`.)"""
+    want = {id(p) for p in params}
+    return {id(p): (mod, name) for mod in model.modules() for name, p in mod._parameters.items() if p is not None and id(p) in want}
+
+
+def bf16_shadow_tensors(mod: nn.Module, name: str):
+    """`(bf16 shadow, fp32-rounded shadow)` of `mod.<name>` as `bf16_param` keeps them, or None while no forward has created them (or
+    they no longer fit the parameter and `bf16_param` would replace them)."""
+    p = getattr(mod, name)
+    hit = mod.__dict__.get("_bf16_shadow", {}).get(name)
+    if hit is None or p is None or p.dtype != torch.float32 or hit[1].shape != p.shape or hit[1].device != p.device:
+        return None
+    return hit[1], hit[2]
+
+
+def bf16_shadow_mark_fresh(mod: nn.Module, name: str) -> None:
+    """Someone else wrote the rounded master into both shadows (and bumped their version counters, so the derived-weight caches
+    rebuild): re-key the entry so that the next `bf16_param` does not copy again."""
+    p = getattr(mod, name)
+    hit = mod.__dict__.get("_bf16_shadow", {}).get(name)
+    if hit is not None:
+        hit[0] = (p.data_ptr(), p._version)
+
+
 class GroupNorm(nn.GroupNorm):
     """nn.GroupNorm on a `[N, C, h, w]` tensor, optionally fused with SiLU (`fmc_groupnorm_silu_fwd`)."""
 

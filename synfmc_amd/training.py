@@ -239,6 +239,26 @@ class GradAllReducer:
         self._next = 0
         self._reinstall_views()      # an optimizer's zero_grad(set_to_none=True) may have dropped the views
 
+    def rearm(self, zeroed: Iterable[torch.nn.Parameter]) -> None:
+        """`zero_grad()` after an update that has already zeroed the gradients of `zeroed` in place (`FusedAdamW.step(zero=True)`): a
+        bucket whose parameters were ALL zeroed through their bucket views skips its fill, every other bucket is filled as usual."""
+        if self._readmit:
+            return self.zero_grad()                              # the buckets are rebuilt: the plain path
+        done = {id(p) for p in zeroed}
+        for p in self.unused:
+            p.grad = None
+        for b in self.buckets:
+            off, covered, esz = 0, True, b["flat"].element_size()
+            for p in b["params"]:
+                covered = covered and id(p) in done and p.grad is not None and p.grad.data_ptr() == b["flat"].data_ptr() + esz * off
+                off += p.numel()
+            if not covered:
+                b["flat"].zero_()
+            b["pending"] = len(b["params"])
+            b["launched"] = False
+        self._next = 0
+        self._reinstall_views()
+
     def _reinstall_views(self):
         for b in self.buckets:
             off = 0
@@ -283,10 +303,240 @@ def stage3_forward_backward(pose_adaptor, noise_scheduler, latents, noise, times
     return loss.detach()
 
 
+def _capturing(t: torch.Tensor) -> bool:
+    return t.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """`torch.optim.AdamW` (amsgrad=False, maximize=False) on this library's kernels: gradient clipping per group, the update, the bf16
+    shadows of the fp32 masters (`layers.bf16_param`) and the zeroing of the gradients in two ABI calls (`fmc_optim_grad_norm`,
+    `fmc_optim_adamw_step`) for all tensors.  Constructor arguments, `param_groups` and the `state_dict()` format are AdamW's: schedulers
+    drive `param_groups[i]["lr"]` as ever, and a checkpoint written under either optimizer resumes under the other.
+
+    * fp32 parameters only (masters are fp32); a parameter whose `.grad is None` is skipped entirely -- no decay, its step counter does not move.
+    * The device tables are rebuilt only when the set of parameters with a gradient, an address (gradient, shadow, state) or the clip grouping
+      changes; inside a HIP-graph capture a rebuild raises: a captured step needs a static set.  `rebuilds` counts them.
+    * Hyper-parameters travel through a small device record: every eager `step` refreshes it, a captured step replays with what
+      `push_hyperparameters()` copied there between the replays.  The graph holds the addresses of the optimizer's tables: keep the
+      optimizer alive as long as the graph.
+    * The kernels write through raw pointers; `step` bumps the version counter of everything they wrote and re-keys the shadows it refreshed
+      (every derived-weight cache of the models is keyed on `(data_ptr, _version)`).  A REPLAYED step runs no Python: call `mark_updated()`
+      after the replays, before the next eager forward.
+    * `attach(model)` tells the optimizer where the shadows live; a master without a shadow simply gets none."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        if amsgrad:
+            raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference's trainers do not use it; the kernel keeps no max of v)")
+        if maximize:
+            raise NotImplementedError("FusedAdamW: maximize is not implemented (negate the loss instead)")
+        if differentiable:
+            raise NotImplementedError("FusedAdamW: the update runs in a HIP kernel outside autograd, it cannot be differentiable")
+        if not 0.0 <= float(lr) or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not 0.0 <= weight_decay:
+            raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                        differentiable=False, fused=None, decoupled_weight_decay=True)
+        self._steps = None                 # one flat fp32 device tensor: state[p]["step"] is a 0-d view of it
+        self._slot = {}
+        self._owners = {}                  # id(p) -> (module, name): where layers.bf16_param keeps p's shadows
+        self._plan, self._plan_key, self._hyper = None, None, None
+        self._max_grad_norm, self._pushed = float("inf"), None
+        self.rebuilds = 0
+        self.grad_norms = None             # per clip group, a device tensor, after step()
+        self.last_stepped: List[torch.nn.Parameter] = []
+        super().__init__(params, defaults)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        for p in self.param_groups[-1]["params"]:
+            if p.dtype != torch.float32:
+                raise TypeError(f"FusedAdamW: fp32 parameters only (masters are fp32 by this project's rule), got {p.dtype}")
+        self._plan_key = None
+
+    def attach(self, *models: torch.nn.Module) -> "FusedAdamW":
+        """Find the modules that own this optimizer's parameters: their `bf16_param` shadows are refreshed by `step` from then on."""
+        from .models.layers import bf16_shadow_owners
+        mine = [p for g in self.param_groups for p in g["params"]]
+        for model in models:
+            self._owners.update(bf16_shadow_owners(model, mine))
+        self._plan_key = None
+        return self
+
+    # ---- state -------------------------------------------------------------------------------------------
+    def _step_slot(self, p: torch.Tensor) -> torch.Tensor:
+        if id(p) not in self._slot:
+            params = [q for g in self.param_groups for q in g["params"]]
+            flat = torch.zeros(len(params), dtype=torch.float32, device=p.device)
+            self._slot = {id(q): i for i, q in enumerate(params)}
+            for q in params:
+                st = self.state.get(q)
+                if st is not None and "step" in st:
+                    flat[self._slot[id(q)]] = float(st["step"])
+                    st["step"] = flat[self._slot[id(q)]]
+            self._steps = flat
+        return self._steps[self._slot[id(p)]]
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["step"] = self._step_slot(p)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    def state_dict(self):
+        """AdamW's format; `step` as the CPU fp32 scalar tensors torch's own AdamW writes."""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (v.detach().cpu().clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()}
+                       for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._steps, self._slot = None, {}
+        for p, st in list(self.state.items()):
+            if "exp_avg" not in st:
+                continue
+            step = st.get("step", 0.0)
+            st.pop("step", None)
+            slot = self._step_slot(p)
+            slot.fill_(float(step))
+            st["step"] = slot
+            for n in ("exp_avg", "exp_avg_sq"):
+                st[n] = st[n].to(device=p.device, dtype=torch.float32).contiguous()
+        self._plan_key = None
+
+    # ---- the tables --------------------------------------------------------------------------------------
+    def _shadows(self, p):
+        own = self._owners.get(id(p))
+        if own is None:
+            return None
+        from .models.layers import bf16_shadow_tensors
+        return bf16_shadow_tensors(*own)
+
+    def _prepare(self, clip_groups, zero):
+        group_of = {}
+        for ci, grp in enumerate(clip_groups or []):
+            for p in grp:
+                if group_of.setdefault(id(p), ci) != ci:
+                    raise ValueError("FusedAdamW: a parameter is in two clip groups")
+        entries, key = [], [len(clip_groups or []), bool(zero)]
+        for hi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("FusedAdamW does not support sparse gradients")
+                sh = self._shadows(p)
+                st = self._state_of(p)
+                entries.append((p, hi, group_of.get(id(p), -1), sh))
+                key += [id(p), p.data_ptr(), p.grad.data_ptr(), hi, group_of.get(id(p), -1),
+                        sh[0].data_ptr() if sh else 0, sh[1].data_ptr() if sh else 0,
+                        st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()]
+        return entries, key
+
+    def _build(self, entries, n_clip_groups, zero):
+        from . import hip_ops as K
+        dev = entries[0][0].device
+        rows = []
+        for p, hi, ci, sh in entries:
+            if p.device != dev:
+                raise RuntimeError("FusedAdamW: all parameters must live on one device")
+            if not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
+                raise RuntimeError("FusedAdamW: parameters and gradients must be contiguous fp32 tensors")
+            st = self._state_of(p)
+            rows.append(dict(p=p.detach(), g=p.grad, m=st["exp_avg"], v=st["exp_avg_sq"], step=st["step"],
+                             shadow_bf16=sh[0] if sh else None, shadow_f32=sh[1] if sh else None, clip_group=ci, hyper_group=hi, zero=zero,
+                             param=p))
+        if self._hyper is None or self._hyper.shape[0] != len(self.param_groups) or self._hyper.device != dev:
+            self._hyper = torch.zeros(len(self.param_groups), K.OPTIM_HYPER, dtype=torch.float32, device=dev)
+            self._pushed = None
+        self.rebuilds += 1
+        return K.OptimPlan(rows, n_clip_groups, self._hyper)
+
+    def push_hyperparameters(self, max_grad_norm: Optional[float] = None) -> None:
+        """Copy `param_groups` (lr, betas, eps, weight_decay) and the clip threshold into the device record the kernels read.  Every eager
+        `step` does it; around a captured step call it between the replays (after `scheduler.step()`)."""
+        if max_grad_norm is not None:
+            self._max_grad_norm = float(max_grad_norm)
+        if self._hyper is None:
+            return
+        rows = [[float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self._max_grad_norm,
+                 1.0 - float(g["betas"][0]), 1.0 - float(g["betas"][1])] for g in self.param_groups]
+        if rows != self._pushed:                                 # a constant schedule costs no copy
+            self._hyper.copy_(torch.tensor(rows, dtype=torch.float64).to(torch.float32))
+            self._pushed = rows
+
+    def mark_updated(self) -> None:
+        """Tell torch what the kernels wrote: bump the version counter of every master, state, shadow and zeroed gradient of the current
+        table and re-key the refreshed shadows.  `step` calls it; after REPLAYS of a captured step the caller does."""
+        if self._plan is None:
+            return
+        from .models.layers import bf16_shadow_mark_fresh
+        wrote = []
+        for e in self._plan.entries:
+            wrote += [e["param"], e["m"], e["v"], e["step"]]
+            wrote += [t for t in (e["shadow_bf16"], e["shadow_f32"]) if t is not None]
+            if e["zero"]:
+                wrote.append(e["g"])
+        torch._C._increment_version(wrote)                        # wants a LIST (a bare tensor would be iterated row by row)
+        for e in self._plan.entries:
+            if e["shadow_bf16"] is not None:
+                bf16_shadow_mark_fresh(*self._owners[id(e["param"])])
+
+    @torch.no_grad()
+    def step(self, closure=None, clip_groups=None, max_grad_norm: Optional[float] = None, zero: bool = False):
+        """clip per group -> AdamW -> shadows -> (zero) in two ABI calls.  `clip_groups`: a list of parameter lists, each clipped to
+        `max_grad_norm` on its own (`clip_grad_norm_` semantics); parameters in no group are not clipped.  `zero`: the gradients are zeroed
+        in place.  Afterwards `grad_norms` holds the groups' norms (device tensor) and `last_stepped` the parameters that were updated."""
+        if closure is not None:
+            raise NotImplementedError("FusedAdamW.step takes no closure")
+        if clip_groups and max_grad_norm is None:
+            raise ValueError("FusedAdamW.step: clip_groups need a max_grad_norm")
+        from . import hip_ops as K
+        rebuild_in_capture = ("FusedAdamW: the tensor table would have to be rebuilt inside a HIP-graph capture (the set of parameters with a "
+                              "gradient, an address or the clip grouping changed) -- run one eager step with the same arguments first")
+        first = next((p for g in self.param_groups for p in g["params"] if p.grad is not None), None)
+        capturing = first is not None and _capturing(first)
+        if capturing and self._plan_key is None:
+            raise RuntimeError(rebuild_in_capture)               # (before any state is allocated on the capturing stream)
+        entries, key = self._prepare(clip_groups, zero)
+        if not entries:
+            self.last_stepped, self.grad_norms = [], None
+            return None
+        if key != self._plan_key:
+            if capturing:
+                raise RuntimeError(rebuild_in_capture)
+            self._plan = self._build(entries, len(clip_groups or []), zero)
+            self._plan_key = key
+        if capturing:
+            if self._pushed is None or (max_grad_norm is not None and float(max_grad_norm) != self._pushed[0][5]):
+                raise RuntimeError("FusedAdamW: max_grad_norm differs from the value in the device record; push_hyperparameters(max_grad_norm) "
+                                   "before the capture")
+        else:
+            self.push_hyperparameters(max_grad_norm)
+        K.optim_grad_norm(self._plan)
+        K.optim_adamw_step(self._plan)
+        self.mark_updated()
+        self.grad_norms = self._plan.norms
+        self.last_stepped = [e["param"] for e in self._plan.entries]
+        return None
+
+
 def optimizer_update(trainable: Iterable[torch.nn.Parameter], optimizer, reducer: Optional["GradAllReducer"],
-                     max_grad_norm: float = 1.0) -> None:
-    """clip -> step -> zero (train_cam_obj_ctrl.py:917-943), on already averaged gradients."""
+                     max_grad_norm: float = 1.0, extra_clip_groups=None) -> None:
+    """clip -> step -> zero (train_cam_obj_ctrl.py:917-943), on already averaged gradients.  With a `FusedAdamW` the three are its two
+    kernel passes: `trainable` and each of `extra_clip_groups` are clipped on their own, the kernel zeroes the gradients it used and the
+    reducer is re-armed without the fills of the buckets that are already zero."""
     params = [p for p in trainable if p.requires_grad and p.grad is not None]
+    if isinstance(optimizer, FusedAdamW):
+        groups = [params] + [[p for p in g if p.grad is not None] for g in (extra_clip_groups or [])]
+        optimizer.step(clip_groups=groups, max_grad_norm=max_grad_norm, zero=reducer is not None)
+        if reducer is not None:
+            reducer.rearm(optimizer.last_stepped)
+        else:
+            optimizer.zero_grad(set_to_none=True)
+        return
     torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
     optimizer.step()
     if reducer is not None:
@@ -318,7 +568,11 @@ def stage3_training_step(pose_adaptor, omcm, noise_scheduler, optimizer, reducer
                                    plucker_embedding, traj_features_fn, obj_masks, sd_loss_weight, mask_loss_weight)
     if reducer is not None:
         reducer.finish()
-    for group in stage3_clip_groups(omcm, lora_params, mm_params)[1:]:
+    extra = stage3_clip_groups(omcm, lora_params, mm_params)[1:]
+    if isinstance(optimizer, FusedAdamW):
+        optimizer_update(omcm.parameters(), optimizer, reducer, max_grad_norm, extra_clip_groups=extra)
+        return loss
+    for group in extra:
         torch.nn.utils.clip_grad_norm_([p for p in group if p.grad is not None], max_grad_norm)
     optimizer_update(omcm.parameters(), optimizer, reducer, max_grad_norm)
     return loss
