@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import FMC_BF16, FMC_F32
+from .derived import derived_on_owner
 
 _DT = {torch.bfloat16: FMC_BF16, torch.float32: FMC_F32}
 
@@ -984,45 +985,21 @@ def split_arms(M: int, N: int, Kd: int):
 W_TILEMAJOR = os.environ.get("FMC_W_TILEMAJOR", "1") != "0"      # A/B switch: the 160 x 320 kernels read weights pre-packed tile-major (tile 18)
 
 
-def _owner_cache(t: torch.Tensor, name: str) -> dict:
-    """A dict living on the tensor that owns t's storage (dies with it), reset when that tensor's version changes."""
-    owner = t._base if t._base is not None else t
-    cache = getattr(owner, name, None)
-    if cache is None or cache[0] != owner._version:
-        cache = (owner._version, {})
-        try:
-            setattr(owner, name, cache)
-        except Exception:
-            pass
-    return cache[1]
-
-
 def _w_tilemajor(weight: torch.Tensor) -> torch.Tensor:
     """`[N, K]` projection weight -> `[N / 320][K / 32][320][32]`: what tile 18 reads (a W piece of a sub-tile = one contiguous KiB)."""
-    cache = _owner_cache(weight, "_fmc_wtm")
-    key = ("lin", weight.storage_offset(), tuple(weight.shape), tuple(weight.stride()), weight._version)
-    hit = cache.get(key)
-    if hit is None:
-        N, Kd = weight.shape
-        with torch.no_grad():
-            hit = weight.detach().reshape(N // 320, 320, Kd // 32, 32).permute(0, 2, 1, 3).contiguous()
-        cache[key] = hit
-    return hit
+    N, Kd = weight.shape
+    return derived_on_owner(weight, "_fmc_wtm", "lin",
+                            lambda: weight.detach().reshape(N // 320, 320, Kd // 32, 32).permute(0, 2, 1, 3).contiguous())
 
 
 def _w_tilemajor_conv(weight_cl: torch.Tensor) -> torch.Tensor:
     """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> `[Cout / 320][Cin / 64][9 taps][2 halves][320][32]`: the conv kernel's own
     sub-tile order (64-channel chunk, tap, 32-channel half)."""
-    cache = _owner_cache(weight_cl, "_fmc_wtm")
-    key = ("conv", weight_cl.storage_offset(), tuple(weight_cl.shape), tuple(weight_cl.stride()), weight_cl._version)
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         cout, cin = weight_cl.shape[:2]
-        with torch.no_grad():
-            w = weight_cl.detach().permute(0, 2, 3, 1).reshape(cout // 320, 320, 9, cin // 64, 2, 32)      # [nt][row][tap][chunk][half][32]
-            hit = w.permute(0, 3, 2, 4, 1, 5).contiguous()                                                 # [nt][chunk][tap][half][row][32]
-        cache[key] = hit
-    return hit
+        w = weight_cl.detach().permute(0, 2, 3, 1).reshape(cout // 320, 320, 9, cin // 64, 2, 32)      # [nt][row][tap][chunk][half][32]
+        return w.permute(0, 3, 2, 4, 1, 5).contiguous()                                                # [nt][chunk][tap][half][row][32]
+    return derived_on_owner(weight_cl, "_fmc_wtm", "conv", build)
 
 
 def pack_temporal_qkv(w_qkv: torch.Tensor, heads: int = 8) -> torch.Tensor:
@@ -1605,27 +1582,15 @@ def resolve_pending_ln(x: torch.Tensor) -> torch.Tensor:
 
 def _ln_folded_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor):
     """(W diag(gamma) in bf16, c[n] = sum_k of it, W beta + bias) for `fmc_linear_bf16_lnc`; cached on the tensor that owns W's storage."""
-    owner = weight._base if weight._base is not None else weight
-    key = (weight.storage_offset(), tuple(weight.shape), weight._version, gamma.data_ptr(), gamma._version, beta.data_ptr(), beta._version,
-           None if bias is None else (bias.data_ptr(), bias._version))
-    cache = getattr(owner, "_fmc_lnw", None)
-    if cache is None or cache[0] != owner._version:
-        cache = (owner._version, {})
-        try:
-            owner._fmc_lnw = cache
-        except Exception:
-            pass
-    hit = cache[1].get(key)
-    if hit is None:
-        with torch.no_grad():
-            w32 = weight.detach().float()
-            wg = (w32 * gamma.float()[None, :]).to(torch.bfloat16).contiguous()
-            b = w32 @ beta.float()
-            if bias is not None:
-                b = b + bias.detach().float()
-            hit = (wg, wg.float().sum(dim=1).contiguous(), b.contiguous())
-        cache[1][key] = hit
-    return hit
+    def build():
+        w32 = weight.detach().float()
+        wg = (w32 * gamma.float()[None, :]).to(torch.bfloat16).contiguous()
+        b = w32 @ beta.float()
+        if bias is not None:
+            b = b + bias.detach().float()
+        return wg, wg.float().sum(dim=1).contiguous(), b.contiguous()
+    tag = (gamma.data_ptr(), gamma._version, beta.data_ptr(), beta._version, None if bias is None else (bias.data_ptr(), bias._version))
+    return derived_on_owner(weight, "_fmc_lnw", tag, build)
 
 
 def lnc_ok(x: torch.Tensor, weight: torch.Tensor) -> bool:
@@ -1886,16 +1851,13 @@ def conv3x3_halo_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: in
 
 def _w_halo_packed(weight_cl: torch.Tensor) -> torch.Tensor:
     """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> the halo kernel's sub-tile order (`fmc_conv3x3_halo_pack_weight`), cached on the weight."""
-    cache = _owner_cache(weight_cl, "_fmc_wtm")
-    key = ("halo", weight_cl.storage_offset(), tuple(weight_cl.shape), tuple(weight_cl.stride()), weight_cl._version)
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         cout, cin = weight_cl.shape[:2]
         assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        hit = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_halo_pack_weight(weight_cl.data_ptr(), hit.data_ptr(), cin, cout, _stream()), "fmc_conv3x3_halo_pack_weight")
-        cache[key] = hit
-    return hit
+        out = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(_lib.load().fmc_conv3x3_halo_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, _stream()), "fmc_conv3x3_halo_pack_weight")
+        return out
+    return derived_on_owner(weight_cl, "_fmc_wtm", "halo", build)
 
 
 def groupnorm_coef(partials: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, hw: int, C: int, groups: int, eps: float,
@@ -1916,17 +1878,14 @@ def conv3x3_halo4_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: i
 
 
 def _w_halo4_packed(weight_cl: torch.Tensor, wide: bool = False) -> torch.Tensor:
-    cache = _owner_cache(weight_cl, "_fmc_wtm")
-    key = ("halo4w" if wide else "halo4", weight_cl.storage_offset(), tuple(weight_cl.shape), tuple(weight_cl.stride()), weight_cl._version)
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         cout, cin = weight_cl.shape[:2]
         assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        hit = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_halo4_pack_weight(weight_cl.data_ptr(), hit.data_ptr(), cin, cout, int(wide), _stream()),
+        out = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(_lib.load().fmc_conv3x3_halo4_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, int(wide), _stream()),
                    "fmc_conv3x3_halo4_pack_weight")
-        cache[key] = hit
-    return hit
+        return out
+    return derived_on_owner(weight_cl, "_fmc_wtm", "halo4w" if wide else "halo4", build)
 
 
 def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 256, wide: bool = False) -> int:
@@ -2080,17 +2039,14 @@ def conv3x3_upfold_arm(n: int, hs: int, ws: int, cin: int, cout: int) -> Optiona
 def _w_upfold_packed(weight_cl: torch.Tensor, tile_channels: int) -> torch.Tensor:
     """Channels-last 3x3 filter -> the folded 4 x 2x2-tap filter in the phase-mode kernels' sub-tile order (16 / 9 of the filter's bytes), cached on
     the weight per version like the other packs."""
-    cache = _owner_cache(weight_cl, "_fmc_wtm")
-    key = ("upfold%d" % tile_channels, weight_cl.storage_offset(), tuple(weight_cl.shape), tuple(weight_cl.stride()), weight_cl._version)
-    hit = cache.get(key)
-    if hit is None:
+    def build():
         cout, cin = weight_cl.shape[:2]
         assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        hit = torch.empty(cout * 16 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_upfold_pack_weight(weight_cl.data_ptr(), hit.data_ptr(), cin, cout, tile_channels, _stream()),
+        out = torch.empty(cout * 16 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(_lib.load().fmc_conv3x3_upfold_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, tile_channels, _stream()),
                    "fmc_conv3x3_upfold_pack_weight")
-        cache[key] = hit
-    return hit
+        return out
+    return derived_on_owner(weight_cl, "_fmc_wtm", "upfold%d" % tile_channels, build)
 
 
 def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emit_gn: bool = False, arm: Optional[str] = None):
@@ -2156,17 +2112,13 @@ def split_bf16x3(src: torch.Tensor, role: int, dst: Optional[torch.Tensor] = Non
 
 
 def _split_weight_cached(weight: torch.Tensor, rows: int, C: int) -> torch.Tensor:
-    """`[hi | lo | hi]` form of a frozen fp32 weight viewed as `[rows, C]`, cached on the tensor per version (views miss: re-split)."""
-    hit = getattr(weight, "_fmc_w3", None)
-    if hit is None or hit[0] != (weight._version, weight.data_ptr()):
+    """`[hi | lo | hi]` form of a frozen fp32 weight viewed as `[rows, C]`, cached per version on the tensor that owns the storage (fresh views of
+    one weight share the entry)."""
+    def build():
         w2 = weight.detach()
         w2 = w2.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(rows, C) if weight.ndim == 4 else w2.reshape(rows, C)
-        hit = ((weight._version, weight.data_ptr()), split_bf16x3(w2.contiguous(), 1))
-        try:
-            weight._fmc_w3 = hit
-        except Exception:
-            pass
-    return hit[1]
+        return split_bf16x3(w2.contiguous(), 1)
+    return derived_on_owner(weight, "_fmc_w3", (rows, C), build)
 
 
 def _f32_arm(key_bf16, tile: int) -> int:
@@ -2705,15 +2657,11 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
 #   linear:   dX = alpha * dY @ W,  d(residual) = dY
 # --------------------------------------------------------------------------------------------
 def _flipped_filter(weight_cl: torch.Tensor) -> torch.Tensor:
-    """`[Cin, Cout, 3, 3]` filter of the backward-data convolution, channels-last memory format.  Cached ON the weight
-    tensor (an attribute, keyed by its version counter): a global dict keyed by `data_ptr()` hands out stale filters
-    when a freed weight's address is reused by another model."""
-    hit = getattr(weight_cl, "_fmc_flipped", None)
-    if hit is None or hit[0] != weight_cl._version:
-        hit = (weight_cl._version,
-               weight_cl.detach().flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last))
-        weight_cl._fmc_flipped = hit
-    return hit[1]
+    """`[Cin, Cout, 3, 3]` filter of the backward-data convolution, channels-last memory format.  Cached on the tensor that
+    owns the weight's storage, per version: a global dict keyed by `data_ptr()` hands out stale filters when a freed
+    weight's address is reused by another model."""
+    return derived_on_owner(weight_cl, "_fmc_flipped", None,
+                            lambda: weight_cl.detach().flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last))
 
 
 class _Conv3x3Frozen(torch.autograd.Function):
@@ -2742,25 +2690,11 @@ def conv3x3_frozen(x, weight_cl, bias, temb=None, residual=None, temb_div: int =
 
 def _transposed_weight(weight: torch.Tensor) -> torch.Tensor:
     """`W^T [K, N]` contiguous: the backward-data GEMM `dX = dY @ W` is `fmc_linear_bf16(dY, W^T)` -- both operands
-    reduction-contiguous.  Cached ON THE TENSOR THAT OWNS THE STORAGE (`weight._base` for a view, else the weight itself), keyed by
-    (offset, shape, strides, version): frozen weights reached through a fresh view every call (`weight.view(out, in)` of a 1x1 conv) hit
-    the cache, and the entry dies with its owner.  (A module-level dict keyed by the storage pointer -- the first form of this cache --
-    handed a freed weight's W^T to the next model whose weight landed on the same address with the same shape: wrong gradients,
-    silently.)"""
-    owner = weight._base if weight._base is not None else weight
-    key = (weight.storage_offset(), tuple(weight.shape), tuple(weight.stride()), weight._version, weight.dtype)
-    cache = getattr(owner, "_fmc_wt", None)
-    if cache is None or cache[0] != owner._version:
-        cache = (owner._version, {})
-        try:
-            owner._fmc_wt = cache
-        except Exception:                                   # (an owner that takes no attributes: transpose per call)
-            pass
-    hit = cache[1].get(key)
-    if hit is None:
-        hit = weight.detach().t().contiguous()
-        cache[1][key] = hit
-    return hit
+    reduction-contiguous.  Cached on the tensor that owns the storage (`derived_on_owner`): frozen weights reached through a fresh view
+    every call (`weight.view(out, in)` of a 1x1 conv) hit the cache, and the entry dies with its owner.  (A module-level dict keyed by
+    the storage pointer -- the first form of this cache -- handed a freed weight's W^T to the next model whose weight landed on the
+    same address with the same shape: wrong gradients, silently.)"""
+    return derived_on_owner(weight, "_fmc_wt", None, lambda: weight.detach().t().contiguous())
 
 
 def linear_backward_data(dy: torch.Tensor, weight: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:

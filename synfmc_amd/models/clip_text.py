@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import hip_ops as K
+from ..derived import derived
 from .layers import LayerNorm, Linear, linear_op
 
 
@@ -48,14 +49,9 @@ class _SelfAttention(nn.Module):
         self.q_proj, self.k_proj, self.v_proj, self.out_proj = Linear(d, d), Linear(d, d), Linear(d, d), Linear(d, d)
 
     def _fused(self):
-        key = tuple((p.data_ptr(), p._version) for p in (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight))
-        hit = self.__dict__.get("_qkv")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, torch.cat([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]).contiguous(),
-                       torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]).contiguous())
-            self.__dict__["_qkv"] = hit
-        return hit[1], hit[2]
+        ws = [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]
+        return derived(self, "_qkv", ws, lambda: (torch.cat(ws).contiguous(),
+                                                  torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]).contiguous()))
 
     def forward(self, x, residual, mask: Optional[torch.Tensor]):
         b, s, d = x.shape

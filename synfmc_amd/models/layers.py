@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import hip_ops as K
+from ..derived import derived, drop
 
 
 # ----------------------------------------------------------------------------
@@ -49,13 +50,7 @@ def f32_param(mod: nn.Module, name: str) -> torch.Tensor:
         return p
     if torch.is_grad_enabled() and p.requires_grad:
         return p.float()                      # differentiable cast: trainable bf16 norm parameters still get a grad
-    cache = mod.__dict__.setdefault("_f32_cache", {})
-    key = (p.data_ptr(), p._version)
-    hit = cache.get(name)
-    if hit is None or hit[0] != key:
-        hit = (key, p.detach().float())
-        cache[name] = hit
-    return hit[1]
+    return derived(mod, "_f32_cache", [p], lambda: p.detach().float(), tag=name)
 
 
 def bf16_param(mod: nn.Module, name: str, rounded_f32: bool = False) -> torch.Tensor:
@@ -230,22 +225,20 @@ class Conv2d(nn.Conv2d):
         MIOpen kernel anywhere in the denoising step or the decoder.  (`unet.py:284-285,155-156` of the reference: plain nn.Conv2d.)"""
         cout, cin = self.weight.shape[:2]
         cin_p, cout_p = (cin + 63) // 64 * 64, (cout + 7) // 8 * 8
-        key = (self.weight.data_ptr(), self.weight._version, None if self.bias is None else (self.bias.data_ptr(), self.bias._version))
-        hit = self.__dict__.get("_padded")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                w = torch.zeros(cout_p, cin_p, 3, 3, dtype=self.weight.dtype, device=self.weight.device)
-                w[:cout, :cin] = self.weight
-                b = torch.zeros(cout_p, dtype=self.weight.dtype, device=self.weight.device)
-                if self.bias is not None:
-                    b[:cout] = self.bias
-                hit = (key, w.contiguous(memory_format=torch.channels_last), b)
-            self.__dict__["_padded"] = hit
+
+        def build():
+            w = torch.zeros(cout_p, cin_p, 3, 3, dtype=self.weight.dtype, device=self.weight.device)
+            w[:cout, :cin] = self.weight
+            b = torch.zeros(cout_p, dtype=self.weight.dtype, device=self.weight.device)
+            if self.bias is not None:
+                b[:cout] = self.bias
+            return w.contiguous(memory_format=torch.channels_last), b
+        wp, bp = derived(self, "_padded", [self.weight, self.bias], build)
         if cin_p != cin:
             xp = torch.zeros(x.shape[0], cin_p, x.shape[2], x.shape[3], dtype=x.dtype, device=x.device).contiguous(memory_format=torch.channels_last)
             xp[:, :cin] = x
             x = xp
-        y = K.conv3x3(x.contiguous(memory_format=torch.channels_last), hit[1], hit[2], own_only=True)
+        y = K.conv3x3(x.contiguous(memory_format=torch.channels_last), wp, bp, own_only=True)
         return y[:, :cout]
 
     def _weight_cl(self) -> torch.Tensor:
@@ -254,12 +247,7 @@ class Conv2d(nn.Conv2d):
         w = self.weight
         if w.is_contiguous(memory_format=torch.channels_last) or (torch.is_grad_enabled() and w.requires_grad):
             return w
-        key = (w.data_ptr(), w._version)
-        hit = self.__dict__.get("_w_cl")
-        if hit is None or hit[0] != key:
-            hit = (key, w.detach().contiguous(memory_format=torch.channels_last))
-            self.__dict__["_w_cl"] = hit
-        return hit[1]
+        return derived(self, "_w_cl", [w], lambda: w.detach().contiguous(memory_format=torch.channels_last))
 
 
 def linear_op(x, weight, bias=None, residual=None, alpha: float = 1.0, x2=None, gn_hw: int = 0, ln=None, lazy_residual: bool = False):
@@ -525,9 +513,8 @@ class Attention(nn.Module):
             self._modules.pop("processor")
         self.processor = processor
         # the merged projection weights and everything packed from them belong to the old processor (a freed merged tensor's address can come
-        # back with version 0 under the caching allocator: the packed caches also hold their sources alive, see `_fused_tb` / `_fused_xb`)
-        for name in ("_fused", "_fused_tb", "_fused_xb", "_text_kv"):
-            self.__dict__.pop(name, None)
+        # back with version 0 under the caching allocator: the packed entries also hold their sources alive, `derived`)
+        drop(self, "_fused", "_fused_tb", "_fused_xb", "_text_kv")
 
     def set_use_memory_efficient_attention_xformers(self, *a, **k):
         pass
@@ -600,11 +587,8 @@ class Attention(nn.Module):
         if lora is not None:
             for n in ("to_q_lora", "to_k_lora", "to_v_lora", "to_out_lora"):
                 srcs += [getattr(lora, n).down.weight, getattr(lora, n).up.weight]
-        key = tuple((p.data_ptr(), p._version) for p in srcs) + (lora_scale,)
-        hit = self.__dict__.get("_fused")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        with torch.no_grad():
+
+        def build():
             def w(lin, name):
                 if lora is None:
                     return lin.weight
@@ -612,11 +596,9 @@ class Attention(nn.Module):
             wq, wk, wv = w(self.to_q, "to_q_lora"), w(self.to_k, "to_k_lora"), w(self.to_v, "to_v_lora")
             wo = w(self.to_out[0], "to_out_lora")
             if self.is_cross:
-                fused = (wq.contiguous(), torch.cat([wk, wv], dim=0).contiguous(), wo.contiguous())
-            else:
-                fused = (torch.cat([wq, wk, wv], dim=0).contiguous(), None, wo.contiguous())
-        self.__dict__["_fused"] = (key, fused)
-        return fused
+                return wq.contiguous(), torch.cat([wk, wv], dim=0).contiguous(), wo.contiguous()
+            return torch.cat([wq, wk, wv], dim=0).contiguous(), None, wo.contiguous()
+        return derived(self, "_fused", srcs, build, extra=(lora_scale,))
 
 
 def interleave_geglu(weight: torch.Tensor, bias: Optional[torch.Tensor], block: int = 32):
@@ -639,15 +621,12 @@ class GEGLU(nn.Module):
     def interleaved(self):
         """(W, b in 32-row value / gate blocks, W, b in [8 value | 8 gate] blocks or None, None): the row orders the fused kernels want, cached."""
         w = self.proj.weight
-        key = (w.data_ptr(), w._version)
-        hit = self.__dict__.get("_il")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                b = None if self.proj.bias is None else self.proj.bias.detach()
-                il160 = interleave_geglu(w.detach(), b, 8) if (w.shape[0] // 2) % 160 == 0 else (None, None)
-                hit = (key, interleave_geglu(w.detach(), b) + il160)
-            self.__dict__["_il"] = hit
-        return hit[1]
+
+        def build():
+            b = None if self.proj.bias is None else self.proj.bias.detach()
+            il160 = interleave_geglu(w.detach(), b, 8) if (w.shape[0] // 2) % 160 == 0 else (None, None)
+            return interleave_geglu(w.detach(), b) + il160
+        return derived(self, "_il", [w], build)
 
     def forward(self, hidden_states, scale: float = 1.0):
         w = self.proj.weight
@@ -671,13 +650,7 @@ class FeedForward(nn.Module):
     def _tail_weights(self, wp, bp):
         """The output projection folded into the transformer's proj_out (`hip_ops.fold_ff_tail`), cached per weight version."""
         out = self.net[2]
-        ts = [out.weight, out.bias, wp, bp]
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
-        hit = self.__dict__.get("_tail_fold")
-        if hit is None or hit[0] != key:
-            hit = (key, K.fold_ff_tail(out.weight, out.bias, wp, bp), ts)      # (the entry keeps the tensors alive: an equal pointer means the same storage)
-            self.__dict__["_tail_fold"] = hit
-        return hit[1]
+        return derived(self, "_tail_fold", [out.weight, out.bias, wp, bp], lambda: K.fold_ff_tail(out.weight, out.bias, wp, bp))
 
     def forward_ln(self, h, norm, residual, tail=None):
         """`ff(norm(h)) + residual` with LayerNorm + GEGLU projection as one launch where `hip_ops.geglu_ln_direct` exists (the 20x32 level), else None.
@@ -690,17 +663,13 @@ class FeedForward(nn.Module):
         M = h.numel() // h.shape[-1]
         pipe = K.geglu_ln_pipe_ok(h, w) and (h.shape[-1] == 320 or K.GEGLU_PIPE_640)
         var = K.geglu_pipe_variant(M, h.shape[-1]) if pipe else -1
-        key = (w.data_ptr(), w._version, var)
-        hit = self.__dict__.get("_geglu_frag")
-        if hit is None or hit[0] != key:
-            hit = (key, K.pack_geglu_frag(w, 16 if var == 1 else 32) if pipe else K.pack_geglu_frag80(w))
-            self.__dict__["_geglu_frag"] = hit
+        frag = derived(self, "_geglu_frag", [w], lambda: K.pack_geglu_frag(w, 16 if var == 1 else 32) if pipe else K.pack_geglu_frag80(w), extra=(var,))
         blocked = K.geglu_direct_blocked_ok(h, out.weight, residual)
         if pipe:      # the gate in the shadow of the next chunk's MFMAs (csrc/geglu_pipe.hip, round 6)
-            mid = K.geglu_ln_pipe(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, hit[1], proj.proj.bias, w.shape[0] // 2, blocked=blocked,
+            mid = K.geglu_ln_pipe(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=blocked,
                                   variant=var)
         else:
-            mid = K.geglu_ln_direct(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, hit[1], proj.proj.bias, w.shape[0] // 2, blocked=blocked)
+            mid = K.geglu_ln_direct(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=blocked)
         if blocked and tail is not None and residual is h and K.ff_tail_ok(h, out.weight, tail[0], tail[2]):
             wc, bc = self._tail_weights(tail[0], tail[1])
             y = K.ff_tail(mid, h, wc, bc, tail[2], tail[3])
@@ -766,29 +735,19 @@ class BasicTransformerBlock(nn.Module):
         """`attn2(norm2(h), text) + h` as one launch (the text's k | v projection and its fragment pack come from `Attention.text_kv`: once per clip)."""
         attn = self.attn2
         w_q, w_kv, w_o = self._attn2_weights(kw)
-        key = (w_q.data_ptr(), w_q._version, w_o.data_ptr(), w_o._version)
-        hit = attn.__dict__.get("_fused_xb")
-        if hit is None or hit[0] != key:
-            # (the entry keeps w_q / w_o alive: an equal data pointer then means the same storage, not a recycled address)
-            hit = ((key, K.pack_w_frag80(w_q), K.pack_w_frag80(w_o), (w_q, w_o)) if w_q.shape[0] == 640
-                   else (key, K.pack_xattn_q40(w_q, attn.heads), K._w_tilemajor(w_o), (w_q, w_o)))
-            attn.__dict__["_fused_xb"] = hit
+        wq_p, wo_p = derived(attn, "_fused_xb", [w_q, w_o], lambda: (K.pack_w_frag80(w_q), K.pack_w_frag80(w_o)) if w_q.shape[0] == 640
+                             else (K.pack_xattn_q40(w_q, attn.heads), K._w_tilemajor(w_o)))
         g, b = f32_param(self.norm2, "weight"), f32_param(self.norm2, "bias")
-        ck = (g.data_ptr(), g._version, b.data_ptr(), b._version)
-        c = self.__dict__.get("_fused_xc")
-        if c is None or c[0] != ck:
-            with torch.no_grad():
-                c = (ck, g.contiguous(), b[None, :].expand(16, -1).float().contiguous())
-            self.__dict__["_fused_xc"] = c
+        gc, bc = derived(self, "_fused_xc", [g, b], lambda: (g.contiguous(), b[None, :].expand(16, -1).float().contiguous()))
         h = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
         kv, frag = attn.text_kv(encoder_hidden_states, w_kv)           # (once per clip, not per step)
         per_text = h.shape[0] // encoder_hidden_states.shape[0]
         if h.shape[2] == 640:
-            return K.xattn_block(h, c[1], c[2], self.norm2.eps, hit[1], kv, hit[2], attn.to_out[0].bias, attn.scale, per_text, frag=frag)
+            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag)
         # the 40x64 level: the feed-forward's norm3 is applied by its GEGLU projection from the row statistics this launch leaves
         if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight):          # (the feed-forward normalises its input itself: no statistics to leave)
-            return K.xattn_block(h, c[1], c[2], self.norm2.eps, hit[1], kv, hit[2], attn.to_out[0].bias, attn.scale, per_text, frag=frag)
-        out, stats = K.xattn_block(h, c[1], c[2], self.norm2.eps, hit[1], kv, hit[2], attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps,
+            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag)
+        out, stats = K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps,
                                    frag=frag)
         K.ln_epilogue_calls["emitted"] += 1
         out._fmc_ln = (stats, self.norm3._ln_key(None, 1, 1), True)

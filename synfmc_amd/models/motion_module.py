@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import hip_ops as K
+from ..derived import derived
 from .attention_processor import (AttnProcessor, LORAPoseAdaptorAttnProcessor, LoRAAttnProcessor, PoseAdaptorAttnProcessor,
                                   _pose_tokens)
 from .layers import Attention, FeedForward, LayerNorm, f32_param, linear_op
@@ -78,11 +79,7 @@ class PositionalEncoding(nn.Module):
         """fp32 `[max_len, C]` table for the fused LayerNorm+PE kernel."""
         pe = self.pe
         if pe.dtype != torch.float32:
-            hit = self.__dict__.get("_pe32")
-            if hit is None or hit[0] != (pe.data_ptr(), pe._version):
-                hit = ((pe.data_ptr(), pe._version), pe.float())
-                self.__dict__["_pe32"] = hit
-            pe = hit[1]
+            pe = derived(self, "_pe32", [pe], lambda: self.pe.float())
         return pe[0]
 
     def forward(self, x):
@@ -182,40 +179,29 @@ class TemporalTransformerBlock(nn.Module):
         norm, enc = self.norms[i], self.attention_blocks[i].pos_encoder
         g, b = f32_param(norm, "weight"), f32_param(norm, "bias")
         pe = None if enc is None else enc.table()
-        key = (g.data_ptr(), g._version, b.data_ptr(), b._version, None if pe is None else (pe.data_ptr(), pe._version), frames)
-        hit = self.__dict__.setdefault("_fused_c", {}).get(i)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                bpe = b[None, :].expand(frames, -1) if pe is None else b[None, :] + pe[:frames]
-                hit = (key, g.contiguous(), bpe.float().contiguous())
-            self.__dict__["_fused_c"][i] = hit
-        return hit[1], hit[2]
+
+        def build():
+            bpe = b[None, :].expand(frames, -1) if pe is None else b[None, :] + pe[:frames]
+            return g.contiguous(), bpe.float().contiguous()
+        return derived(self, "_fused_c", [g, b, pe], build, extra=(frames,), tag=i)
 
     def _fused_weights(self, i, lora, lora_scale):
         attn = self.attention_blocks[i]
         w_qkv, _, w_o = attn.fused_weights(lora, lora_scale)
-        key = (w_qkv.data_ptr(), w_qkv._version, w_o.data_ptr(), w_o._version)
-        hit = attn.__dict__.get("_fused_tb")
-        if hit is None or hit[0] != key:
-            # (the entry keeps w_qkv / w_o alive: an equal data pointer then means the same storage, not an address the caching allocator
-            #  handed to the NEXT processor's merged weights; `Attention.set_processor` drops the entry as well)
+
+        def build():
             if w_o.shape[0] == 640:                      # the 20x32 level: weights in MFMA-fragment order (temporal_block640.hip)
-                hit = (key, K.pack_temporal_qkv80(w_qkv, attn.heads), K.pack_w_frag80(w_o), (w_qkv, w_o))
-            else:
-                hit = (key, K.pack_temporal_qkv(w_qkv, attn.heads), K._w_tilemajor(w_o), (w_qkv, w_o))
-            attn.__dict__["_fused_tb"] = hit
-        return hit[1], hit[2]
+                return K.pack_temporal_qkv80(w_qkv, attn.heads), K.pack_w_frag80(w_o)
+            return K.pack_temporal_qkv(w_qkv, attn.heads), K._w_tilemajor(w_o)
+        # (the entry keeps w_qkv / w_o alive: an equal data pointer is then not an address the caching allocator handed to the NEXT
+        #  processor's merged weights; `Attention.set_processor` drops the entry as well)
+        return derived(attn, "_fused_tb", [w_qkv, w_o], build)
 
     @staticmethod
     def _merge_packed(proc, wm):
         if wm.shape[0] != 640:
             return K._w_tilemajor(wm)
-        key = (wm.data_ptr(), wm._version)
-        hit = proc.__dict__.get("_fused_wm")
-        if hit is None or hit[0] != key:
-            hit = (key, K.pack_w_frag80(wm), wm)
-            proc.__dict__["_fused_wm"] = hit
-        return hit[1]
+        return derived(proc, "_fused_wm", [wm], lambda: K.pack_w_frag80(wm))
 
     def _forward_fused(self, hidden_states, cross_attention_kwargs, tail=None):
         frames = hidden_states.shape[1]

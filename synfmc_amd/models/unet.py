@@ -24,6 +24,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from ..derived import derived
 from .attention_processor import (AttnProcessor, LORAPoseAdaptorAttnProcessor, LoRAAttnProcessor,
                                   PoseAdaptorAttnProcessor)
 from .layers import GroupNorm, TimestepEmbedding, Timesteps
@@ -377,16 +378,12 @@ class UNet3DConditionModel(nn.Module):
         if torch.is_grad_enabled() or not rs or not emb.is_cuda or emb.dtype != torch.bfloat16 \
                 or os.environ.get("FMC_NO_TEMB_BATCH"):
             return
-        key = tuple((r.time_emb_proj.weight.data_ptr(), r.time_emb_proj.weight._version) for r in rs)
-        cache = getattr(self, "_temb_cat", None)
-        if cache is None or cache[0] != key:
-            w = torch.cat([r.time_emb_proj.weight.detach() for r in rs], 0).to(emb.dtype)
-            b = torch.cat([r.time_emb_proj.bias.detach() for r in rs], 0).to(emb.dtype)
-            cache = (key, w, b)
-            object.__setattr__(self, "_temb_cat", cache)
-        t_all = F.linear(F.silu(emb), cache[1], cache[2])               # [clips, sum Cout]
+        w, b = derived(self, "_temb_cat", [r.time_emb_proj.weight for r in rs],
+                       lambda: (torch.cat([r.time_emb_proj.weight.detach() for r in rs], 0).to(emb.dtype),
+                                torch.cat([r.time_emb_proj.bias.detach() for r in rs], 0).to(emb.dtype)))
+        t_all = F.linear(F.silu(emb), w, b)               # [clips, sum Cout]
         from .. import hip_ops as K
-        K._log_call("vendor", (emb.shape[0], cache[1].shape[0], cache[1].shape[1], True, False), 2.0 * emb.shape[0] * cache[1].numel())
+        K._log_call("vendor", (emb.shape[0], w.shape[0], w.shape[1], True, False), 2.0 * emb.shape[0] * w.numel())
         off = 0
         for r in rs:
             co = r.time_emb_proj.weight.shape[0]
