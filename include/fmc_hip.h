@@ -115,7 +115,10 @@ int fmc_spatial_attn_fwd(const void* q, const void* k, const void* v, void* o, f
  * clip_stride = HW*F*C, pix_stride = F*C, frame_stride = C; the native channels-last layout
  * `[(b f), hw, c]` is clip_stride = F*HW*C, frame_stride = HW*C, pix_stride = C -- no transposing
  * copy in either case.  q/k/v share one stride triple (they are slices of one fused QKV row),
- * o has its own.   F in {16, 32};  D % 8 == 0, D <= 160;  (H*D) % 8 == 0.
+ * o has its own.   1 <= F <= 32 (anything else is FMC_E_SHAPE);  D % 8 == 0, D <= 160;  (H*D) % 8 == 0.
+ * A clip length that is not a multiple of 16 runs with a partial last 16-frame tile: only the F real frame
+ * rows are read and written (frame F of clip n may be frame 0 of clip n + 1), so the launch moves the
+ * algorithmic 4 * n_clips * n_pix * F * H * D elements.  The same holds for the three entry points below.
  * ------------------------------------------------------------------------------------------- */
 int fmc_temporal_attn_fwd(const void* q, const void* k, const void* v, void* o, int n_clips, int n_pix,
                           int F, int H, int D, int64_t clip_stride, int64_t frame_stride,
@@ -528,7 +531,7 @@ int fmc_spatial_attn_bwd(const void* q, const void* k, const void* v, const void
                          int64_t dkv_batch_stride, int64_t dkv_row_stride, int kv_batch_div, float scale, int dtype,
                          void* stream);
 /* dQ, dK, dV of fmc_temporal_attn_fwd (probabilities are recomputed; nothing saved by the forward).
- * q/k/v share (clip, frame, pix) strides, d_o has its own, dq/dk/dv share a third triple. */
+ * q/k/v share (clip, frame, pix) strides, d_o has its own, dq/dk/dv share a third triple.  1 <= F <= 32. */
 int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v, const void* d_o, void* dq, void* dk, void* dv,
                           int n_clips, int n_pix, int F, int H, int D, int64_t clip_stride, int64_t frame_stride,
                           int64_t pix_stride, int64_t do_clip_stride, int64_t do_frame_stride, int64_t do_pix_stride,
@@ -547,8 +550,8 @@ int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v, const voi
  *   next call's scales from.
  * fmc_temporal_attn_fp8_fwd: S^T = K Q^T on v_mfma_f32_16x16x32_fp8_fp8, softmax in fp32, P V on the bf16 MFMA with V
  *   converted e4m3 -> bf16 (exact); o is bf16.  q/k/v strides in bytes (multiples of 16), o strides in elements; scales = 3
- *   device floats {scale_q, scale_k, scale_v}.  F in {16, 32}.
- * fmc_temporal_attn_fp8_bwd: fmc_temporal_attn_bwd with e4m3 q, k, v (dequantised while staged; d_o, dq, dk, dv bf16).
+ *   device floats {scale_q, scale_k, scale_v}.  1 <= F <= 32.
+ * fmc_temporal_attn_fp8_bwd: fmc_temporal_attn_bwd with e4m3 q, k, v (dequantised while staged; d_o, dq, dk, dv bf16).  1 <= F <= 32.
  * fmc_fp8_scales_roll: the delayed-scaling update, one tiny launch: scale[b] = max(margin * amax[b] / 448, 1e-12),
  *   inv_scale[b] = 1 / scale[b], amax[b] = 0 for the three blocks (all fp32 device words; amax as written by the atomicMax of
  *   non-negative float bit patterns).

@@ -1,4 +1,5 @@
-// Temporal attention for gfx950: per (pixel, head) softmax(Q K^T * scale) V over F in {16, 32} frames.
+// Temporal attention for gfx950: per (pixel, head) softmax(Q K^T * scale) V over 1 <= F <= 32 frames (one or two 16-frame tiles, the last
+// one partial when F % 16 != 0: see PART at temporal_attn_kernel).
 //
 // Replaces head_to_batch_dim + baddbmm + softmax + bmm + batch_to_head_dim of
 // fmc/models/attention_processor.py:271-281 (PoseAdaptorAttnProcessor) and :61-67 (AttnProcessor)
@@ -56,10 +57,13 @@ __device__ __forceinline__ void load_f8(const float* p, bool valid, F8<float>& f
     }
     split_bf16x8(v, f.hi, f.lo);
 }
-__device__ __forceinline__ void mma_qk(const F8<bf16_t>& a, const F8<bf16_t>& b, f32x4& acc) {
+// LL (fp32 storage only): add the lo * lo product that the x3 form drops (2^-18 of the term: a third of the x3 form's error, and the part that
+// does not average out when one key dominates a row).  The partial-tile forward kernels take it -- see the note at temporal_attn_kernel.
+template <bool LL = false> __device__ __forceinline__ void mma_qk(const F8<bf16_t>& a, const F8<bf16_t>& b, f32x4& acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
 }
-__device__ __forceinline__ void mma_qk(const F8<float>& a, const F8<float>& b, f32x4& acc) {
+template <bool LL = false> __device__ __forceinline__ void mma_qk(const F8<float>& a, const F8<float>& b, f32x4& acc) {
+    if constexpr (LL) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.lo, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
@@ -77,10 +81,11 @@ __device__ __forceinline__ void make_f4(const float (&v)[4], F4<float>& f) {
     f.hi = s16x4{(short)h[0], (short)h[1], (short)h[2], (short)h[3]};
     f.lo = s16x4{(short)l[0], (short)l[1], (short)l[2], (short)l[3]};
 }
-__device__ __forceinline__ void mma_pv(const F4<bf16_t>& a, const F4<bf16_t>& b, f32x4& acc) {
+template <bool LL = false> __device__ __forceinline__ void mma_pv(const F4<bf16_t>& a, const F4<bf16_t>& b, f32x4& acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.hi, b.hi, acc, 0, 0, 0);
 }
-__device__ __forceinline__ void mma_pv(const F4<float>& a, const F4<float>& b, f32x4& acc) {
+template <bool LL = false> __device__ __forceinline__ void mma_pv(const F4<float>& a, const F4<float>& b, f32x4& acc) {
+    if constexpr (LL) acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.lo, b.lo, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.lo, b.hi, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.hi, b.lo, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.hi, b.hi, acc, 0, 0, 0);
@@ -98,11 +103,25 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, const float (
 template <> __device__ __forceinline__ void st4<float>(float* p, const float (&v)[4]) {
     *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
 }
+__device__ __forceinline__ void zero8(float (&v)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = 0.f;
+}
 
-// FT = F/16 frame tiles; NK32 = ceil(D/32) k-steps of the QK^T reduction
-template <typename T, int FT, int NK32, int NWV>     // NWV waves per unit (they split its heads)
+// A clip of 1 <= P.F <= 32 frames occupies FT = ceil(P.F / 16) frame tiles of 16 rows.  PART = the last tile is partial (P.F % 16 != 0): the
+// LDS tiles keep their FT * 16 rows, but rows >= P.F are pad -- never read from nor written to global memory (in native [B, F, P, C] storage
+// frame P.F of clip b IS frame 0 of clip b + 1), zero in LDS (a V pad row meets P = 0 in the MFMA, and 0 * NaN is NaN), and as keys their scores
+// are REPLACED by -inf before the row maximum.  Query pad rows are computed (on zeros: finite) and not stored.  Without PART every test on PART
+// below is compile-time false and Fr is the compile-time tile height: the whole-tile instantiations compile to the instruction streams they had.
+// fp32 storage: the PART forward kernels compute Q K^T and P V as four split products (lo * lo included), not three.  The x3 form's rel-inf error
+// against the fp32 oracle is 0.9 - 1.6e-5 on most inputs but reached 2.07e-5 on one (F = 25, d = 8), beyond the 2e-5 the parity mode is held to;
+// with lo * lo the worst of 110 draws over all lengths at that shape is 1.3e-5.  The whole-tile kernels keep x3: their results must not move.
+// FT = ceil(F/16) frame tiles; NK32 = ceil(D/32) k-steps of the QK^T reduction
+template <typename T, int FT, int NK32, int NWV, bool PART>     // NWV waves per unit (they split its heads)
 __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams P) {
     constexpr int F = FT * 16;
+    const int Fr = PART ? P.F : F;                   // real frames (rows of global memory)
+    constexpr bool LL = PART && sizeof(T) == 4;      // fp32 storage, partial tile: four split products (see above)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int D = P.D, GH = P.GH, CW = GH * D, CPR = CW / 8, PITCH = CW + 8;
     T* Qs = reinterpret_cast<T*>(smem_raw);  // [F][PITCH]; O overwrites it head by head
@@ -139,7 +158,8 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
 #pragma unroll
                 for (int j = 0; j < MAXC; ++j) {
                     const int c = tid + j * NTH, f = c / CPR, ch = c - f * CPR;
-                    if (c < chunks) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 8);
+                    if constexpr (PART) r[which][j] = u32x4{0u, 0u, 0u, 0u};
+                    if (c < chunks && (!PART || f < Fr)) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 8);
                 }
             }
 #pragma unroll
@@ -159,7 +179,8 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
 #pragma unroll 5
                 for (int c = tid; c < chunks; c += NTH) {
                     const int f = c / CPR, ch = c - f * CPR;
-                    *reinterpret_cast<u32x4*>(dst + f * PITCH + ch * 8) = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 8);
+                    if (PART && f >= Fr) *reinterpret_cast<u32x4*>(dst + f * PITCH + ch * 8) = u32x4{0u, 0u, 0u, 0u};
+                    else *reinterpret_cast<u32x4*>(dst + f * PITCH + ch * 8) = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 8);
                 }
             }
         }
@@ -172,7 +193,8 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
             for (int c = tid; c < chunks; c += NTH) {
                 const int f = c / CPR, ch = c - f * CPR;
                 float v[8];
-                Vec8<T>::load(src + (int64_t)f * P.fs + ch * 8, v);
+                if (PART && f >= Fr) zero8(v);
+                else Vec8<T>::load(src + (int64_t)f * P.fs + ch * 8, v);
                 Vec8<T>::store(dst + f * PITCH + ch * 8, v);
             }
         }
@@ -203,7 +225,7 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
                     const int d0 = ks * 32 + lg * 8;
                     F8<T> kf;
                     load_f8(Ks + (kt * 16 + l15) * PITCH + hc + d0, d0 < D, kf);
-                    mma_qk(kf, qf[ks], s[kt]);
+                    mma_qk<LL>(kf, qf[ks], s[kt]);
                 }
             }
             // ---- softmax over keys: lane holds keys kt*16 + lg*4 + r of query qt*16 + l15 --------------------
@@ -211,7 +233,11 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
 #pragma unroll
             for (int kt = 0; kt < FT; ++kt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] *= P.scale_log2; mx = fmaxf(mx, s[kt][r]); }
+                for (int r = 0; r < 4; ++r) {
+                    s[kt][r] *= P.scale_log2;
+                    if (PART && kt == FT - 1 && (FT - 1) * 16 + lg * 4 + r >= Fr) s[kt][r] = -INFINITY;     // pad key: replaced, not added to
+                    mx = fmaxf(mx, s[kt][r]);
+                }
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             float sum = 0.f;
@@ -252,7 +278,7 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
                             v4[i] = dA < D ? ldsf(Vs + (kt * 16 + lg * 4 + i) * PITCH + hc + dA) : 0.f;
                         make_f4(v4, vf);
                     }
-                    mma_pv(vf, pf[kt], o);
+                    mma_pv<LL>(vf, pf[kt], o);
                 }
                 const int dO = dt * 16 + lg * 4;    // 4 consecutive output channels of query l15
                 if (dO < D) {
@@ -266,8 +292,9 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
 
     // ---- O: LDS -> global ------------------------------------------------------------------------------
     T* og = (T*)P.o + out_off;
+    const int ochunks = Fr * CPR;                    // (pad rows stay in LDS)
 #pragma unroll 5
-    for (int c = tid; c < chunks; c += NTH) {
+    for (int c = tid; c < ochunks; c += NTH) {
         const int f = c / CPR, ch = c - f * CPR;
         if constexpr (sizeof(T) == 2) {
             *reinterpret_cast<u32x4*>(og + (int64_t)f * P.ofs + ch * 8) = *reinterpret_cast<const u32x4*>(Qs + f * PITCH + ch * 8);
@@ -297,9 +324,10 @@ struct TA8Params {
 
 __device__ __forceinline__ float fp8_to_f32(unsigned char b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
 
-template <int FT, int NK32>
+template <int FT, int NK32, bool PART>               // PART: see temporal_attn_kernel (pad rows: zero bytes in LDS, nothing in global memory)
 __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params P) {
     constexpr int F = FT * 16;
+    const int Fr = PART ? P.F : F;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int D = P.D, GH = P.GH, CW = GH * D, CPR16 = CW / 16, PB = CW + 16;      // byte pitch of the fp8 rows
     const int OPITCH = CW + 8;                                                      // bf16 pitch of the O rows
@@ -330,7 +358,8 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
 #pragma unroll
             for (int j = 0; j < MAXC8; ++j) {
                 const int c = tid + j * 256, f = c / CPR16, ch = c - f * CPR16;
-                if (c < chunks) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 16);
+                if constexpr (PART) r[which][j] = u32x4{0u, 0u, 0u, 0u};
+                if (c < chunks && (!PART || f < Fr)) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 16);
             }
         }
 #pragma unroll
@@ -350,7 +379,8 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
 #pragma unroll 5
             for (int c = tid; c < chunks; c += NTH) {
                 const int f = c / CPR16, ch = c - f * CPR16;
-                *reinterpret_cast<u32x4*>(dst + f * PB + ch * 16) = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 16);
+                if (PART && f >= Fr) *reinterpret_cast<u32x4*>(dst + f * PB + ch * 16) = u32x4{0u, 0u, 0u, 0u};
+                else *reinterpret_cast<u32x4*>(dst + f * PB + ch * 16) = *reinterpret_cast<const u32x4*>(src + (int64_t)f * P.fs + ch * 16);
             }
         }
     }
@@ -381,7 +411,11 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
 #pragma unroll
             for (int kt = 0; kt < FT; ++kt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] *= sl2; mx = fmaxf(mx, s[kt][r]); }
+                for (int r = 0; r < 4; ++r) {
+                    s[kt][r] *= sl2;
+                    if (PART && kt == FT - 1 && (FT - 1) * 16 + lg * 4 + r >= Fr) s[kt][r] = -INFINITY;
+                    mx = fmaxf(mx, s[kt][r]);
+                }
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             float sum = 0.f;
@@ -422,7 +456,7 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
     }
     __syncthreads();
     bf16_t* og = P.o + out_off;
-    const int CPR = CW / 8, ochunks = F * CPR;
+    const int CPR = CW / 8, ochunks = Fr * CPR;
 #pragma unroll 5
     for (int c = tid; c < ochunks; c += NTH) {
         const int f = c / CPR, ch = c - f * CPR;
@@ -455,9 +489,14 @@ template <typename T> __device__ __forceinline__ void col_f4(const T* base, int 
     make_f4(v4, f);
 }
 
-template <typename T, int FT, int NK32>
+// PART (see temporal_attn_kernel): the Q, K, V, dO pad rows are zero in LDS; P and dS of pad keys are zero in both layouts (L1: the score is
+// replaced by -inf, so P = 0 and with it P .* dP and dS; L2: P is set to 0, and dS = P * (..)), so rowsum(P .* dP) runs over the valid keys.
+// Pad QUERIES need no mask: their dO row is zero, so dP = 0, rowsum = 0, dS = 0, and P meets only the zero dO row in dV.  dQ / dK / dV pad
+// rows stay in LDS.
+template <typename T, int FT, int NK32, bool PART>
 __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParams P) {
     constexpr int F = FT * 16;
+    const int Fr = PART ? P.F : F;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int D = P.D, GH = P.GH, CW = GH * D, CPR = CW / 8, PITCH = CW + 8;
     T* Qs = reinterpret_cast<T*>(smem_raw);
@@ -496,7 +535,8 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
 #pragma unroll
                 for (int j = 0; j < MAXCB; ++j) {
                     const int c = tid + j * 256, f = c / CPR, ch = c - f * CPR;
-                    if (c < chunks) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * fstride + ch * 8);
+                    if constexpr (PART) r[which][j] = u32x4{0u, 0u, 0u, 0u};
+                    if (c < chunks && (!PART || f < Fr)) r[which][j] = *reinterpret_cast<const u32x4*>(src + (int64_t)f * fstride + ch * 8);
                 }
             }
 #pragma unroll
@@ -519,7 +559,7 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
             const float sc = P.q8_scales[which];
             for (int c = tid; c < chunks; c += NTH) {
                 const int f = c / CPR, ch = c - f * CPR;
-                const u32x2 w = *reinterpret_cast<const u32x2*>(src8 + (int64_t)f * P.fs + ch * 8);
+                const u32x2 w = (PART && f >= Fr) ? u32x2{0u, 0u} : *reinterpret_cast<const u32x2*>(src8 + (int64_t)f * P.fs + ch * 8);
                 float v[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = fp8_to_f32((unsigned char)((w[i >> 2] >> (8 * (i & 3))) & 0xffu)) * sc;
@@ -534,7 +574,8 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
         for (int c = tid; c < chunks; c += NTH) {
             const int f = c / CPR, ch = c - f * CPR;
             float v[8];
-            Vec8<T>::load(src + (int64_t)f * fstride + ch * 8, v);
+            if (PART && f >= Fr) zero8(v);
+            else Vec8<T>::load(src + (int64_t)f * fstride + ch * 8, v);
             Vec8<T>::store(dst + f * PITCH + ch * 8, v);
         }
     }
@@ -573,7 +614,11 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
 #pragma unroll
             for (int kt = 0; kt < FT; ++kt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { s[kt][r] *= P.scale_log2; mx = fmaxf(mx, s[kt][r]); }
+                for (int r = 0; r < 4; ++r) {
+                    s[kt][r] *= P.scale_log2;
+                    if (PART && kt == FT - 1 && (FT - 1) * 16 + lg * 4 + r >= Fr) s[kt][r] = -INFINITY;     // pad key: P = 0, so dS = 0 too
+                    mx = fmaxf(mx, s[kt][r]);
+                }
             mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             float sum = 0.f;
@@ -647,6 +692,7 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
                     const float m = __shfl(st_m[qt], ql, 64), inv = __shfl(st_inv[qt], ql, 64);
                     const float dsum = __shfl(st_d[qt], ql, 64);
                     p4[r] = exp2f(s2[r] * P.scale_log2 - m) * inv;
+                    if (PART && kt == FT - 1 && (FT - 1) * 16 + l15 >= Fr) p4[r] = 0.f;      // pad key (this lane's column)
                     d4[r] = p4[r] * (dp2[r] - dsum) * P.scale;
                 }
                 make_f4(p4, pf[qt]);
@@ -679,8 +725,9 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
     for (int which = 0; which < 3; ++which) {
         T* dst = (T*)(which == 0 ? P.dq : which == 1 ? P.dk : P.dv) + dq_off;
         const T* srcl = which == 0 ? dQs : which == 1 ? dKs : dVs;
+        const int ochunks = Fr * CPR;
 #pragma unroll 5
-        for (int c = tid; c < chunks; c += NTH) {
+        for (int c = tid; c < ochunks; c += NTH) {
             const int f = c / CPR, ch = c - f * CPR;
             float v[8];
             Vec8<T>::load(srcl + f * PITCH + ch * 8, v);
@@ -689,37 +736,45 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
     }
 }
 
-template <typename T, int FT, int NK32>
+template <typename T, int FT, int NK32, bool PART>
 void launch_ta_bwd(const TABwdParams& P, hipStream_t st) {
     const int CW = P.GH * P.D;
     const size_t lds = sizeof(T) * 7 * (size_t)(FT * 16) * (CW + 8);
     if (lds > 64 * 1024) {
         static FmcPerDeviceFlag raised;
         if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_bwd_kernel<T, FT, NK32>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_bwd_kernel<T, FT, NK32, PART>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             raised = true;
         }
     }
     const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
     dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    hipLaunchKernelGGL((temporal_attn_bwd_kernel<T, FT, NK32>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((temporal_attn_bwd_kernel<T, FT, NK32, PART>), grid, block, lds, st, P);
 }
 
-template <typename T, int FT>
+template <typename T, int FT, bool PART>
 int dispatch_ta_bwd_k(const TABwdParams& P, hipStream_t st) {
     switch ((P.D + 31) / 32) {
-        case 1: launch_ta_bwd<T, FT, 1>(P, st); break;
-        case 2: launch_ta_bwd<T, FT, 2>(P, st); break;
-        case 3: launch_ta_bwd<T, FT, 3>(P, st); break;
-        case 4: launch_ta_bwd<T, FT, 4>(P, st); break;
-        case 5: launch_ta_bwd<T, FT, 5>(P, st); break;
+        case 1: launch_ta_bwd<T, FT, 1, PART>(P, st); break;
+        case 2: launch_ta_bwd<T, FT, 2, PART>(P, st); break;
+        case 3: launch_ta_bwd<T, FT, 3, PART>(P, st); break;
+        case 4: launch_ta_bwd<T, FT, 4, PART>(P, st); break;
+        case 5: launch_ta_bwd<T, FT, 5, PART>(P, st); break;
         default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: head dim %d > 160", P.D);
     }
     return 0;
 }
 
-template <typename T, int FT, int NK32>
+// frame tiles and partial flag from the real frame count: F = 16 / 32 take the whole-tile kernels they always took
+template <typename T>
+int dispatch_ta_bwd(const TABwdParams& P, hipStream_t st) {
+    if (P.F == 16) return dispatch_ta_bwd_k<T, 1, false>(P, st);
+    if (P.F == 32) return dispatch_ta_bwd_k<T, 2, false>(P, st);
+    return P.F < 16 ? dispatch_ta_bwd_k<T, 1, true>(P, st) : dispatch_ta_bwd_k<T, 2, true>(P, st);
+}
+
+template <typename T, int FT, int NK32, bool PART>
 void launch_ta(const TAParams& P, hipStream_t st) {
     const int CW = P.GH * P.D;
     const size_t lds = sizeof(T) * 3 * (size_t)(FT * 16) * (CW + 8);
@@ -729,26 +784,26 @@ void launch_ta(const TAParams& P, hipStream_t st) {
         if (lds > 64 * 1024) {
             static FmcPerDeviceFlag raised;
             if (!raised) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_kernel<T, FT, NK32, NW>),
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_kernel<T, FT, NK32, NW, PART>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 raised = true;
             }
         }
-        hipLaunchKernelGGL((temporal_attn_kernel<T, FT, NK32, NW>), grid, dim3(64 * NW), lds, st, P);
+        hipLaunchKernelGGL((temporal_attn_kernel<T, FT, NK32, NW, PART>), grid, dim3(64 * NW), lds, st, P);
     };
     if (P.GH >= 4) go(std::integral_constant<int, 4>{});
     else if (P.GH >= 2) go(std::integral_constant<int, 2>{});
     else go(std::integral_constant<int, 1>{});
 }
 
-template <typename T, int FT>
+template <typename T, int FT, bool PART>
 int dispatch_ta_k(const TAParams& P, hipStream_t st) {
     switch ((P.D + 31) / 32) {
-        case 1: launch_ta<T, FT, 1>(P, st); break;
-        case 2: launch_ta<T, FT, 2>(P, st); break;
-        case 3: launch_ta<T, FT, 3>(P, st); break;
-        case 4: launch_ta<T, FT, 4>(P, st); break;
-        case 5: launch_ta<T, FT, 5>(P, st); break;
+        case 1: launch_ta<T, FT, 1, PART>(P, st); break;
+        case 2: launch_ta<T, FT, 2, PART>(P, st); break;
+        case 3: launch_ta<T, FT, 3, PART>(P, st); break;
+        case 4: launch_ta<T, FT, 4, PART>(P, st); break;
+        case 5: launch_ta<T, FT, 5, PART>(P, st); break;
         default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn: head dim %d > 160", P.D);
     }
     return 0;
@@ -756,10 +811,14 @@ int dispatch_ta_k(const TAParams& P, hipStream_t st) {
 
 template <typename T>
 int dispatch_ta(const TAParams& P, hipStream_t st) {
-    if (P.F == 16) return dispatch_ta_k<T, 1>(P, st);
-    if (P.F == 32) return dispatch_ta_k<T, 2>(P, st);
-    FMC_FAIL(FMC_E_SHAPE, "temporal_attn: F must be 16 or 32 (got %d)", P.F);
+    if (P.F < 1 || P.F > 32) FMC_FAIL(FMC_E_SHAPE, "temporal_attn: F must be in 1..32 (got %d)", P.F);
+    if (P.F == 16) return dispatch_ta_k<T, 1, false>(P, st);
+    if (P.F == 32) return dispatch_ta_k<T, 2, false>(P, st);
+    return P.F < 16 ? dispatch_ta_k<T, 1, true>(P, st) : dispatch_ta_k<T, 2, true>(P, st);
 }
+
+// rows of the LDS tiles: the frame count rounded up to whole 16-row tiles
+inline int ta_tile_rows(int F) { return (F + 15) / 16 * 16; }
 
 }  // namespace
 
@@ -803,8 +862,8 @@ extern "C" int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v
                                      void* stream) {
     if (!q || !k || !v || !d_o || !dq || !dk || !dv) FMC_FAIL(FMC_E_NULL, "temporal_attn_bwd: NULL tensor");
     if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "temporal_attn_bwd: dtype %d", dtype);
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || (F != 16 && F != 32))
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: need F in {16,32}, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
     const int64_t strides[] = {clip_stride, frame_stride, pix_stride, do_clip_stride, do_frame_stride, do_pix_stride,
                                dq_clip_stride, dq_frame_stride, dq_pix_stride};
     for (int64_t s : strides)
@@ -816,11 +875,11 @@ extern "C" int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v
     P.q = q; P.k = k; P.v = v; P.d_o = d_o; P.dq = dq; P.dk = dk; P.dv = dv;
     P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
     // head group: largest divisor of H whose 7 LDS tiles fit in ~150 KiB and whose rows are <= 320 channels
-    const size_t esz = dtype == FMC_BF16 ? 2 : 4;
+    const size_t esz = dtype == FMC_BF16 ? 2 : 4, FR = (size_t)ta_tile_rows(F);
     int gh = 1;
     for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320 && 7 * (size_t)F * (g * D + 8) * esz <= 150 * 1024) gh = g;
-    if (7 * (size_t)F * (gh * D + 8) * esz > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: F=%d D=%d does not fit LDS in this dtype", F, D);
+        if (H % g == 0 && g * D <= 320 && 7 * FR * (g * D + 8) * esz <= 150 * 1024) gh = g;
+    if (7 * FR * (gh * D + 8) * esz > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: F=%d D=%d does not fit LDS in this dtype", F, D);
     P.GH = gh;
     P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;
     P.ocs = do_clip_stride; P.ofs = do_frame_stride; P.ops = do_pix_stride;
@@ -829,38 +888,38 @@ extern "C" int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v
     P.q8_scales = nullptr;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (dtype == FMC_BF16) rc = F == 16 ? dispatch_ta_bwd_k<bf16_t, 1>(P, st) : dispatch_ta_bwd_k<bf16_t, 2>(P, st);
-    else rc = F == 16 ? dispatch_ta_bwd_k<float, 1>(P, st) : dispatch_ta_bwd_k<float, 2>(P, st);
+    if (dtype == FMC_BF16) rc = dispatch_ta_bwd<bf16_t>(P, st);
+    else rc = dispatch_ta_bwd<float>(P, st);
     if (rc) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_bwd");
     return 0;
 }
 
 namespace {
-template <int FT, int NK32>
+template <int FT, int NK32, bool PART>
 void launch_ta8(const TA8Params& P, hipStream_t st) {
     const int CW = P.GH * P.D;
     const size_t lds = 3 * (size_t)(FT * 16) * (CW + 16) + sizeof(bf16_t) * (size_t)(FT * 16) * (CW + 8);
     if (lds > 64 * 1024) {
         static FmcPerDeviceFlag raised;
         if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_fp8_kernel<FT, NK32>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_fp8_kernel<FT, NK32, PART>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             raised = true;
         }
     }
     const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
     dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    hipLaunchKernelGGL((temporal_attn_fp8_kernel<FT, NK32>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((temporal_attn_fp8_kernel<FT, NK32, PART>), grid, block, lds, st, P);
 }
-template <int FT>
+template <int FT, bool PART>
 int dispatch_ta8(const TA8Params& P, hipStream_t st) {
     switch ((P.D + 31) / 32) {
-        case 1: launch_ta8<FT, 1>(P, st); break;
-        case 2: launch_ta8<FT, 2>(P, st); break;
-        case 3: launch_ta8<FT, 3>(P, st); break;
-        case 4: launch_ta8<FT, 4>(P, st); break;
-        case 5: launch_ta8<FT, 5>(P, st); break;
+        case 1: launch_ta8<FT, 1, PART>(P, st); break;
+        case 2: launch_ta8<FT, 2, PART>(P, st); break;
+        case 3: launch_ta8<FT, 3, PART>(P, st); break;
+        case 4: launch_ta8<FT, 4, PART>(P, st); break;
+        case 5: launch_ta8<FT, 5, PART>(P, st); break;
         default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: head dim %d > 160", P.D);
     }
     return 0;
@@ -872,8 +931,8 @@ extern "C" int fmc_temporal_attn_fp8_fwd(const void* q, const void* k, const voi
                                          int64_t frame_stride, int64_t pix_stride, int64_t o_clip_stride,
                                          int64_t o_frame_stride, int64_t o_pix_stride, float scale, void* stream) {
     if (!q || !k || !v || !o || !scales) FMC_FAIL(FMC_E_NULL, "temporal_attn_fp8: NULL tensor");
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || (F != 16 && F != 32))
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: need F in {16,32}, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
     const int64_t strides[] = {clip_stride, frame_stride, pix_stride};
     for (int64_t s : strides)
         if (s % 16) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_fp8: q/k/v strides must be multiples of 16 bytes");
@@ -895,7 +954,8 @@ extern "C" int fmc_temporal_attn_fp8_fwd(const void* q, const void* k, const voi
     P.ocs = o_clip_stride; P.ofs = o_frame_stride; P.ops = o_pix_stride;
     P.scale_log2 = scale * LOG2E;
     hipStream_t st = (hipStream_t)stream;
-    const int rc = F == 16 ? dispatch_ta8<1>(P, st) : dispatch_ta8<2>(P, st);
+    const int rc = F == 16 ? dispatch_ta8<1, false>(P, st) : F == 32 ? dispatch_ta8<2, false>(P, st)
+                 : F < 16 ? dispatch_ta8<1, true>(P, st) : dispatch_ta8<2, true>(P, st);
     if (rc) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_fp8_fwd");
     return 0;
@@ -908,8 +968,8 @@ extern "C" int fmc_temporal_attn_fp8_bwd(const void* q, const void* k, const voi
                                          int64_t dq_clip_stride, int64_t dq_frame_stride, int64_t dq_pix_stride, float scale,
                                          void* stream) {
     if (!q || !k || !v || !scales || !d_o || !dq || !dk || !dv) FMC_FAIL(FMC_E_NULL, "temporal_attn_fp8_bwd: NULL tensor");
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || (F != 16 && F != 32))
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: need F in {16,32}, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
     const int64_t strides[] = {clip_stride, frame_stride, pix_stride, do_clip_stride, do_frame_stride, do_pix_stride,
                                dq_clip_stride, dq_frame_stride, dq_pix_stride};
     for (int64_t s : strides)
@@ -917,10 +977,11 @@ extern "C" int fmc_temporal_attn_fp8_bwd(const void* q, const void* k, const voi
     TABwdParams P;
     P.q = q; P.k = k; P.v = v; P.d_o = d_o; P.dq = dq; P.dk = dk; P.dv = dv;
     P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
+    const size_t FR = (size_t)ta_tile_rows(F);
     int gh = 1;
     for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320 && 7 * (size_t)F * (g * D + 8) * 2 <= 150 * 1024) gh = g;
-    if (7 * (size_t)F * (gh * D + 8) * 2 > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: F=%d D=%d does not fit LDS", F, D);
+        if (H % g == 0 && g * D <= 320 && 7 * FR * (g * D + 8) * 2 <= 150 * 1024) gh = g;
+    if (7 * FR * (gh * D + 8) * 2 > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: F=%d D=%d does not fit LDS", F, D);
     P.GH = gh;
     P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;          // bytes = elements for the e4m3 inputs
     P.ocs = do_clip_stride; P.ofs = do_frame_stride; P.ops = do_pix_stride;
@@ -928,7 +989,7 @@ extern "C" int fmc_temporal_attn_fp8_bwd(const void* q, const void* k, const voi
     P.scale = scale; P.scale_log2 = scale * LOG2E;
     P.q8_scales = (const float*)scales;
     hipStream_t st = (hipStream_t)stream;
-    const int rc = F == 16 ? dispatch_ta_bwd_k<bf16_t, 1>(P, st) : dispatch_ta_bwd_k<bf16_t, 2>(P, st);
+    const int rc = dispatch_ta_bwd<bf16_t>(P, st);
     if (rc) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_fp8_bwd");
     return 0;
