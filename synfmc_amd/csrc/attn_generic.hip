@@ -233,13 +233,7 @@ template <typename T, int NKS>
 int ag_launch(const AGParams& P, hipStream_t st) {
     constexpr int D = 32 * NKS, NPL = AGPlanes<T>::N;
     constexpr int lds = NPL * (AG_KB * (D + 8) + D * AG_VP) * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_generic_kernel<T, NKS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        raised = true;
-    }
-    hipLaunchKernelGGL((attn_generic_kernel<T, NKS>), dim3((unsigned)((P.Sq + 63) / 64), (unsigned)(P.B * P.H)), dim3(256), lds, st, P);
+    fmc_launch<attn_generic_kernel<T, NKS>>(dim3((unsigned)((P.Sq + 63) / 64), (unsigned)(P.B * P.H)), dim3(256), lds, st, P);
     return 0;
 }
 

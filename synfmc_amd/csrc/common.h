@@ -23,14 +23,35 @@ void fmc_set_error(const char* fmt, ...);
     } while (0)
 
 // ---- per-device host state -------------------------------------------------------------------------
-// A process may drive several GPUs: the CU count and the "dynamic-LDS attribute raised" flags are kept per device id.
+// A process may drive several GPUs: the CU count and the dynamic-LDS size that fmc_launch has raised a kernel to are kept per device id
+// (64 slots, device & 63), never per process.
 int fmc_device();                 // the calling thread's current device (0 when the runtime cannot say)
 int fmc_cu_count();               // compute units of that device, looked up once per device
-struct FmcPerDeviceFlag {         // `static FmcPerDeviceFlag raised; if (!raised) { ...; raised = true; }` -- once per device, not per process
-    unsigned long long mask = 0;
-    bool operator!() const { return !((mask >> (fmc_device() & 63)) & 1ull); }
-    FmcPerDeviceFlag& operator=(bool v) { if (v) mask |= 1ull << (fmc_device() & 63); return *this; }
-};
+
+// A/B switches: atoi of the environment variable, or dflt when it is unset.  Call sites keep the result in a `static const int`.
+int fmc_env_int(const char* name, int dflt);
+
+// The launch of a kernel that may need 64 KiB or more of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize has to be raised
+// before the first such launch of every instantiation on every device.  Kept here per instantiation and device: the LARGEST size
+// raised so far (a size, not a flag -- one ring-kernel instantiation runs with two LDS sizes), raised again when a launch asks for
+// more.  Below 64 KiB the launch is the only runtime call; from there on one hipGetDevice is added.  A refused attribute shows as a
+// failed launch (FMC_CHECK_LAUNCH).
+// hipcc emits a unit's kernels in the order in which their instantiations are first named, and the launch is now the only place that
+// names them: a launcher whose branches look reordered ("if (!ln_stats)" first, a `form` index before a flat list of launches) lists
+// them in the order that keeps the device code object byte-identical to the one built before this helper existed.  New launchers may
+// use any order.
+template <auto Kernel, class... A>
+void fmc_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    if (lds >= 64 * 1024) {
+        static size_t raised[64];
+        size_t& r = raised[fmc_device() & 63];
+        if (lds > r) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            r = lds;
+        }
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
 
 static inline bool fmc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

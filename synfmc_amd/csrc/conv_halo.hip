@@ -573,17 +573,10 @@ extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, co
     const int64_t hs = upsample2x ? H / 2 : H, ws = upsample2x ? W / 2 : W;
     P.x_bytes = (int64_t)n_img * hs * ws * Cin1 * 2; P.x2_bytes = (int64_t)n_img * hs * ws * (Cin - Cin1) * 2;
     P.w_bytes = (int64_t)Cout * 9 * Cin * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        raised = true;
-    }
     const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    if (!gn_coef) hipLaunchKernelGGL(conv_halo_kernel<0>, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else if (gn_act) hipLaunchKernelGGL(conv_halo_kernel<1>, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL(conv_halo_kernel<2>, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    if (!gn_coef) fmc_launch<conv_halo_kernel<0>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    else if (gn_act) fmc_launch<conv_halo_kernel<1>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    else fmc_launch<conv_halo_kernel<2>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_bf16");
     return 0;
 }
@@ -629,13 +622,8 @@ extern "C" int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, c
     P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = Ws / TW; P.tiles_n = 4 * (Cout / BN);
     P.x_bytes = (int64_t)n_img * Hs * Ws * Cin * 2; P.x2_bytes = 0;
     P.w_bytes = (int64_t)Cout * 16 * Cin * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        raised = true;
-    }
     const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    hipLaunchKernelGGL((conv_halo_kernel<0, true>), dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    fmc_launch<conv_halo_kernel<0, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_bf16");
     return 0;
 }

@@ -498,7 +498,7 @@ template <int TW, int NWV, bool PH = false> int launch_c4(C4Params& P, hipStream
     P.tiles_x = P.W / TW;
     P.tiles_p = (P.n_img * P.tiles_y * P.tiles_x + G::NB - 1) / G::NB;
     {   // XCD grid (see the kernel): FMC_C4_XCD = 0 contiguous ranges (rounds 5's order), 1 / 2 / 4 / 8 forced where it divides, unset = least fabric traffic
-        static const int forced = getenv("FMC_C4_XCD") ? atoi(getenv("FMC_C4_XCD")) : -1;
+        static const int forced = fmc_env_int("FMC_C4_XCD", -1);
         const int tnv = P.tiles_n * P.splits;
         double best = 0.;
         P.xcd_pc = 0;
@@ -510,12 +510,7 @@ template <int TW, int NWV, bool PH = false> int launch_c4(C4Params& P, hipStream
             }
         }
     }
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo4_kernel<TW, NWV, PH>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        raised = true;
-    }
-    hipLaunchKernelGGL((conv_halo4_kernel<TW, NWV, PH>), dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
+    fmc_launch<conv_halo4_kernel<TW, NWV, PH>>(dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
     if (P.splits > 1) {
         const int64_t chunks = (int64_t)P.n_img * P.H * P.W * (P.cout / 8);
         const unsigned grid = (unsigned)((chunks + 255) / 256 < 2048 ? (chunks + 255) / 256 : 2048);

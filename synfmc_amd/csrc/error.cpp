@@ -1,6 +1,7 @@
 // Thread-local error message + version for libfmc_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,11 @@ void fmc_set_error(const char* fmt, ...) {
 
 extern "C" int fmc_version(void) { return FMC_VERSION; }
 extern "C" const char* fmc_last_error(void) { return g_err; }
+
+int fmc_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 int fmc_device() {
     int dev = 0;

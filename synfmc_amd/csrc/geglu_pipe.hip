@@ -362,17 +362,11 @@ extern "C" int fmc_geglu_pipe_ln_bf16(const void* h, void* out, const float* ln_
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
     P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
     constexpr int lds320 = 80 * 320 * 2 + 640, lds640 = 80 * 640 * 2 + 640, lds320w = 160 * 320 * 2 + 1280;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_pipe_kernel<320, 4, 5, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds320);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_pipe_kernel<640, 4, 5, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds640);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_pipe_kernel<320, 8, 10, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds320w);
-        raised = true;
-    }
     hipStream_t st = (hipStream_t)stream;
-    if (variant == 1) hipLaunchKernelGGL((geglu_pipe_kernel<320, 8, 10, 2>), dim3((unsigned)(M / 160)), dim3(512), lds320w, st, P);
-    else if (C == 320) hipLaunchKernelGGL((geglu_pipe_kernel<320, 4, 5, 4>), dim3((unsigned)(M / 80)), dim3(256), lds320, st, P);
-    else hipLaunchKernelGGL((geglu_pipe_kernel<640, 4, 5, 4>), dim3((unsigned)(M / 80)), dim3(256), lds640, st, P);
+    // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
+    if (variant == 0 && C == 320) fmc_launch<geglu_pipe_kernel<320, 4, 5, 4>>(dim3((unsigned)(M / 80)), dim3(256), lds320, st, P);
+    else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4>>(dim3((unsigned)(M / 80)), dim3(256), lds640, st, P);
+    else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2>>(dim3((unsigned)(M / 160)), dim3(512), lds320w, st, P);
     FMC_CHECK_LAUNCH("fmc_geglu_pipe_ln_bf16");
     return 0;
 }

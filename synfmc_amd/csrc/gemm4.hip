@@ -212,12 +212,7 @@ extern "C" int fmc_linear4_bf16(const void* x, const void* w, const void* bias, 
     P.out = (bf16_t*)out; P.M = M; P.N = N; P.K = K; P.lda = ldx; P.ldres = ldres; P.ldo = ldo; P.alpha = alpha;
     P.tiles_m = (int)((M + BM - 1) / BM); P.tiles_n = (N + BN - 1) / BN;
     P.a_bytes = ((M - 1) * ldx + K) * 2; P.w_bytes = (int64_t)N * K * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        raised = true;
-    }
-    hipLaunchKernelGGL(gemm4_kernel, dim3((unsigned)(P.tiles_m * P.tiles_n)), dim3(256), LDS_BYTES, (hipStream_t)stream, P);
+    fmc_launch<gemm4_kernel>(dim3((unsigned)(P.tiles_m * P.tiles_n)), dim3(256), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_linear4_bf16");
     return 0;
 }

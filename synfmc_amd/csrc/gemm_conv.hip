@@ -2312,21 +2312,36 @@ void gemm160p_kernel(const GemmParams P) {
 }
 
 int gemm_geometry_override() {   // FMC_GEMM_TILE = 0 (caller's choice) | 1..10: see fmc_hip.h
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMC_GEMM_TILE");
-        v = e ? atoi(e) : 0;
-    }
+    static const int v = fmc_env_int("FMC_GEMM_TILE", 0);
     return v;
 }
 
 int gemm_group_m_override() {   // FMC_GEMM_GM: m-tiles per group of the tile order (1 = row-major); unset = per launch
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("FMC_GEMM_GM");
-        v = e ? atoi(e) : -1;
-    }
+    static const int v = fmc_env_int("FMC_GEMM_GM", -1);
     return v;
+}
+
+int conv_tap_outer() {          // FMC_CONV_TAP_OUTER: A/B switch of the convolutions' k-loop order (GemmParams::tap_outer)
+    static const int v = fmc_env_int("FMC_CONV_TAP_OUTER", 0);
+    return v;
+}
+
+int g160_persist() {            // FMC_G160_PERSIST = 1 (default) | 0: never the persistent 160 x 320 form | 2: also launches of exactly one round
+    static const int v = fmc_env_int("FMC_G160_PERSIST", 1);
+    return v;
+}
+
+// Tile order (lin_to_tile): m-tiles per group.  Row-major (1) is optimal while the weight matrix fits an XCD's L2 or the c workgroups
+// an XCD runs at once already span all n-tiles; otherwise make their footprint square in bytes: gm x c/gm tiles with
+// gm * BM = (c / gm) * BN, where c = min(cap, tiles / 8); gm = round(sqrt(c * bn / bm)), evaluated in double and in this order.  Measured (tools/pmc_tile_order.sh): L2-miss bytes of
+// the level-1 / level-2 GEGLU projections 810 -> 172 MB and 1015 -> 221 MB per launch, launch time -4 .. -8 %; convs (3-5 n-tiles,
+// k-lockstep already shares W) only lost L2 hits to grouping, so they keep row-major: `token` = a token projection (MODE 0).
+int xcd_group_m(const GemmParams& P, bool token, double cap, int bn, int bm) {
+    if (gemm_group_m_override() > 0) return gemm_group_m_override();
+    if (!token || (int64_t)P.N * P.K * 2 <= (int64_t)5 << 19) return 1;
+    const double c = fmin(cap, (double)P.tiles_m * P.tiles_n / 8.0);
+    const int gm = (int)lround(sqrt(c * bn / bm));
+    return gm > 1 && P.tiles_n * 2 > 3 * (c / gm) ? gm : 1;
 }
 
 // second pass of a split-K launch: out = alpha * (sum_s ws[s] + bias) (+ temb) (+ residual), fixed summation order
@@ -2433,29 +2448,14 @@ __global__ __launch_bounds__(256) void sk_finish_kernel(const GemmParams P) {
     *reinterpret_cast<u32x2*>(P.out + m * P.ldo + n) = u32x2{pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
 }
 
-template <int MODE, int EPI, int WM, int WN, int MI, int BK, int STAGES, bool SK>
-void launch_gemm_k(GemmParams& P, unsigned grid, size_t lds, hipStream_t st) {
-    static size_t raised = 0;                            // (the LDS size of one instantiation depends on the epilogue variant)
-    if (lds > raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<MODE, EPI, WM, WN, MI, BK, STAGES, SK>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = lds;
-    }
-    hipLaunchKernelGGL((gemm_kernel<MODE, EPI, WM, WN, MI, BK, STAGES, SK>), dim3(grid), dim3(64 * WM * WN), lds, st, P);
-}
-
 template <int MODE, int EPI, int WM, int WN, int BK, int STAGES, int MI = 2>
 void launch_gemm_g(GemmParams& P, hipStream_t st) {
     constexpr int BM = 32 * MI * WM, BN = 64 * WN;
     P.tiles_m = (int)((P.M + BM - 1) / BM);
     P.tiles_n = (P.N + BN - 1) / BN;
-    P.group_m = 1;
-    {
-        static const int tap_outer = getenv("FMC_CONV_TAP_OUTER") ? atoi(getenv("FMC_CONV_TAP_OUTER")) : 0;
-        P.tap_outer = tap_outer;
-        static const int regepi = getenv("FMC_GEMM_REGEPI") ? atoi(getenv("FMC_GEMM_REGEPI")) : 1;
-        P.regepi = regepi;
-    }
+    P.tap_outer = conv_tap_outer();
+    static const int regepi = fmc_env_int("FMC_GEMM_REGEPI", 1);
+    P.regepi = regepi;
     size_t lds = (size_t)STAGES * (BM + BN) * BK * sizeof(bf16_t) + 1024;
     const size_t slab = (size_t)64 * (BN + 8) * sizeof(float);
     if (slab > lds) lds = slab;
@@ -2467,18 +2467,7 @@ void launch_gemm_g(GemmParams& P, hipStream_t st) {
     constexpr int by_waves = 16 / (WM * WN) > 0 ? 16 / (WM * WN) : 1;
     const int by_lds = (int)(160 * 1024 / (P.sk ? lds : lds_plain));
     const int per_cu = by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : by_waves;
-    // Tile order (lin_to_tile).  Row-major is optimal while the weight matrix fits an XCD's L2 or the c workgroups an
-    // XCD runs at once already span all n-tiles; otherwise make their footprint square in bytes: gm x c/gm tiles with
-    // gm * BM = (c / gm) * BN.  Measured (tools/pmc_tile_order.sh): L2-miss bytes of the level-1 / level-2 GEGLU
-    // projections 810 -> 172 MB and 1015 -> 221 MB per launch, launch time -4 .. -8 %; convs (3-5 n-tiles, k-lockstep
-    // already shares W) only lost L2 hits to grouping, so they keep row-major.
-    if (gemm_group_m_override() > 0) {
-        P.group_m = gemm_group_m_override();
-    } else if (MODE == 0 && (int64_t)P.N * P.K * 2 > (int64_t)5 << 19) {
-        const double c = fmin(32.0 * per_cu, (double)P.tiles_m * P.tiles_n / 8.0);
-        const int gm = (int)lround(sqrt(c * BN / BM));
-        if (gm > 1 && P.tiles_n * 2 > 3 * (c / gm)) P.group_m = gm;
-    }
+    P.group_m = xcd_group_m(P, MODE == 0, 32.0 * per_cu, BN, BM);
     if (P.sk) {
         // persistent grid: exactly the co-resident workgroups, a multiple of 8
         const int64_t iters = (int64_t)P.tiles_m * P.tiles_n * (P.K / BK);
@@ -2493,11 +2482,12 @@ void launch_gemm_g(GemmParams& P, hipStream_t st) {
     }
     if constexpr (STAGES == 2 && MI == 2) {
         if (P.sk) {
-            launch_gemm_k<MODE, EPI, WM, WN, MI, BK, STAGES, true>(P, grid, lds, st);
+            fmc_launch<gemm_kernel<MODE, EPI, WM, WN, MI, BK, STAGES, true>>(dim3(grid), dim3(64 * WM * WN), lds, st, P);
             return;
         }
     }
-    launch_gemm_k<MODE, EPI, WM, WN, MI, BK, STAGES, false>(P, grid, lds_plain, st);
+    // (the LDS size of this instantiation depends on the epilogue variant)
+    fmc_launch<gemm_kernel<MODE, EPI, WM, WN, MI, BK, STAGES, false>>(dim3(grid), dim3(64 * WM * WN), lds_plain, st, P);
     if (P.split_k > 1) {
         const int64_t chunks = P.M * (P.N / 8);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, P);
@@ -2509,29 +2499,12 @@ template <int MODE, int EPI, int PF>
 void launch_gemm8(GemmParams& P, hipStream_t st) {
     P.tiles_m = (int)((P.M + 255) / 256);
     P.tiles_n = (P.N + 255) / 256;
-    P.group_m = 1;
-    static const int tap_outer = getenv("FMC_CONV_TAP_OUTER") ? atoi(getenv("FMC_CONV_TAP_OUTER")) : 0;
-    P.tap_outer = tap_outer;
-    if (gemm_group_m_override() > 0) {
-        P.group_m = gemm_group_m_override();
-    } else if (MODE == 0 && (int64_t)P.N * P.K * 2 > (int64_t)5 << 19) {     // as launch_gemm_g: square per-XCD footprint
-        const double c = fmin(32.0, (double)P.tiles_m * P.tiles_n / 8.0);
-        const int gm = (int)lround(sqrt(c));
-        if (gm > 1 && P.tiles_n * 2 > 3 * (c / gm)) P.group_m = gm;
-    }
+    P.tap_outer = conv_tap_outer();
+    P.group_m = xcd_group_m(P, MODE == 0, 32.0, 1, 1);
     constexpr size_t ring = (size_t)2 * 512 * 64 * sizeof(bf16_t) + 1024;
     constexpr size_t staged = (size_t)256 * ((EPI != 0 ? 128 : 256) + 8) * sizeof(bf16_t);
     constexpr size_t lds = staged > ring ? staged : ring;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8_kernel<MODE, EPI, PF, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8_kernel<MODE, EPI, PF, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8_kernel<MODE, EPI, PF, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
+    constexpr auto plain = gemm8_kernel<MODE, EPI, PF, 0>, sk_main = gemm8_kernel<MODE, EPI, PF, 1>, sk_finish = gemm8_kernel<MODE, EPI, PF, 2>;   // ROLE 0, 1, 2 (see the kernel), named in the order hipcc is to emit them in
     const int tiles = P.tiles_m * P.tiles_n;
     P.sk_t0 = 0;
     if (P.sk && P.sk_hybrid && !P.sk_lock) {
@@ -2547,9 +2520,9 @@ void launch_gemm8(GemmParams& P, hipStream_t st) {
             P.sk_maxseg = maxseg;
             P.sk_whole = 0;
             P.sk_t0 = t0;
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 1>), dim3((unsigned)g), dim3(512), lds, st, P);
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 0>), dim3((unsigned)t0), dim3(512), lds, st, P);
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 2>), dim3((unsigned)rem), dim3(512), lds, st, P);
+            fmc_launch<sk_main>(dim3((unsigned)g), dim3(512), lds, st, P);
+            fmc_launch<plain>(dim3((unsigned)t0), dim3(512), lds, st, P);
+            fmc_launch<sk_finish>(dim3((unsigned)rem), dim3(512), lds, st, P);
             return;
         }
         if (rem == 0) P.sk = 0;                           // whole rounds only: the plain grid (else: fewer tiles than CUs -> full stream-K below)
@@ -2576,9 +2549,9 @@ void launch_gemm8(GemmParams& P, hipStream_t st) {
             P.sk = g;
             P.sk_lock = S;
             P.sk_lock_len = L;
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 1>), dim3((unsigned)g), dim3(512), lds, st, P);
+            fmc_launch<sk_main>(dim3((unsigned)g), dim3(512), lds, st, P);
             if constexpr (EPI == 0) hipLaunchKernelGGL((sk_finish_kernel<MODE>), dim3((unsigned)tiles * 64), dim3(256), 0, st, P);
-            else hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 2>), dim3((unsigned)tiles), dim3(512), lds, st, P);
+            else fmc_launch<sk_finish>(dim3((unsigned)tiles), dim3(512), lds, st, P);
             return;
         }
         P.sk_lock = 0;                                    // too little work / workspace: plain stream-K rules below
@@ -2593,13 +2566,13 @@ void launch_gemm8(GemmParams& P, hipStream_t st) {
             P.sk = g;
             P.sk_maxseg = maxseg;
             P.sk_whole = 0;
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 1>), dim3((unsigned)g), dim3(512), lds, st, P);
-            hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 2>), dim3((unsigned)tiles), dim3(512), lds, st, P);
+            fmc_launch<sk_main>(dim3((unsigned)g), dim3(512), lds, st, P);
+            fmc_launch<sk_finish>(dim3((unsigned)tiles), dim3(512), lds, st, P);
             return;
         }
         P.sk = 0;                                         // too little work (or workspace): the plain grid
     }
-    hipLaunchKernelGGL((gemm8_kernel<MODE, EPI, PF, 0>), dim3((unsigned)tiles), dim3(512), lds, st, P);
+    fmc_launch<plain>(dim3((unsigned)tiles), dim3(512), lds, st, P);
 }
 
 // =====================================================================================================================
@@ -2791,10 +2764,7 @@ __global__ __launch_bounds__(320, (MI * NI == 1 ? 3 : (MI * NI == 2 ? 2 : 1))) v
 }
 
 inline int gemm_k320_cfg() {          // FMC_K320_CFG = 22 (default) | 11 | 21 | 12: (MI, NI) blocks per wave (A/B)
-    static const int v = [] {
-        const char* e = getenv("FMC_K320_CFG");
-        return e ? atoi(e) : 22;
-    }();
+    static const int v = fmc_env_int("FMC_K320_CFG", 22);
     return v;
 }
 bool gemm_k320_ok(const GemmParams& P) {
@@ -2809,14 +2779,8 @@ void launch_gemm_k320_c(GemmParams& P, hipStream_t st) {
     const int per_cu = MI * NI == 1 ? 3 : (MI * NI == 2 ? 2 : 1);
     const int tiles = (int)(P.M / (32 * MI)), slots = fmc_cu_count() * per_cu;
     dim3 grid((unsigned)(tiles < slots ? tiles : slots), (unsigned)(P.N / (160 * NI)));
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_k320_kernel<MI, NI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_k320_kernel<MI, NI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
-    if (P.res) hipLaunchKernelGGL((gemm_k320_kernel<MI, NI, true>), grid, dim3(320), lds, st, P);
-    else hipLaunchKernelGGL((gemm_k320_kernel<MI, NI, false>), grid, dim3(320), lds, st, P);
+    if (P.res) fmc_launch<gemm_k320_kernel<MI, NI, true>>(grid, dim3(320), lds, st, P);
+    else fmc_launch<gemm_k320_kernel<MI, NI, false>>(grid, dim3(320), lds, st, P);
 }
 void launch_gemm_k320(GemmParams& P, hipStream_t st) {
     switch (gemm_k320_cfg()) {
@@ -2835,25 +2799,14 @@ template <int MODE, int EPI>
 void launch_gemm160(GemmParams& P, hipStream_t st) {
     P.tiles_m = (int)((P.M + 159) / 160);
     P.tiles_n = P.N / 320;
-    P.group_m = 1;
     P.tap_outer = 0;
-    if (gemm_group_m_override() > 0) {
-        P.group_m = gemm_group_m_override();
-    } else if (MODE == 0 && (int64_t)P.N * P.K * 2 > (int64_t)5 << 19) {     // as launch_gemm8: square per-XCD footprint in bytes
-        const double c = fmin(32.0, (double)P.tiles_m * P.tiles_n / 8.0);
-        const int gm = (int)lround(sqrt(c * 2.0));
-        if (gm > 1 && P.tiles_n * 2 > 3 * (c / gm)) P.group_m = gm;
-    }
+    P.group_m = xcd_group_m(P, MODE == 0, 32.0, 320, 160);
     constexpr size_t lds = (size_t)5 * (160 + 320) * 32 * sizeof(bf16_t) + 1024;          // five sub-tile buffers + the dummies' KiB
     static_assert(lds >= (size_t)160 * 328 * 2 && lds >= (size_t)160 * 164 * 4, "epilogue staging fits the operand buffers");
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160_kernel<MODE, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
+    constexpr auto plain = gemm160_kernel<MODE, EPI>;
     if (P.split_k > 1) {
         if constexpr (EPI == 0) {
-            hipLaunchKernelGGL((gemm160_kernel<MODE, 0>), dim3((unsigned)(P.tiles_m * P.tiles_n * P.split_k)), dim3(512), lds, st, P);
+            fmc_launch<plain>(dim3((unsigned)(P.tiles_m * P.tiles_n * P.split_k)), dim3(512), lds, st, P);
             const int64_t chunks = P.M * (P.N / 8);
             hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, P);
         }
@@ -2861,64 +2814,33 @@ void launch_gemm160(GemmParams& P, hipStream_t st) {
     }
     if constexpr (MODE == 0) {
         // more tiles than CUs on a token projection: the persistent form (the next tile's operands stream in under this tile's epilogue)
-        static const int persist = getenv("FMC_G160_PERSIST") ? atoi(getenv("FMC_G160_PERSIST")) : 1;
+        const int persist = g160_persist();
         const int cus = fmc_cu_count() & ~7;
         // (FMC_G160_PERSIST=2: also launches of exactly one round -- tiles == CUs, the level-1 N = 640 projections -- A/B switch)
         // (a tile-major A operand exists in the persistent form only: it also takes launches of exactly one round -- the two halves of a split feed-forward)
         if (persist && !P.f32io && P.M % 160 == 0 && ((persist == 2 || P.a_blocked || P.bias_img) ? P.tiles_m * P.tiles_n >= cus : P.tiles_m * P.tiles_n > cus) && cus >= 8) {
             constexpr size_t ldsp = (size_t)3 * (160 + 320) * 32 * sizeof(bf16_t) + 1024 + (EPI == 1 ? (size_t)160 * 168 * 2 + 4096 : (size_t)80 * 328 * 2 + 5120);
-            static FmcPerDeviceFlag raisedp;
-            if (!raisedp) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<EPI, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<EPI, 5, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                if constexpr (EPI == 0) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<0, 5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<0, 5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                }
-                raisedp = true;
-            }
+            // which form <EPI, 5, LN, LNC, A2, IMG> (linear_impl has checked what each one needs); the plain epilogue (EPI 0) has them all:
+            //   4 | 5: per-image weights / fp32 bias rows, without | with the LayerNorm statistics   6: two-segment reduction (tile-major first segment)
+            //   1: this GEMM applies the LayerNorm of its input rows   2: LayerNorm output (N == 320, no GroupNorm partials)   3: LayerNorm statistics
+            // (the launches below stand in the order hipcc is to emit the instantiations in, kept as it was: see fmc_launch)
+            const bool e0 = EPI == 0;
+            const int form = e0 && P.bias_img ? (P.ln_stats ? 5 : 4) : e0 && P.a2 ? 6 : P.lnc_stats ? 1 : e0 && P.ln_out ? 2 : e0 && P.ln_stats ? 3 : 0;
+            const dim3 grid((unsigned)cus), block(512);
+            if (form == 0) fmc_launch<gemm160p_kernel<EPI, 5>>(grid, block, ldsp, st, P);
+            else if (form == 1) fmc_launch<gemm160p_kernel<EPI, 5, 0, 1>>(grid, block, ldsp, st, P);
             if constexpr (EPI == 0) {
-                if (P.bias_img) {                             // per-image weights / fp32 bias rows (linear_impl has checked; with or without the LayerNorm statistics)
-                    static FmcPerDeviceFlag raised3;
-                    if (!raised3) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<0, 5, 0, 0, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<0, 5, 2, 0, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                        raised3 = true;
-                    }
-                    if (P.ln_stats) hipLaunchKernelGGL((gemm160p_kernel<0, 5, 2, 0, 0, 1>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                    else hipLaunchKernelGGL((gemm160p_kernel<0, 5, 0, 0, 0, 1>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                    return;
-                }
-                if (P.a2) {                                   // two-segment reduction (linear_impl has checked: tile-major first segment, plain epilogue)
-                    static FmcPerDeviceFlag raised2;
-                    if (!raised2) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<0, 5, 0, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                        raised2 = true;
-                    }
-                    hipLaunchKernelGGL((gemm160p_kernel<0, 5, 0, 0, 1>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                    return;
-                }
+                if (form == 2) fmc_launch<gemm160p_kernel<0, 5, 1>>(grid, block, ldsp, st, P);
+                else if (form == 3) fmc_launch<gemm160p_kernel<0, 5, 2>>(grid, block, ldsp, st, P);
+                else if (form == 4) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 1>>(grid, block, ldsp, st, P);
+                else if (form == 5) fmc_launch<gemm160p_kernel<0, 5, 2, 0, 0, 1>>(grid, block, ldsp, st, P);
+                else if (form == 6) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1>>(grid, block, ldsp, st, P);
             }
-            if (P.lnc_stats) {                                // this GEMM applies the LayerNorm of its input rows (linear_impl has checked the rest)
-                hipLaunchKernelGGL((gemm160p_kernel<EPI, 5, 0, 1>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                return;
-            }
-            if constexpr (EPI == 0) {
-                if (P.ln_out) {                               // (linear_impl has checked N == 320 and no GroupNorm partials)
-                    hipLaunchKernelGGL((gemm160p_kernel<0, 5, 1>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                    return;
-                }
-                if (P.ln_stats) {
-                    hipLaunchKernelGGL((gemm160p_kernel<0, 5, 2>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL((gemm160p_kernel<EPI, 5>), dim3((unsigned)cus), dim3(512), ldsp, st, P);
             return;
         }
     }
     // (not reached with ln_out / ln_stats / lnc_stats set: linear_impl checks the persistent form's conditions)
-    hipLaunchKernelGGL((gemm160_kernel<MODE, EPI>), dim3((unsigned)(P.tiles_m * P.tiles_n)), dim3(512), lds, st, P);
+    fmc_launch<plain>(dim3((unsigned)(P.tiles_m * P.tiles_n)), dim3(512), lds, st, P);
 }
 
 // tile 17: 256 x 320 tiles, persistent, GEGLU epilogue only (the feed-forward input projections: M % 256 == 0, more tiles than CUs)
@@ -2929,23 +2851,11 @@ bool gemm256p_ok(const GemmParams& P) {
 void launch_gemm256p(GemmParams& P, hipStream_t st) {
     P.tiles_m = (int)(P.M / 256);
     P.tiles_n = P.N / 320;
-    P.group_m = 1;
     P.tap_outer = 0;
-    if (gemm_group_m_override() > 0) {
-        P.group_m = gemm_group_m_override();
-    } else if ((int64_t)P.N * P.K * 2 > (int64_t)5 << 19) {                   // as launch_gemm160: square per-XCD footprint in bytes
-        const double c = fmin(32.0, (double)P.tiles_m * P.tiles_n / 8.0);
-        const int gm = (int)lround(sqrt(c * 1.25));
-        if (gm > 1 && P.tiles_n * 2 > 3 * (c / gm)) P.group_m = gm;
-    }
+    P.group_m = xcd_group_m(P, true, 32.0, 320, 256);
     constexpr size_t ldsp = (size_t)3 * (256 + 320) * 32 * sizeof(bf16_t) + 1024 + (size_t)128 * 168 * 2;
     static_assert(ldsp <= 160 * 1024, "ring + staging fit the LDS");
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm160p_kernel<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-        raised = true;
-    }
-    hipLaunchKernelGGL((gemm160p_kernel<1, 8>), dim3((unsigned)(fmc_cu_count() & ~7)), dim3(512), ldsp, st, P);
+    fmc_launch<gemm160p_kernel<1, 8>>(dim3((unsigned)(fmc_cu_count() & ~7)), dim3(512), ldsp, st, P);
 }
 
 bool gemm8_ok(GemmParams& P) {
@@ -3084,7 +2994,7 @@ static int linear_impl(const void* x, const void* w, const void* bias, const voi
         if (f32io || tile != 16 || split_k != 1 || gn_partials || ln_out || ln_stats || x2 || bias || residual || residual2 || alpha != 1.f || N % 320 ||
             M % 160 || (M / 160) * (N / 320) <= cus || cus < 8 || !lnc_c || !lnc_bias || !fmc_aligned16(lnc_c) || !fmc_aligned16(lnc_bias) ||
             ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31) ||
-            (getenv("FMC_G160_PERSIST") && atoi(getenv("FMC_G160_PERSIST")) == 0))
+            g160_persist() == 0)
             FMC_FAIL(FMC_E_SHAPE, "linear_bf16_lnc: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, more tiles than CUs, no bf16 bias / "
                                   "residual, alpha 1)");
     }
@@ -3098,7 +3008,7 @@ static int linear_impl(const void* x, const void* w, const void* bias, const voi
             (a_blocked && (M / 160) * (N / 320) < cus) ||
             (a_blocked && (epilogue != 0 || ldx != (x2 ? k_split : K) || K % 32)) ||
             (x2 && (ln_out || ln_stats || lnc_stats || ((M - 1) * ldx2 + (K - k_split)) * 2 >= ((int64_t)1 << 31))) || (out_blocked && (epilogue != 1 || ldo != N / 2 || (N / 2) % 32)) ||
-            (int64_t)M * (a_blocked ? K : N / 2) * 2 >= ((int64_t)1 << 31) || (getenv("FMC_G160_PERSIST") && atoi(getenv("FMC_G160_PERSIST")) == 0))
+            (int64_t)M * (a_blocked ? K : N / 2) * 2 >= ((int64_t)1 << 31) || g160_persist() == 0)
             FMC_FAIL(FMC_E_SHAPE, "linear_bf16: the tile-major feed-forward intermediate needs tile 16's persistent form (M %% 160 == 0, N %% 320 == 0, "
                                   "more tiles than CUs, dense rows)");
     }
@@ -3109,7 +3019,7 @@ static int linear_impl(const void* x, const void* w, const void* bias, const voi
         if (f32io || epilogue != 0 || tile != 16 || split_k != 1 || gn_partials || x2 || bias || residual || residual2 || alpha != 1.f || ln_out || lnc_stats ||
             a_blocked || out_blocked || N % 320 || M % 160 || (M / 160) * (N / 320) < cus || cus < 8 || img_rows < 160 || img_rows % 160 || M % img_rows ||
             ((uintptr_t)bias_img & 15) || ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (M / img_rows) * (int64_t)N * K * 2 >= ((int64_t)1 << 31) ||
-            (getenv("FMC_G160_PERSIST") && atoi(getenv("FMC_G160_PERSIST")) == 0))
+            g160_persist() == 0)
             FMC_FAIL(FMC_E_SHAPE, "linear_bf16_imgw: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, at least as many tiles as CUs, images of a multiple "
                                   "of 160 rows, no bf16 bias / residual, all weights < 2 GiB)");
         P.bias_img = bias_img; P.w_img_stride = (int64_t)N * K; P.img_rows = img_rows;
@@ -3119,7 +3029,7 @@ static int linear_impl(const void* x, const void* w, const void* bias, const voi
         if ((ln_out != nullptr) == (ln_stats != nullptr)) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: exactly one of ln_out / ln_stats");
         if (f32io || epilogue != 0 || tile != 16 || split_k != 1 || gn_partials || x2 || N != 320 || M % 160 || (bias_img ? M / 160 < cus : M / 160 <= cus) || cus < 8 ||
             (ln_out && (!ln_gamma || !ln_beta || !fmc_aligned16(ln_out))) || (ln_stats && ((uintptr_t)ln_stats & 7)) || (ln_pe && (ln_pe_inner <= 0 || ln_pe_inner % 160 || ln_pe_frames <= 0)) ||
-            ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (getenv("FMC_G160_PERSIST") && atoi(getenv("FMC_G160_PERSIST")) == 0))
+            ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || g160_persist() == 0)
             FMC_FAIL(FMC_E_SHAPE, "linear_bf16_ln: the LayerNorm output comes out of tile 16's persistent form only (bf16, N == 320, M %% 160 == 0, "
                                   "M / 160 > CUs, plain epilogue, positional-encoding frames of a multiple of 160 rows)");
     }

@@ -242,12 +242,7 @@ extern "C" int fmc_linear_wgrad_bf16(const fmc_wgrad_problem* problems, int n_pr
     }
     if (wgs >= ((int64_t)1 << 31) || red >= ((int64_t)1 << 31)) FMC_FAIL(FMC_E_SHAPE, "linear_wgrad_bf16: launch too large");
     hipStream_t st = (hipStream_t)stream;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS);
-        raised = true;
-    }
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)wgs), dim3(256), WG_LDS, st, P);
+    fmc_launch<wgrad_kernel>(dim3((unsigned)wgs), dim3(256), WG_LDS, st, P);
     FMC_CHECK_LAUNCH("fmc_linear_wgrad_bf16");
     if (red > 0) {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(red / 256)), dim3(256), 0, st, P);

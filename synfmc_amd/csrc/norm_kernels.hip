@@ -852,7 +852,7 @@ static void launch_ln_g(const void* x, void* y, const float* gamma, const float*
 template <typename T>
 static bool try_launch_ln16(const void* x, void* y, const float* gamma, const float* beta, const float* pe, int64_t M, int C,
                             float eps, int pe_inner, int pe_frames, hipStream_t st, const void* addend = nullptr, void* sum_out = nullptr) {
-    static const int force_u = getenv("FMC_LN_U") ? atoi(getenv("FMC_LN_U")) : 0;      // A/B switch: 1 / 2 rows per lane group whatever M
+    static const int force_u = fmc_env_int("FMC_LN_U", 0);     // A/B switch: 1 / 2 rows per lane group whatever M
     // (one row per lane group everywhere: two measured 7-35 % slower at every FMC shape, also at M = 81920 -- tools/scratch/r04/probe_ln.py)
     const bool many = force_u == 2;
     switch (C) {

@@ -1060,10 +1060,7 @@ __global__ __launch_bounds__(512, 1) void xattn40_kernel(const SAParams P, const
 }
 
 inline int sa_xattn_env() {           // FMC_SA_XATTN=0: the block-by-block kernel for the text cross-attention too (A/B)
-    static const int v = [] {
-        const char* e = getenv("FMC_SA_XATTN");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = fmc_env_int("FMC_SA_XATTN", 1);
     return v;
 }
 inline bool xattn40_ok(const SAParams& P) {
@@ -1071,22 +1068,11 @@ inline bool xattn40_ok(const SAParams& P) {
 }
 inline void launch_xattn40(const SAParams& P, hipStream_t st) {
     const int nkvb = P.B / P.kv_batch_div, nq32 = P.Sq / 32, units = P.kv_batch_div * nq32;
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
-    int per = cus / nkvb;
+    int per = fmc_cu_count() / nkvb;                     // (per device; with the one in fmc_launch, two hipGetDevice per call)
     if (per < 1) per = 1;
     if (per > units) per = units;
     const size_t lds = (size_t)8 * 96 * XA_VP * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn40_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
-    hipLaunchKernelGGL(xattn40_kernel, dim3((unsigned)(per * nkvb)), dim3(512), lds, st, P, nq32, units, nkvb);
+    fmc_launch<xattn40_kernel>(dim3((unsigned)(per * nkvb)), dim3(512), lds, st, P, nq32, units, nkvb);
 }
 
 // =====================================================================================================================
@@ -1409,48 +1395,28 @@ __global__ __launch_bounds__(512, 1) void sa_big80_kernel_w8(const SAParams P) {
 __global__ __launch_bounds__(320, 3) void sa_big80_kernel_w5(const SAParams P) { sa_big80_body<5>(P); }
 
 inline bool sa_big80_ok(const SAParams& P) {     // FMC_SA_BIG80=0: the tiled kernel at the 20x32 level too (A/B)
-    static const bool on = [] {
-        const char* e = getenv("FMC_SA_BIG80");
-        return !e || atoi(e) != 0;
-    }();
+    static const bool on = fmc_env_int("FMC_SA_BIG80", 1) != 0;
     return on && P.D == 80 && P.Skv % 32 == 0 && P.Skv >= 256 && P.Sq >= 160;
 }
 inline void launch_sa_big80(const SAParams& Pin, hipStream_t st) {
     SAParams P = Pin;
-    static const int nw = [] { const char* e = getenv("FMC_SA_BIG80_WAVES"); const int v = e ? atoi(e) : 10; return v == 8 || v == 5 ? v : 10; }();
+    static const int nw = [] { const int v = fmc_env_int("FMC_SA_BIG80_WAVES", 10); return v == 8 || v == 5 ? v : 10; }();
     P.nqblk = (P.Sq + 32 * nw - 1) / (32 * nw);
     if (P.xcd_remap != 2) P.xcd_remap = 0;
     const size_t lds = (size_t)(nw == 5 ? 160 : 320) * (5 * 16 + 8 + sa_vr_pitch<3>()) * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sa_big80_kernel_w10), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sa_big80_kernel_w8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sa_big80_kernel_w5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
-    if (nw == 5) hipLaunchKernelGGL(sa_big80_kernel_w5, dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(320), lds, st, P);
-    else if (nw == 8) hipLaunchKernelGGL(sa_big80_kernel_w8, dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(512), lds, st, P);
-    else hipLaunchKernelGGL(sa_big80_kernel_w10, dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(640), lds, st, P);
+    if (nw == 5) fmc_launch<sa_big80_kernel_w5>(dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(320), lds, st, P);
+    else if (nw == 8) fmc_launch<sa_big80_kernel_w8>(dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(512), lds, st, P);
+    else fmc_launch<sa_big80_kernel_w10>(dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(640), lds, st, P);
 }
 
 inline bool sa_small_ok(const SAParams& P) {     // FMC_SA_SMALL=0: the tiled kernel at the inner levels too (A/B)
-    static const bool on = [] {
-        const char* e = getenv("FMC_SA_SMALL");
-        return !e || atoi(e) != 0;
-    }();
+    static const bool on = fmc_env_int("FMC_SA_SMALL", 1) != 0;
     return on && P.D == 160 && P.Skv <= 160;
 }
 template <int NB>
 void launch_sa_small_nb(const SAParams& P, hipStream_t st) {
     const size_t lds = (size_t)NB * 32 * (10 * 16 + 8 + sa_vr_pitch<5>()) * 2;
-    if (lds > 64 * 1024) {
-        static FmcPerDeviceFlag raised;
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sa_small160_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((sa_small160_kernel<NB>), dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(320), lds, st, P);
+    fmc_launch<sa_small160_kernel<NB>>(dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(320), lds, st, P);
 }
 inline void launch_sa_small(const SAParams& Pin, hipStream_t st) {
     SAParams P = Pin;
@@ -1460,10 +1426,7 @@ inline void launch_sa_small(const SAParams& Pin, hipStream_t st) {
 }
 
 inline int sa_pipe_env() {            // FMC_SA_PIPE=0: the block-by-block kernel at d = 40 too (A/B); 4: persistent workgroups
-    static const int v = [] {
-        const char* e = getenv("FMC_SA_PIPE");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = fmc_env_int("FMC_SA_PIPE", 1);
     return v;
 }
 inline bool sa40_ok(const SAParams& P) {
@@ -1479,12 +1442,7 @@ inline void launch_sa40(const SAParams& Pin, hipStream_t st) {
     // list instead -- measured 4 % slower for that reason.
     int grid = nitems;
     if (sa_pipe_env() == 4) {
-        static const int resident = [] {
-            int dev = 0, cus = 256;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            return 2 * cus;
-        }();
+        const int resident = 2 * fmc_cu_count();
         if (nitems > resident) grid = resident;
     }
     hipLaunchKernelGGL(sa40d_kernel, dim3((unsigned)grid), dim3(256), D40_LDS, st, P, nitems);
@@ -1497,47 +1455,27 @@ void launch_sa_v(const SAParams& Pin, hipStream_t st) {
     constexpr int NDT = (NKS + 1) / 2;
     const size_t lds = sizeof(T) * ((size_t)SA_BK * (NKS * 16 + 8) + (VR ? (size_t)SA_BK * sa_vr_pitch<NDT>() : (size_t)NDT * 32 * (SA_BK + 4)));
     dim3 grid((unsigned)(P.B * P.H * P.nqblk)), block(64 * SA_WAVES);
-    if (lds > 64 * 1024) {  // gfx950 has 160 KiB of LDS per CU; opting in is needed above 64 KiB
-        static FmcPerDeviceFlag raised;
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_attn_kernel<T, NKS, SHORT_KV, PF, NQ, MK, VR>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((spatial_attn_kernel<T, NKS, SHORT_KV, PF, NQ, MK, VR>), grid, block, lds, st, P);
+    fmc_launch<spatial_attn_kernel<T, NKS, SHORT_KV, PF, NQ, MK, VR>>(grid, block, lds, st, P);   // (gfx950 has 160 KiB of LDS per CU; above 64 KiB it is opt-in)
 }
 
 // FMC_SA_PREFETCH=0/1 overrides the default policy (experiments only)
 inline int sa_prefetch_env() {
-    static const int v = [] {
-        const char* e = getenv("FMC_SA_PREFETCH");
-        return e ? atoi(e) : -1;
-    }();
+    static const int v = fmc_env_int("FMC_SA_PREFETCH", -1);
     return v;
 }
 
 inline int sa_nq_env() {              // FMC_SA_NQ = 1 | 2 query blocks per wave for d <= 48 (default 2)
-    static const int v = [] {
-        const char* e = getenv("FMC_SA_NQ");
-        return e ? atoi(e) : 2;
-    }();
+    static const int v = fmc_env_int("FMC_SA_NQ", 2);
     return v;
 }
 
 inline int sa_vr_env() {              // FMC_SA_VR=0: V transposed while staging instead of by the transpose read (A/B)
-    static const int v = [] {
-        const char* e = getenv("FMC_SA_VR");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = fmc_env_int("FMC_SA_VR", 1);
     return v;
 }
 
 inline int sa_mk_env() {              // FMC_SA_MK=0: softmax reference through the accumulator instead of the QK^T reduction
-    static const int v = [] {               // (the reduction form frees 33 VGPRs: -2 % on top of the transpose-read V path)
-        const char* e = getenv("FMC_SA_MK");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = fmc_env_int("FMC_SA_MK", 1);
     return v;
 }
 
@@ -1620,10 +1558,8 @@ extern "C" int fmc_spatial_attn_fwd(const void* q, const void* k, const void* v,
     P.scale_log2 = scale * LOG2E;
     P.nqblk = (Sq + SA_BQ - 1) / SA_BQ;
     P.xcd_remap = (B % 8 == 0) ? 2 : ((B * H) % 8 == 0) ? 1 : 0;
-    if (const char* e = getenv("FMC_SA_XCD")) {          // A/B switch: 0 = plain order, 1 = (batch, head) per XCD
-        const int want = atoi(e);
-        if (want == 0 || (want == 1 && (B * H) % 8 == 0)) P.xcd_remap = want;
-    }
+    static const int want = fmc_env_int("FMC_SA_XCD", -1);   // A/B switch: 0 = plain order, 1 = (batch, head) per XCD
+    if (want == 0 || (want == 1 && (B * H) % 8 == 0)) P.xcd_remap = want;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == FMC_BF16 && xattn40_ok(P)) {
         launch_xattn40(P, st);

@@ -15,7 +15,7 @@
 // S is recomputed in both 2 and 3 (7 matrix products instead of 5) in exchange for atomic-free, deterministic grads.
 // Algorithmic flops per backward = 14 * B*H*Sq*Skv*D (2.5x + 1 recompute of the forward's 4).
 #include "attn_common.h"
-#include <cstdlib>
+#include <climits>
 
 namespace {
 
@@ -322,12 +322,9 @@ __global__ __launch_bounds__(64 * WAVES) void attn_dkdv_kernel(const SABwdParams
     }
 }
 
-template <typename K>
-void raise_lds(K kernel, size_t lds, FmcPerDeviceFlag& raised) {
-    if (lds > 64 * 1024 && !raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        raised = true;
-    }
+inline bool sab_xcd0() {              // FMC_SAB_XCD0 (set to anything): plain workgroup order instead of one (batch, head) group per XCD (A/B)
+    static const int v = fmc_env_int("FMC_SAB_XCD0", INT_MIN);   // presence only: the default stands for "unset"
+    return v != INT_MIN;
 }
 
 template <typename T, int NKS>
@@ -344,22 +341,18 @@ void launch_bwd(SABwdParams P, hipStream_t st) {
     }
     {
         const size_t lds = sizeof(T) * ((size_t)2 * BK2 * KP + (size_t)NDT * 32 * VP);
-        static FmcPerDeviceFlag raised;
-        raise_lds(&attn_dq_kernel<T, NKS>, lds, raised);
         P.nblk = (P.Sq + 127) / 128;
-        P.xcd = (P.B % 8 == 0 && !getenv("FMC_SAB_XCD0")) ? 1 : 0;
-        hipLaunchKernelGGL((attn_dq_kernel<T, NKS>), dim3((unsigned)(P.B * P.H * P.nblk)), dim3(256), lds, st, P);
+        P.xcd = (P.B % 8 == 0 && !sab_xcd0()) ? 1 : 0;
+        fmc_launch<attn_dq_kernel<T, NKS>>(dim3((unsigned)(P.B * P.H * P.nblk)), dim3(256), lds, st, P);
     }
     if (P.dk) {                                       // dk == dv == NULL: the key/value side needs no gradient
         constexpr int BKV = 32 * WAVES;
         const size_t lds = sizeof(T) * ((size_t)2 * BKV * KP + (size_t)2 * BQ * KP + (size_t)2 * NDT * 32 * (BQ + 4)) +
                            2 * BQ * sizeof(float);
-        static FmcPerDeviceFlag raised;
-        raise_lds(&attn_dkdv_kernel<T, NKS, WAVES, BQ>, lds, raised);
         P.nblk = (P.Skv + BKV - 1) / BKV;
         const int bkv = P.B / P.kv_batch_div;
-        P.xcd = (bkv % 8 == 0 && !getenv("FMC_SAB_XCD0")) ? 1 : 0;
-        hipLaunchKernelGGL((attn_dkdv_kernel<T, NKS, WAVES, BQ>), dim3((unsigned)(bkv * P.H * P.nblk)), dim3(64 * WAVES), lds, st, P);
+        P.xcd = (bkv % 8 == 0 && !sab_xcd0()) ? 1 : 0;
+        fmc_launch<attn_dkdv_kernel<T, NKS, WAVES, BQ>>(dim3((unsigned)(bkv * P.H * P.nblk)), dim3(64 * WAVES), lds, st, P);
     }
 }
 

@@ -740,17 +740,10 @@ template <typename T, int FT, int NK32, bool PART>
 void launch_ta_bwd(const TABwdParams& P, hipStream_t st) {
     const int CW = P.GH * P.D;
     const size_t lds = sizeof(T) * 7 * (size_t)(FT * 16) * (CW + 8);
-    if (lds > 64 * 1024) {
-        static FmcPerDeviceFlag raised;
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_bwd_kernel<T, FT, NK32, PART>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            raised = true;
-        }
-    }
     const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
     dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    hipLaunchKernelGGL((temporal_attn_bwd_kernel<T, FT, NK32, PART>), grid, block, lds, st, P);
+    // (lds grows with GH * D: the eager warm-up before a graph capture has to cover the largest shape, as for the ring GEMMs)
+    fmc_launch<temporal_attn_bwd_kernel<T, FT, NK32, PART>>(grid, block, lds, st, P);
 }
 
 template <typename T, int FT, bool PART>
@@ -781,15 +774,7 @@ void launch_ta(const TAParams& P, hipStream_t st) {
     dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH)));
     auto go = [&](auto nw) {                                          // the waves of a workgroup split the unit's heads
         constexpr int NW = decltype(nw)::value;
-        if (lds > 64 * 1024) {
-            static FmcPerDeviceFlag raised;
-            if (!raised) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_kernel<T, FT, NK32, NW, PART>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                raised = true;
-            }
-        }
-        hipLaunchKernelGGL((temporal_attn_kernel<T, FT, NK32, NW, PART>), grid, dim3(64 * NW), lds, st, P);
+        fmc_launch<temporal_attn_kernel<T, FT, NK32, NW, PART>>(grid, dim3(64 * NW), lds, st, P);
     };
     if (P.GH >= 4) go(std::integral_constant<int, 4>{});
     else if (P.GH >= 2) go(std::integral_constant<int, 2>{});
@@ -900,17 +885,9 @@ template <int FT, int NK32, bool PART>
 void launch_ta8(const TA8Params& P, hipStream_t st) {
     const int CW = P.GH * P.D;
     const size_t lds = 3 * (size_t)(FT * 16) * (CW + 16) + sizeof(bf16_t) * (size_t)(FT * 16) * (CW + 8);
-    if (lds > 64 * 1024) {
-        static FmcPerDeviceFlag raised;
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_fp8_kernel<FT, NK32, PART>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            raised = true;
-        }
-    }
     const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
     dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    hipLaunchKernelGGL((temporal_attn_fp8_kernel<FT, NK32, PART>), grid, block, lds, st, P);
+    fmc_launch<temporal_attn_fp8_kernel<FT, NK32, PART>>(grid, block, lds, st, P);
 }
 template <int FT, bool PART>
 int dispatch_ta8(const TA8Params& P, hipStream_t st) {

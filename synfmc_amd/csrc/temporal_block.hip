@@ -751,14 +751,9 @@ extern "C" int fmc_xattn_block320_bf16(const void* h, void* out, const float* ln
     P.dbg_times = nullptr;
     const int cus = fmc_cu_count();
     const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        raised = true;
-    }
-    if (ln_stats) hipLaunchKernelGGL((temporal_block_kernel<false, true, true>), dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL((temporal_block_kernel<false, false, true>), dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+    // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
+    if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+    else fmc_launch<temporal_block_kernel<false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_xattn_block320_bf16");
     return 0;
 }
@@ -809,20 +804,12 @@ extern "C" int fmc_temporal_block_bf16(const void* h, void* out, const float* ln
     const int cus = fmc_cu_count();
     const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
     hipStream_t st = (hipStream_t)stream;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        raised = true;
-    }
-    if (w_merge_tm) {
-        if (ln_stats) hipLaunchKernelGGL((temporal_block_kernel<true, true>), dim3(grid), dim3(512), TB_LDS, st, P);
-        else hipLaunchKernelGGL((temporal_block_kernel<true, false>), dim3(grid), dim3(512), TB_LDS, st, P);
+    if (w_merge_tm) {                                  // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
+        if (!ln_stats) fmc_launch<temporal_block_kernel<true, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        else fmc_launch<temporal_block_kernel<true, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
     } else {
-        if (ln_stats) hipLaunchKernelGGL((temporal_block_kernel<false, true>), dim3(grid), dim3(512), TB_LDS, st, P);
-        else hipLaunchKernelGGL((temporal_block_kernel<false, false>), dim3(grid), dim3(512), TB_LDS, st, P);
+        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        else fmc_launch<temporal_block_kernel<false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
     }
     FMC_CHECK_LAUNCH("fmc_temporal_block_bf16");
     return 0;

@@ -840,14 +840,8 @@ int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma
     P.total_rows = (int64_t)n_clips * T6_F * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
     const unsigned grid = (unsigned)(n_clips * P.tpc);
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block640_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, T6_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block640_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, T6_LDS);
-        raised = true;
-    }
-    if (w_merge_frag) hipLaunchKernelGGL((temporal_block640_kernel<true, false>), dim3(grid), dim3(512), T6_LDS, st, P);
-    else hipLaunchKernelGGL((temporal_block640_kernel<false, false>), dim3(grid), dim3(512), T6_LDS, st, P);
+    if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
+    else fmc_launch<temporal_block640_kernel<false, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
     FMC_CHECK_LAUNCH("fmc_temporal_block_bf16 (C = 640)");
     return 0;
 }
@@ -875,12 +869,7 @@ extern "C" int fmc_xattn_block640_bf16(const void* h, void* out, const float* ln
     P.total_rows = (int64_t)n_images * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
     const unsigned grid = (unsigned)(P.total_rows / T6_ROWS);
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_block640_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, T6_LDS);
-        raised = true;
-    }
-    hipLaunchKernelGGL((temporal_block640_kernel<false, true>), dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
+    fmc_launch<temporal_block640_kernel<false, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_xattn_block640_bf16");
     return 0;
 }
@@ -908,12 +897,7 @@ extern "C" int fmc_geglu640_ln_bf16(const void* h, void* out, const float* ln_ga
     G6Params P{};
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
     P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_direct_kernel<640>), hipFuncAttributeMaxDynamicSharedMemorySize, T6_LDS);
-        raised = true;
-    }
-    hipLaunchKernelGGL(geglu_direct_kernel<640>, dim3((unsigned)(M / 80)), dim3(512), T6_LDS, (hipStream_t)stream, P);
+    fmc_launch<geglu_direct_kernel<640>>(dim3((unsigned)(M / 80)), dim3(512), T6_LDS, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_geglu640_ln_bf16");
     return 0;
 }
@@ -932,20 +916,14 @@ extern "C" int fmc_geglu320_ln_bf16(const void* h, void* out, const float* ln_ga
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
     P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
     constexpr int lds = (80 * 320 + 80 * 168) * 2;
-    static FmcPerDeviceFlag raised;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_direct_kernel<320>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_direct_kernel<320, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&geglu_direct_kernel<320, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds);
-        raised = true;
-    }
     // FMC_GEGLU320_ROWS160: 0 = 80-row workgroups of 4 waves, two per CU; 1 = 160 rows on 8 waves (round 5 A/B: 215 - 225 us either way on 81920 x 2560 x 320,
     // gpurun_out/r05n/geglu_ab.txt -- pairing the halves in one workgroup leaves every wave's fragment loads in place); 2 = 160 rows on 4 waves, each weight
     // fragment used for both halves (SEQ, round 6)
-    static const int rows160 = [] { const char* e = getenv("FMC_GEGLU320_ROWS160"); return e ? atoi(e) : FMC_GEGLU320_ROWS160_DEFAULT; }();
-    if (rows160 == 2 && M % 160 == 0) hipLaunchKernelGGL((geglu_direct_kernel<320, 2, true>), dim3((unsigned)(M / 160)), dim3(256), 2 * lds, (hipStream_t)stream, P);
-    else if (rows160 == 1 && M % 160 == 0) hipLaunchKernelGGL((geglu_direct_kernel<320, 2>), dim3((unsigned)(M / 160)), dim3(512), 2 * lds, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL(geglu_direct_kernel<320>, dim3((unsigned)(M / 80)), dim3(256), lds, (hipStream_t)stream, P);
+    static const int rows160 = fmc_env_int("FMC_GEGLU320_ROWS160", FMC_GEGLU320_ROWS160_DEFAULT);
+    const int rows = M % 160 == 0 ? rows160 : 0;       // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
+    if (rows != 1 && rows != 2) fmc_launch<geglu_direct_kernel<320>>(dim3((unsigned)(M / 80)), dim3(256), lds, (hipStream_t)stream, P);
+    else if (rows == 1) fmc_launch<geglu_direct_kernel<320, 2>>(dim3((unsigned)(M / 160)), dim3(512), 2 * lds, (hipStream_t)stream, P);
+    else fmc_launch<geglu_direct_kernel<320, 2, true>>(dim3((unsigned)(M / 160)), dim3(256), 2 * lds, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_geglu320_ln_bf16");
     return 0;
 }

@@ -7,7 +7,11 @@ Tolerances (rel-inf = max|a-b| / max|b|):
     difference is the bf16 rounding of the output (2^-8 relative per element) plus, for attention, the bf16
     rounding of the probabilities: 1e-2.
 """
+import json
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -598,6 +602,20 @@ def test_linear_second_residual(K, tile):
     assert rel_inf(got.float(), want) < 1e-2
     with pytest.raises((ValueError, AssertionError)):
         K.linear_bf16(hd, wd, bd, None, s_, residual2=r2d)                      # a second residual needs the first
+
+
+def test_launch_lds_grows_for_one_instantiation(K):
+    """One instantiation of the ring kernel, two dynamic-LDS sizes, in one fresh process: tile 6 (256 x 256 tiles, 32-deep k-tiles) runs
+    with 67,584 B when a second residual keeps the epilogue on the fp32 slab, and with 135,168 B when it stages the whole bf16 tile.
+    The launch helper must raise the attribute a second time for the larger size -- a "raised" flag fails the second launch (an error
+    status, no fault).  Bound: the one of the other linear_bf16 tests (bf16 rounding of the output)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tests", "launch_child.py"), root, "0:6:256:256:64:1", "0:6:256:256:64:0"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    errs = json.loads(out.stdout.splitlines()[-1])
+    print("rel-inf, 67,584 B then 135,168 B:", errs)
+    assert len(errs) == 2 and all(e < 1e-2 for e in errs), errs
 
 
 @pytest.mark.parametrize("tile", [0, 1, 3, 5, 7, 11])

@@ -93,3 +93,15 @@ def test_grad_allreducer_over_rccl(tmp_path):
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("[")][-1])
     assert all(s["bit_equal_across_ranks"] and s["err"] < 1e-5 and s["n_unused"] == 2 and s["unused_none"] for s in res), res
+
+
+def test_launch_lds_raised_on_second_device():
+    """The dynamic-LDS attribute is raised per DEVICE: in one fresh process the 256 x 256 ring kernel with 64-deep k-tiles (tile 3,
+    129 KiB and more of LDS) runs on cuda:0, then on cuda:1, each result checked on its own device against F.linear in fp32."""
+    _need_two_gpus()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "launch_child.py"), ROOT, "0:3:256:256:128:0", "1:3:256:256:128:0"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    errs = json.loads(out.stdout.splitlines()[-1])
+    print("rel-inf on cuda:0, cuda:1:", errs)
+    assert len(errs) == 2 and all(e < 1e-2 for e in errs), errs
