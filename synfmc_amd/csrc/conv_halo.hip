@@ -18,12 +18,14 @@
 // see halo_px_slot) + W ring 5 x 10,240 B + GroupNorm coefficients 2 x 512 B = 158,720 B.
 //
 // Roofline: MFMA bound.  Algorithmic flops per launch = 2 * n_img*H*W * Cout * 9*Cin; algorithmic bytes = x + w + out (+ residual).
-#include <type_traits>
-
-#include "common.h"
+//
+// What this kernel shares with its small-feature-map geometry (conv_halo4.hip) -- the common parameters, halo piece addressing, the W stream, the
+// filter pack kernels (compiled here), the host-side checks -- is in conv_halo_common.h.
+#include "conv_halo_common.h"
 
 namespace {
 
+using halo::IC;
 constexpr int TH = 10, TW = 32, BM = TH * TW, BN = 160;
 constexpr int HWID = TW + 2, HPIX = (TH + 2) * HWID;       // 34 x 12 = 408 halo pixels
 constexpr int NP = 416;                                    // pixels per channel-group plane (a multiple of 16: every plane starts at the same bank)
@@ -34,23 +36,13 @@ constexpr int WSUB = BN * 64;                              // one 32-deep W sub-
 constexpr int OFF_W = 2 * HALO, OFF_COEF = OFF_W + NBW * WSUB;
 constexpr int LDS_BYTES = OFF_COEF + 2 * 512;              // 158,720
 constexpr int NPIECE = 7;                                  // halo pieces (16 B) per thread and chunk: 51 blocks of 8 pixels x 8 channel groups over 8 waves
-constexpr unsigned OOB = 0x80000000u;
 
-struct CHParams {
-    const bf16_t* x; const bf16_t* x2;      // input [n_img, Hs, Ws, c1] (+ second channel block [n_img, Hs, Ws, cin - c1]: the up blocks' skip connection)
-    int c1;                                 // channels [0, c1) come from x; c1 == cin without x2; c1 % 64 == 0
-    const bf16_t* w;                        // packed filter, see fmc_conv3x3_halo_pack_weight
-    const bf16_t* bias; const bf16_t* temb; const bf16_t* res; bf16_t* out;
-    int n_img, H, W, cin, cout, ups;        // H, W = OUTPUT size; ups: x is [n_img, H/2, W/2, .] read through a nearest 2x upsample
-                                            // (phase mode: H, W = SOURCE size, the output is [n_img, 2 H, 2 W, cout]; tiles_n = 4 * cout / 160)
-    int64_t temb_ld; int temb_div;
+struct CHParams : halo::Params {
     const float* gn_coef; int gn_act;       // [n_img, cin, 2] (scale, shift) or NULL; gn_act: SiLU behind the affine map
     float* gn_part;                         // [n_img, tiles_y * tiles_x, 32, 2] partial (sum, sum of squares) of the ROUNDED outputs, or NULL
     int tiles_y, tiles_x, tiles_n;
     int64_t x_bytes, x2_bytes, w_bytes;
 };
-
-template <int I> using IC = std::integral_constant<int, I>;
 
 __device__ __forceinline__ float silu_fast(float z) { return z * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z)); }
 
@@ -119,17 +111,7 @@ void conv_halo_kernel(const CHParams P) {
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)P.w, 0, (int)P.w_bytes, 0x00020000);
     const int c2 = P.cin - P.c1;
     u32x4 hreg[2];
-    // chunk `ch64` of the input: which source, its row pitch and the channel offset inside it (all wave-uniform); branch-free per lane
-    auto halo_load = [&](int j, int ch64, u32x4& dst) {
-        const int cbeg = ch64 * 64;
-        const bool second = cbeg >= P.c1, past = ch64 >= nchunk;
-        const int pitch = past ? 0 : (second ? c2 : P.c1) * 2;
-        const unsigned coff = past ? OOB : (unsigned)(((second ? cbeg - P.c1 : cbeg) + pg * 8) * 2);
-        unsigned vo = (unsigned)(h_pix[j] * pitch) + coff;
-        vo = h_pix[j] < 0 ? OOB : vo;
-        const __amdgpu_buffer_rsrc_t rs = second ? rsX2 : rsX;
-        dst = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, 0, 0));
-    };
+    auto halo_load = [&](int j, int ch64, u32x4& dst) { dst = halo::piece_load(rsX, rsX2, P.c1, c2, h_pix[j], pg, ch64 * 64, ch64, nchunk); };
     // GroupNorm + SiLU of one staged piece, registers only (runs INSIDE an MFMA phase: its ~64 VALU instructions fill the issue slots between
     // the 25 matrix instructions instead of lengthening a LOAD phase); the 16 coefficients come from LDS ([64 channels][scale, shift] per chunk)
     auto halo_transform = [&](int j, int coefbuf, const u32x4& raw) -> u32x4 {
@@ -164,19 +146,13 @@ void conv_halo_kernel(const CHParams P) {
 
     // ---- W stream ------------------------------------------------------------------------------------------------------------------------
     // packed filter: [tiles_n][sub-tile s = (chunk, tap, half)][160 rows][32] with the LDS chunk swizzle already applied: piece p = KiB p of the block
+    // waves 0, 1 take pieces 0 .. 3 (two neighbours each), the others pieces 4 .. 9
     const int my_piece = clsA ? 2 * wave : wave + 2;
     const unsigned w_vo0 = (unsigned)(lane * 16 + my_piece * 1024);
-    const int w_dst0 = OFF_W + my_piece * 1024;
-    int iss_soff = tile_n * nsub * WSUB, iss_left = nsub, iss_slot = 0;
-    auto w_issue = [&](auto cls) {
-        unsigned char* dst = smem_raw + w_dst0 + iss_slot * WSUB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)dst, 16, (int)w_vo0, iss_soff, 0, 0);
-        if constexpr (decltype(cls)::value)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + 1024), 16, (int)w_vo0, iss_soff + 1024, 0, 0);
-        iss_soff += WSUB;
-        if (--iss_left == 0) { iss_left = nsub; iss_soff = tile_n * nsub * WSUB; }      // (past the end the stream wraps to valid addresses: the counts stay exact)
-        iss_slot = iss_slot + 1 == NBW ? 0 : iss_slot + 1;
-    };
+    const int w_dst0 = OFF_W + my_piece * 1024;             // (the ring offset with my piece folded in: the address arithmetic of the loop as it was)
+    halo::WStream<NBW, WSUB, 1024> ws;
+    ws.start(tile_n * nsub * WSUB, nsub);
+    auto w_issue = [&](auto cls) { ws.template issue<decltype(cls)::value>(smem_raw, rsW, w_vo0, w_dst0, 0, tile_n * nsub * WSUB, nsub); };
 
     // ---- fragments -----------------------------------------------------------------------------------------------------------------------
     f32x4 acc[5][5];
@@ -443,9 +419,10 @@ void conv_halo_kernel(const CHParams P) {
     }
 }
 
-// ---- filter packing: [Cout][3][3][Cin] (channels-last filter) -> [Cout / 160][Cin / 64][9 taps][2 halves][160 rows][32], the 16-byte chunks of a row
-// already in their LDS places (physical chunk p of row r holds logical chunk p ^ (3 * ((r >> 3) & 1))) --------------------------------------------
-__global__ __launch_bounds__(256) void conv_halo_pack_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ dst, int cout, int cin) {
+// ---- filter packing, for both kernels: [Cout][3][3][Cin] (channels-last filter) -> [Cout / BN][Cin / 64][9 taps][2 halves][BN rows][32], the 16-byte
+// chunks of a row already in their LDS places (physical chunk p of row r holds logical chunk p ^ (3 * ((r >> 3) & 1))); BN = 160 here and in the
+// 8-wave form of conv_halo4_kernel, 80 in its 4-wave form ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void conv_halo_pack_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ dst, int cout, int cin, int BN) {
     const int64_t total = (int64_t)cout * 9 * cin / 8;      // 16-byte chunks
     for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (int64_t)gridDim.x * blockDim.x) {
         int64_t t = id;
@@ -526,15 +503,19 @@ __global__ __launch_bounds__(256) void gn_coef_kernel(const float* __restrict__ 
 
 }  // namespace
 
+void halo::pack_filter(const bf16_t* w, bf16_t* dst, int Cin, int Cout, int bn, hipStream_t st) {
+    const int64_t chunks = (int64_t)Cout * 9 * Cin / 8;
+    const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
+    hipLaunchKernelGGL(conv_halo_pack_kernel, dim3(grid), dim3(256), 0, st, w, dst, Cout, Cin, bn);
+}
+
 extern "C" int64_t fmc_conv3x3_halo_packed_bytes(int Cin, int Cout) { return (int64_t)Cout * 9 * Cin * 2; }
 
 extern "C" int fmc_conv3x3_halo_pack_weight(const void* w, void* dst, int Cin, int Cout, void* stream) {
     if (!w || !dst) FMC_FAIL(FMC_E_NULL, "conv3x3_halo_pack_weight: NULL pointer");
     if (Cin % 64 || Cout % BN) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_pack_weight: Cin %% 64 / Cout %% 160 (Cin=%d Cout=%d)", Cin, Cout);
     if (!fmc_aligned16(w) || !fmc_aligned16(dst)) FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo_pack_weight: pointers must be 16-byte aligned");
-    const int64_t chunks = (int64_t)Cout * 9 * Cin / 8;
-    const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
-    hipLaunchKernelGGL(conv_halo_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w, (bf16_t*)dst, Cout, Cin);
+    halo::pack_filter((const bf16_t*)w, (bf16_t*)dst, Cin, Cout, BN, (hipStream_t)stream);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_pack_weight");
     return 0;
 }
@@ -552,27 +533,16 @@ extern "C" int fmc_conv3x3_halo_supported(int n_img, int H, int W, int Cin, int 
 extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
                                      const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
                                      int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
-    if (!x || !w_packed || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo: NULL x / w / out");
     if (!x2) Cin1 = Cin;
-    if (!fmc_conv3x3_halo_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo: needs W %% 32 == 0, Cin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
-                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x);
-    if (!fmc_aligned16(x) || !fmc_aligned16(w_packed) || !fmc_aligned16(out) || (x2 && !fmc_aligned16(x2)) || (residual && !fmc_aligned16(residual)) ||
-        (bias && (reinterpret_cast<uintptr_t>(bias) & 7)) || (temb && ((reinterpret_cast<uintptr_t>(temb) & 7) || temb_row_stride % 4)))
-        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo: x / w / out / residual must be 16-byte aligned, bias / temb rows 8-byte aligned");
-    if (temb && temb_img_div < 1) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo: temb_img_div %d", temb_img_div);
-    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))     // a channel tile must hold whole GroupNorm groups of an even number of channels
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo: the statistics epilogue needs Cout %% 64 == 0 and 160 %% (Cout / 32) == 0 (Cout=%d)", Cout);
+    if (int e = halo::check_args("conv3x3_halo", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x),
+                                 "%s: needs W %% 32 == 0, Cin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
+        return e;
     CHParams P;
-    P.x = (const bf16_t*)x; P.x2 = (const bf16_t*)x2; P.c1 = Cin1;
-    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.temb = (const bf16_t*)temb; P.res = (const bf16_t*)residual; P.out = (bf16_t*)out;
-    P.n_img = n_img; P.H = H; P.W = W; P.cin = Cin; P.cout = Cout; P.ups = upsample2x ? 1 : 0;
-    P.temb_ld = temb_row_stride; P.temb_div = temb ? temb_img_div : 1;
-    P.gn_coef = gn_coef; P.gn_act = gn_act; P.gn_part = gn_partials;
+    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
+    P.gn_coef = gn_coef; P.gn_act = gn_act;
     P.tiles_y = (H + TH - 1) / TH; P.tiles_x = W / TW; P.tiles_n = Cout / BN;
-    const int64_t hs = upsample2x ? H / 2 : H, ws = upsample2x ? W / 2 : W;
-    P.x_bytes = (int64_t)n_img * hs * ws * Cin1 * 2; P.x2_bytes = (int64_t)n_img * hs * ws * (Cin - Cin1) * 2;
-    P.w_bytes = (int64_t)Cout * 9 * Cin * 2;
     const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
     if (!gn_coef) fmc_launch<conv_halo_kernel<0>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     else if (gn_act) fmc_launch<conv_halo_kernel<1>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
@@ -605,23 +575,15 @@ extern "C" int fmc_conv3x3_halo_fold_supported(int n_img, int Hs, int Ws, int Ci
 
 extern "C" int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
                                           int Cout, float* gn_partials, void* stream) {
-    if (!x || !w_folded || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo_fold: NULL x / w / out");
-    if (!fmc_conv3x3_halo_fold_supported(n_img, Hs, Ws, Cin, Cout))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_fold: needs Ws %% 32 == 0, Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
-                 n_img, Hs, Ws, Cin, Cout);
-    if (!fmc_aligned16(x) || !fmc_aligned16(w_folded) || !fmc_aligned16(out) || (bias && (reinterpret_cast<uintptr_t>(bias) & 7)))
-        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo_fold: x / w / out must be 16-byte aligned, bias 8-byte aligned");
-    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_fold: the statistics epilogue needs Cout %% 64 == 0 and 160 %% (Cout / 32) == 0 (Cout=%d)", Cout);
+    if (int e = halo::check_args("conv3x3_halo_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_fold_supported(n_img, Hs, Ws, Cin, Cout),
+                                 "%s: needs Ws %% 32 == 0, Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
+                                 n_img, Hs, Ws, Cin, Cout))
+        return e;
     CHParams P;
-    P.x = (const bf16_t*)x; P.x2 = nullptr; P.c1 = Cin;
-    P.w = (const bf16_t*)w_folded; P.bias = (const bf16_t*)bias; P.temb = nullptr; P.res = nullptr; P.out = (bf16_t*)out;
-    P.n_img = n_img; P.H = Hs; P.W = Ws; P.cin = Cin; P.cout = Cout; P.ups = 0;
-    P.temb_ld = 0; P.temb_div = 1;
-    P.gn_coef = nullptr; P.gn_act = 0; P.gn_part = gn_partials;
+    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
+    P.gn_coef = nullptr; P.gn_act = 0;
     P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = Ws / TW; P.tiles_n = 4 * (Cout / BN);
-    P.x_bytes = (int64_t)n_img * Hs * Ws * Cin * 2; P.x2_bytes = 0;
-    P.w_bytes = (int64_t)Cout * 16 * Cin * 2;
     const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
     fmc_launch<conv_halo_kernel<0, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_bf16");

@@ -15,18 +15,15 @@
 //     while the 25 MFMAs of sub-tile s run -- with ONE barrier per sub-tile (it publishes the W sub-tile the next reads need).
 // LDS: halo double buffer 2 x 8 x NP x 16 B + W ring 5 x 5 KiB (TW = 16: 135,168 B; TW = 8: 163,840 - the ring shrinks to 4).
 // Roofline: MFMA bound.  Algorithmic flops per launch = 2 * n_img*H*W * Cout * 9*Cin.
-#include <type_traits>
-
-#include "common.h"
+//
+// What this kernel shares with conv_halo_kernel -- the common parameters, halo piece addressing, the W stream, the filter pack kernels (compiled in
+// conv_halo.hip), the host-side checks -- is in conv_halo_common.h.
+#include "conv_halo_common.h"
 
 namespace {
 
+using halo::IC;
 constexpr int BM = 320;
-#ifndef FMC_C4_INTERLEAVE
-#define FMC_C4_INTERLEAVE 1
-#endif
-constexpr bool INTERLEAVE = FMC_C4_INTERLEAVE != 0;          // A/B switch (compile time): C - E issued between the MFMAs instead of in front of them
-constexpr unsigned OOB = 0x80000000u;
 
 // NWV waves: 4 (one per SIMD, 320 pixels x 80 channels) or 8 (two per SIMD, 320 x 160: wave = pixel block wave % 4, channel block wave / 4)
 template <int TW, int NWV> struct Geo {
@@ -48,12 +45,7 @@ template <int TW, int NWV> struct Geo {
     static_assert(HPIX % 8 == 0 && LDS_BYTES <= 163840 && NPIECE <= 18, "geometry");
 };
 
-struct C4Params {
-    const bf16_t* x; const bf16_t* x2; int c1;              // as conv_halo.hip: two-source input, channels [0, c1) from x
-    const bf16_t* w;                                        // fmc_conv3x3_halo4_pack_weight: [Cout / 80][Cin / 64][9][2][80 rows][32], chunk-swizzled
-    const bf16_t* bias; const bf16_t* temb; const bf16_t* res; bf16_t* out;
-    int n_img, H, W, cin, cout, ups;                        // (phase mode: H, W = SOURCE size, the output is [n_img, 2 H, 2 W, cout]; tiles_n = 4 * cout / BN)
-    int64_t temb_ld; int temb_div;
+struct C4Params : halo::Params {                            // (w: fmc_conv3x3_halo4_pack_weight, [Cout / BN][Cin / 64][9][2][BN rows][32], chunk-swizzled)
     float* gn_part;                                         // [n_img, tiles_y, 32, 2] partial sums of the rounded outputs (one split per row block), or NULL
     int tiles_y, tiles_x, tiles_p, tiles_n;                 // row blocks per image column / per image row, pixel tiles, channel tiles
     int splits; float* ws;                                  // split-K: the 64-channel chunks are dealt to `splits` workgroups per tile, which leave fp32 partial
@@ -61,8 +53,6 @@ struct C4Params {
     int64_t x_bytes, x2_bytes, w_bytes;
     int xcd_pc;                                             // tile order: the 8 XCDs as xcd_pc filter-slice groups x 8 / xcd_pc pixel groups (launch_c4), 0 = contiguous ranges
 };
-
-template <int I> using IC = std::integral_constant<int, I>;
 
 // halo pieces requested in sub-tile i of a chunk (requested at LOAD(i), written at LOAD(i + 3)): PPS = 2 per sub-tile where a thread has more than
 // 12 pieces per chunk (4 waves), else one (8 waves: fewer staging registers in flight)
@@ -149,14 +139,7 @@ void conv_halo4_kernel(const C4Params P) {
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)P.w, 0, (int)P.w_bytes, 0x00020000);
     const int c2 = P.cin - P.c1;
     auto halo_load = [&](int j, int crel) -> u32x4 {             // crel: chunk relative to my range
-        const int cbeg = (ck0 + crel) * 64;
-        const bool second = cbeg >= P.c1, past = crel >= nchunk;
-        const int pitch = past ? 0 : (second ? c2 : P.c1) * 2;
-        const unsigned coff = past ? OOB : (unsigned)(((second ? cbeg - P.c1 : cbeg) + pg * 8) * 2);
-        unsigned vo = (unsigned)(h_pix[j] * pitch) + coff;
-        vo = h_pix[j] < 0 ? OOB : vo;
-        const __amdgpu_buffer_rsrc_t rs = second ? rsX2 : rsX;
-        return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, 0, 0));
+        return halo::piece_load(rsX, rsX2, P.c1, c2, h_pix[j], pg, (ck0 + crel) * 64, crel, nchunk);
     };
     auto halo_store = [&](int j, int buf, const u32x4& v) {
         if (8 * (NWV * j + wave) < G::HPIX)                   // (wave-uniform: the last piece index exists for the first waves only)
@@ -166,16 +149,9 @@ void conv_halo4_kernel(const C4Params P) {
     // ---- W stream: piece p = KiB p of the 5-KiB sub-tile block; wave w issues piece w, wave 0 also piece 4 --------------------------------------------
     const unsigned w_vo0 = (unsigned)(lane * 16 + wave * 1024);
     const int w_base = (tile_n * nchunk_all + ck0) * NS * WSUB;       // my first sub-tile inside the channel tile's block
-    int iss_soff = w_base, iss_left = nsub, iss_slot = 0;
-    auto w_issue = [&](auto cls) {
-        unsigned char* dst = smem_raw + OFF_W + iss_slot * WSUB + wave * 1024;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)dst, 16, (int)w_vo0, iss_soff, 0, 0);
-        if constexpr (decltype(cls)::value)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + NWV * 1024), 16, (int)w_vo0, iss_soff + NWV * 1024, 0, 0);
-        iss_soff += WSUB;
-        if (--iss_left == 0) { iss_left = nsub; iss_soff = w_base; }      // (past the end the stream wraps to valid addresses)
-        iss_slot = iss_slot + 1 == NBW ? 0 : iss_slot + 1;
-    };
+    halo::WStream<NBW, WSUB, NWV * 1024> ws;
+    ws.start(w_base, nsub);
+    auto w_issue = [&](auto cls) { ws.template issue<decltype(cls)::value>(smem_raw, rsW, w_vo0, OFF_W, wave * 1024, w_base, nsub); };
 
     // ---- fragments: my 80 pixels x all 80 channels ------------------------------------------------------------------------------------------------------
     f32x4 acc[5][5];
@@ -257,25 +233,23 @@ void conv_halo4_kernel(const C4Params P) {
 #pragma unroll
                     for (int nb = 0; nb < 5; ++nb)
                         acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i & 1][nb], af[i & 1][mb], acc[mb][nb], 0, 0, 0);
-                if constexpr (INTERLEAVE) {
-                    constexpr int NST = PH ? PPS : 2, NRQ = PH ? PPS + 2 : 4;
+                constexpr int NST = PH ? PPS : 2, NRQ = PH ? PPS + 2 : 4;
 #pragma unroll
-                    for (int k = 0; k < NST; ++k) {              // staging stores first (their data is oldest), one per matrix instruction
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 10; ++k) {               // the 10 fragment reads of sub-tile s + 1
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NRQ; ++k) {              // halo requests and the W request(s)
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 25 - 10 - NST - NRQ, 0);
+                for (int k = 0; k < NST; ++k) {                  // staging stores first (their data is oldest), one per matrix instruction
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
                 }
+#pragma unroll
+                for (int k = 0; k < 10; ++k) {                   // the 10 fragment reads of sub-tile s + 1
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+#pragma unroll
+                for (int k = 0; k < NRQ; ++k) {                  // halo requests and the W request(s)
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 25 - 10 - NST - NRQ, 0);
                 __builtin_amdgcn_sched_barrier(0);
             };
             sub(IC<0>{}); sub(IC<1>{}); sub(IC<2>{}); sub(IC<3>{}); sub(IC<4>{}); sub(IC<5>{});
@@ -433,25 +407,6 @@ void conv_halo4_kernel(const C4Params P) {
     }
 }
 
-// filter [Cout][3][3][Cin] -> [Cout / 80][Cin / 64][9 taps][2 halves][80 rows][32], 16-byte chunks in their LDS places (chunk p of row r holds
-// logical chunk p ^ (3 * ((r >> 3) & 1)))
-__global__ __launch_bounds__(256) void conv_halo4_pack_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ dst, int cout, int cin, int BN) {
-    const int64_t total = (int64_t)cout * 9 * cin / 8;
-    for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (int64_t)gridDim.x * blockDim.x) {
-        int64_t t = id;
-        const int p = (int)(t & 3); t >>= 2;
-        const int row = (int)(t % BN); t /= BN;
-        const int hk = (int)(t & 1); t >>= 1;
-        const int tap = (int)(t % 9); t /= 9;
-        const int nchunk = cin >> 6;
-        const int ch64 = (int)(t % nchunk); t /= nchunk;
-        const int nt = (int)t;
-        const int lc = p ^ (3 * ((row >> 3) & 1));
-        const int64_t src = (((int64_t)(nt * BN + row) * 9 + tap) * cin + ch64 * 64 + hk * 32 + lc * 8);
-        *reinterpret_cast<u32x4*>(dst + id * 8) = *reinterpret_cast<const u32x4*>(w + src);
-    }
-}
-
 // second pass of a split launch: out = sum over the splits (fixed order) + bias + temb + residual, 8 channels of one pixel per thread
 __global__ __launch_bounds__(256) void conv_halo4_finish_kernel(const C4Params P) {
     const int64_t mtot = (int64_t)P.n_img * P.H * P.W, cpr = P.cout / 8, total = mtot * cpr;
@@ -527,9 +482,7 @@ extern "C" int fmc_conv3x3_halo4_pack_weight(const void* w, void* dst, int Cin, 
     if (!w || !dst) FMC_FAIL(FMC_E_NULL, "conv3x3_halo4_pack_weight: NULL pointer");
     if (Cin % 64 || Cout % BN) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_pack_weight: Cin %% 64 / Cout %% %d (Cin=%d Cout=%d)", BN, Cin, Cout);
     if (!fmc_aligned16(w) || !fmc_aligned16(dst)) FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo4_pack_weight: pointers must be 16-byte aligned");
-    const int64_t chunks = (int64_t)Cout * 9 * Cin / 8;
-    const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
-    hipLaunchKernelGGL(conv_halo4_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w, (bf16_t*)dst, Cout, Cin, BN);
+    halo::pack_filter((const bf16_t*)w, (bf16_t*)dst, Cin, Cout, BN, (hipStream_t)stream);      // (the one pack kernel, conv_halo.hip)
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_pack_weight");
     return 0;
 }
@@ -565,17 +518,12 @@ extern "C" int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, c
                                       int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes,
                                       int wide, void* stream) {
     const int BN = wide ? 160 : 80;
-    if (!x || !w_packed || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo4: NULL x / w / out");
     if (!x2) Cin1 = Cin;
-    if (!fmc_conv3x3_halo4_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: needs W %% 8 == 0 (wide: %% 16), Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
-                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", BN, n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x);
-    if (!fmc_aligned16(x) || !fmc_aligned16(w_packed) || !fmc_aligned16(out) || (x2 && !fmc_aligned16(x2)) || (residual && !fmc_aligned16(residual)) ||
-        (bias && (reinterpret_cast<uintptr_t>(bias) & 7)) || (temb && ((reinterpret_cast<uintptr_t>(temb) & 7) || temb_row_stride % 4)))
-        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo4: x / w / out / residual must be 16-byte aligned, bias / temb rows 8-byte aligned");
-    if (temb && temb_img_div < 1) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: temb_img_div %d", temb_img_div);
-    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: the statistics epilogue needs Cout %% 64 == 0 and %d %% (Cout / 32) == 0 (Cout=%d)", BN, Cout);
+    if (int e = halo::check_args("conv3x3_halo4", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo4_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide),
+                                 "%s: needs W %% 8 == 0 (wide: %% 16), Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", BN, n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
+        return e;
     if (split_k < 1) split_k = 1;
     if (split_k > Cin / 64) split_k = Cin / 64;
     if (split_k > 1) {
@@ -584,15 +532,9 @@ extern "C" int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, c
             FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: split_k %d needs a 16-byte aligned workspace of %lld bytes", split_k, (long long)split_k * n_img * H * W * Cout * 4);
     }
     C4Params P;
-    P.x = (const bf16_t*)x; P.x2 = (const bf16_t*)x2; P.c1 = Cin1;
-    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.temb = (const bf16_t*)temb; P.res = (const bf16_t*)residual; P.out = (bf16_t*)out;
-    P.n_img = n_img; P.H = H; P.W = W; P.cin = Cin; P.cout = Cout; P.ups = upsample2x ? 1 : 0;
-    P.temb_ld = temb_row_stride; P.temb_div = temb ? temb_img_div : 1;
-    P.gn_part = gn_partials; P.tiles_n = Cout / BN;
+    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
+    P.tiles_n = Cout / BN;
     P.splits = split_k; P.ws = (float*)workspace;
-    const int64_t hs = upsample2x ? H / 2 : H, ws = upsample2x ? W / 2 : W;
-    P.x_bytes = (int64_t)n_img * hs * ws * Cin1 * 2; P.x2_bytes = (int64_t)n_img * hs * ws * (Cin - Cin1) * 2;
-    P.w_bytes = (int64_t)Cout * 9 * Cin * 2;
     hipStream_t st = (hipStream_t)stream;
     if (c4_tw(W) == 8) launch_c4<8, 4>(P, st);
     else if (wide) launch_c4<16, 8>(P, st);
@@ -613,23 +555,15 @@ extern "C" int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int C
 extern "C" int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
                                            int Cout, float* gn_partials, int wide, void* stream) {
     const int BN = wide ? 160 : 80;
-    if (!x || !w_folded || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_halo4_fold: NULL x / w / out");
-    if (!fmc_conv3x3_halo4_fold_supported(n_img, Hs, Ws, Cin, Cout, wide))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_fold: needs Ws %% 8 == 0 (wide: %% 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
-                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d)", BN, n_img, Hs, Ws, Cin, Cout);
-    if (!fmc_aligned16(x) || !fmc_aligned16(w_folded) || !fmc_aligned16(out) || (bias && (reinterpret_cast<uintptr_t>(bias) & 7)))
-        FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo4_fold: x / w / out must be 16-byte aligned, bias 8-byte aligned");
-    if (gn_partials && (Cout % 64 || BN % (Cout / 32)))
-        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_fold: the statistics epilogue needs Cout %% 64 == 0 and %d %% (Cout / 32) == 0 (Cout=%d)", BN, Cout);
+    if (int e = halo::check_args("conv3x3_halo4_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo4_fold_supported(n_img, Hs, Ws, Cin, Cout, wide),
+                                 "%s: needs Ws %% 8 == 0 (wide: %% 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
+                                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d)", BN, n_img, Hs, Ws, Cin, Cout))
+        return e;
     C4Params P;
-    P.x = (const bf16_t*)x; P.x2 = nullptr; P.c1 = Cin;
-    P.w = (const bf16_t*)w_folded; P.bias = (const bf16_t*)bias; P.temb = nullptr; P.res = nullptr; P.out = (bf16_t*)out;
-    P.n_img = n_img; P.H = Hs; P.W = Ws; P.cin = Cin; P.cout = Cout; P.ups = 0;
-    P.temb_ld = 0; P.temb_div = 1;
-    P.gn_part = gn_partials; P.tiles_n = 4 * (Cout / BN);
+    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
+    P.tiles_n = 4 * (Cout / BN);
     P.splits = 1; P.ws = nullptr;
-    P.x_bytes = (int64_t)n_img * Hs * Ws * Cin * 2; P.x2_bytes = 0;
-    P.w_bytes = (int64_t)Cout * 16 * Cin * 2;
     hipStream_t st = (hipStream_t)stream;
     if (c4_tw(Ws) == 8) launch_c4<8, 4, true>(P, st);
     else if (wide) launch_c4<16, 8, true>(P, st);

@@ -1849,15 +1849,48 @@ def conv3x3_halo_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: in
     return bool(_lib.load().fmc_conv3x3_halo_supported(n, h, w, cin, cin1, cout, int(upsample)))
 
 
-def _w_halo_packed(weight_cl: torch.Tensor) -> torch.Tensor:
-    """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> the halo kernel's sub-tile order (`fmc_conv3x3_halo_pack_weight`), cached on the weight."""
+def _w_packed(weight_cl: torch.Tensor, key: str, factor: int, fn: str, *args) -> torch.Tensor:
+    """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> a halo kernel's sub-tile order, cached on the weight per version under `key`:
+    `factor` = 9 taps, or 16 for the folded filter of the phase mode; `fn(filter, packed, Cin, Cout, *args, stream)` is the C pack routine."""
     def build():
         cout, cin = weight_cl.shape[:2]
         assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        out = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_halo_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, _stream()), "fmc_conv3x3_halo_pack_weight")
+        out = torch.empty(cout * factor * cin, dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(getattr(_lib.load(), fn)(weight_cl.data_ptr(), out.data_ptr(), cin, cout, *args, _stream()), fn)
         return out
-    return derived_on_owner(weight_cl, "_fmc_wtm", "halo", build)
+    return derived_on_owner(weight_cl, "_fmc_wtm", key, build)
+
+
+def _w_halo_packed(weight_cl: torch.Tensor) -> torch.Tensor:
+    """The filter in `conv_halo_kernel`'s sub-tile order (`fmc_conv3x3_halo_pack_weight`: 160-channel tiles), cached on the weight."""
+    return _w_packed(weight_cl, "halo", 9, "fmc_conv3x3_halo_pack_weight")
+
+
+def _gn_tagged(y, want: bool, cout: int):
+    """A halo launch's result in `conv3x3` -- `(out, partials)` with `want`, else `out` -- as NCHW view; the statistics go with it as `_fmc_gn` for
+    the GroupNorm that consumes it."""
+    if not want:
+        return y.permute(0, 3, 1, 2)
+    y, part = y
+    gn_epilogue_calls["emitted"] += 1
+    y = y.permute(0, 3, 1, 2)
+    y._fmc_gn = (part, cout)
+    return y
+
+
+def _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc):
+    """The shape checks `conv3x3_halo` and `conv3x3_halo4` share -> `(n, h, w, c1, cin, cout)`, h x w the OUTPUT size."""
+    n, hs, ws, c1 = x_nhwc.shape
+    h, w = (2 * hs, 2 * ws) if upsample else (hs, ws)
+    cout, cin = weight_cl.shape[:2]
+    assert x_nhwc.is_contiguous() and x_nhwc.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16
+    if x2_nhwc is not None:
+        assert x2_nhwc.is_contiguous() and x2_nhwc.shape[:3] == x_nhwc.shape[:3] and x2_nhwc.dtype == x_nhwc.dtype and c1 + x2_nhwc.shape[3] == cin
+    else:
+        assert c1 == cin
+    assert temb is None or (temb.stride(1) == 1 and temb.shape == (n // temb_div, cout) and n % temb_div == 0)
+    assert residual_nhwc is None or (residual_nhwc.is_contiguous() and residual_nhwc.shape == (n, h, w, cout))
+    return n, h, w, c1, cin, cout
 
 
 def groupnorm_coef(partials: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, hw: int, C: int, groups: int, eps: float,
@@ -1878,14 +1911,7 @@ def conv3x3_halo4_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: i
 
 
 def _w_halo4_packed(weight_cl: torch.Tensor, wide: bool = False) -> torch.Tensor:
-    def build():
-        cout, cin = weight_cl.shape[:2]
-        assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        out = torch.empty(cout * 9 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_halo4_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, int(wide), _stream()),
-                   "fmc_conv3x3_halo4_pack_weight")
-        return out
-    return derived_on_owner(weight_cl, "_fmc_wtm", "halo4w" if wide else "halo4", build)
+    return _w_packed(weight_cl, "halo4w" if wide else "halo4", 9, "fmc_conv3x3_halo4_pack_weight", int(wide))
 
 
 def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 256, wide: bool = False) -> int:
@@ -1906,16 +1932,7 @@ def conv3x3_halo4(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb
     """`conv3x3` on the small feature maps (images 8 / 16 / 32 pixels wide; csrc/conv_halo4.hip): arguments and results as `conv3x3_halo` without the
     GroupNorm operand path; the statistics partials are per (image, row block of 5 / 10 rows)."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc)
-    n, hs, ws, c1 = x_nhwc.shape
-    h, w = (2 * hs, 2 * ws) if upsample else (hs, ws)
-    cout, cin = weight_cl.shape[:2]
-    assert x_nhwc.is_contiguous() and x_nhwc.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16
-    if x2_nhwc is not None:
-        assert x2_nhwc.is_contiguous() and x2_nhwc.shape[:3] == x_nhwc.shape[:3] and x2_nhwc.dtype == x_nhwc.dtype and c1 + x2_nhwc.shape[3] == cin
-    else:
-        assert c1 == cin
-    assert temb is None or (temb.stride(1) == 1 and temb.shape == (n // temb_div, cout) and n % temb_div == 0)
-    assert residual_nhwc is None or (residual_nhwc.is_contiguous() and residual_nhwc.shape == (n, h, w, cout))
+    n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     L = _lib.load()
     wp = _w_halo4_packed(weight_cl, wide)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
@@ -1953,16 +1970,7 @@ def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=
     filter `[Cout, C1 + C2, 3, 3]` channels-last, `gn_coef [N, C1 + C2, 2]` fp32 or None (plain convolution).  Returns out `[N, H, W, Cout]`, or
     `(out, partials [N, tiles, 32, 2])` with `emit_gn` (statistics of the output for the GroupNorm that consumes it)."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc, gn_coef)
-    n, hs, ws, c1 = x_nhwc.shape
-    h, w = (2 * hs, 2 * ws) if upsample else (hs, ws)
-    cout, cin = weight_cl.shape[:2]
-    assert x_nhwc.is_contiguous() and x_nhwc.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16
-    if x2_nhwc is not None:
-        assert x2_nhwc.is_contiguous() and x2_nhwc.shape[:3] == x_nhwc.shape[:3] and x2_nhwc.dtype == x_nhwc.dtype and c1 + x2_nhwc.shape[3] == cin
-    else:
-        assert c1 == cin
-    assert temb is None or (temb.stride(1) == 1 and temb.shape == (n // temb_div, cout) and n % temb_div == 0)
-    assert residual_nhwc is None or (residual_nhwc.is_contiguous() and residual_nhwc.shape == (n, h, w, cout))
+    n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     assert gn_coef is None or (gn_coef.shape == (n, cin, 2) and gn_coef.dtype == torch.float32 and gn_coef.is_contiguous())
     L = _lib.load()
     wp = _w_halo_packed(weight_cl)
@@ -2039,14 +2047,7 @@ def conv3x3_upfold_arm(n: int, hs: int, ws: int, cin: int, cout: int) -> Optiona
 def _w_upfold_packed(weight_cl: torch.Tensor, tile_channels: int) -> torch.Tensor:
     """Channels-last 3x3 filter -> the folded 4 x 2x2-tap filter in the phase-mode kernels' sub-tile order (16 / 9 of the filter's bytes), cached on
     the weight per version like the other packs."""
-    def build():
-        cout, cin = weight_cl.shape[:2]
-        assert weight_cl.is_contiguous(memory_format=torch.channels_last)
-        out = torch.empty(cout * 16 * cin, dtype=weight_cl.dtype, device=weight_cl.device)
-        _lib.check(_lib.load().fmc_conv3x3_upfold_pack_weight(weight_cl.data_ptr(), out.data_ptr(), cin, cout, tile_channels, _stream()),
-                   "fmc_conv3x3_upfold_pack_weight")
-        return out
-    return derived_on_owner(weight_cl, "_fmc_wtm", "upfold%d" % tile_channels, build)
+    return _w_packed(weight_cl, "upfold%d" % tile_channels, 16, "fmc_conv3x3_upfold_pack_weight", tile_channels)
 
 
 def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emit_gn: bool = False, arm: Optional[str] = None):
@@ -2596,13 +2597,7 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
             want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and bn % (cout // 32) == 0 and (arm == "halo" or h * w >= GN_MIN_HW))
             dispatch_calls["conv3x3"]["own"] += 1
             y = conv3x3_upfold(x, weight_cl, bias, emit_gn=want, arm=arm)
-            if want:
-                y, part = y
-                gn_epilogue_calls["emitted"] += 1
-                y = y.permute(0, 3, 1, 2)
-                y._fmc_gn = (part, cout)
-                return y
-            return y.permute(0, 3, 1, 2)
+            return _gn_tagged(y, want, cout)
     # the halo-resident kernel (csrc/conv_halo.hip): 1.75 - 1.95 x the ring kernels wherever its 10 x 32 pixel x 160 channel tiles fill the chip
     # (tools/scratch/r05/bench_halo.py); every such convolution also leaves the statistics of the GroupNorm that consumes its output
     if (CONV_HALO and not stride2 and (temb is None or temb.stride(1) == 1) and conv3x3_halo_supported(n, h, w, cin, cin, cout, upsample)
@@ -2610,13 +2605,7 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
         want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0 and not torch.is_grad_enabled())
         dispatch_calls["conv3x3"]["own"] += 1
         y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
-        if want:
-            y, part = y
-            gn_epilogue_calls["emitted"] += 1
-            y = y.permute(0, 3, 1, 2)
-            y._fmc_gn = (part, cout)
-            return y
-        return y.permute(0, 3, 1, 2)
+        return _gn_tagged(y, want, cout)
     # ... and its 4-wave form for the small feature maps (images 8 / 16 pixels wide: the two inner levels; csrc/conv_halo4.hip), split over the
     # reduction where the tiles alone would leave most of the chip idle (5x8-pixel images: 64 tiles)
     if (CONV_HALO and CONV_HALO4 and not stride2 and w % 8 == 0 and (temb is None or temb.stride(1) == 1)
@@ -2628,13 +2617,7 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
         want = bool(emit_gn and GN_EPILOGUE and h * w >= GN_MIN_HW and cout % 64 == 0 and 80 % (cout // 32) == 0 and not torch.is_grad_enabled()
                     and conv3x3_halo4_split(n, h, w, cin, cout) == 1)
         y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
-        if want:
-            y, part = y
-            gn_epilogue_calls["emitted"] += 1
-            y = y.permute(0, 3, 1, 2)
-            y._fmc_gn = (part, cout)
-            return y
-        return y.permute(0, 3, 1, 2)
+        return _gn_tagged(y, want, cout)
     if emit_gn and gn_emit_ok(n * h * w, cout, 9 * cin, h * w, x.dtype):
         dispatch_calls["conv3x3"]["own"] += 1
         y, tag = conv3x3_gn(x, weight_cl, bias, temb, r, temb_div, upsample, stride2)

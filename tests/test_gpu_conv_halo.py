@@ -198,3 +198,21 @@ def test_conv3x3_halo4_matches_fp32_conv(n, h, w, cin, cout, c2, ups, extras):
             wide, wparts = wide
             assert rel_inf(wparts.sum(1), parts.sum(1)) < 1e-5
         assert torch.equal(wide, got)
+
+
+def test_halo_and_wide_halo4_filter_packs_are_one_kernel():
+    """`fmc_conv3x3_halo_pack_weight` and `fmc_conv3x3_halo4_pack_weight(wide = 1)` both pack for 160-channel tiles through the one pack kernel
+    (csrc/conv_halo.hip): at Cin = 64, Cout = 160 the two buffers are bit-equal."""
+    from synfmc_amd import _lib
+    from synfmc_amd import hip_ops as K
+    cin, cout = 64, 160
+    g = torch.Generator().manual_seed(5)
+    wt = torch.randn(cout, cin, 3, 3, generator=g).bfloat16().cuda().contiguous(memory_format=torch.channels_last)
+    a = torch.zeros(cout * 9 * cin, dtype=torch.bfloat16, device="cuda")
+    b = torch.ones_like(a)
+    L = _lib.load()
+    _lib.check(L.fmc_conv3x3_halo_pack_weight(wt.data_ptr(), a.data_ptr(), cin, cout, K._stream()), "fmc_conv3x3_halo_pack_weight")
+    _lib.check(L.fmc_conv3x3_halo4_pack_weight(wt.data_ptr(), b.data_ptr(), cin, cout, 1, K._stream()), "fmc_conv3x3_halo4_pack_weight")
+    torch.cuda.synchronize()
+    assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+    assert torch.equal(a.view(torch.int16).sort().values, wt.permute(0, 2, 3, 1).reshape(-1).view(torch.int16).sort().values)     # a permutation of the filter
