@@ -736,6 +736,36 @@ __global__ __launch_bounds__(256) void temporal_attn_bwd_kernel(const TABwdParam
     }
 }
 
+// One frame: the softmax over a single key is 1 whatever its score, so O = V and the gradients are dV = dO, dQ = dK = 0 -- exactly, in
+// every storage type.  The general kernel gets there only as far as its products go: in fp32 storage `1.0 * dO` is three split-bf16
+// products and comes back with 16 of dO's 24 significant bits.  Nothing is staged and Q, K, V are not read (the fp8 entry included: its
+// dO and gradients are bf16); one thread copies 8 channels of one (clip, pixel) row.
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_attn_bwd_one_frame_kernel(const TABwdParams P) {
+    const int cpr = P.H * P.D / 8;
+    const int64_t total = (int64_t)P.n_clips * P.n_pix * cpr;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int ch = (int)(idx % cpr);
+        const int64_t u = idx / cpr;
+        const int64_t pix = u % P.n_pix, clip = u / P.n_pix;
+        const int64_t out = clip * P.dcs + pix * P.dps + ch * 8;
+        float v[8];
+        Vec8<T>::load((const T*)P.d_o + clip * P.ocs + pix * P.ops + ch * 8, v);
+        Vec8<T>::store((T*)P.dv + out, v);
+        zero8(v);
+        Vec8<T>::store((T*)P.dq + out, v);
+        Vec8<T>::store((T*)P.dk + out, v);
+    }
+}
+
+template <typename T>
+void launch_ta_bwd_one_frame(const TABwdParams& P, hipStream_t st) {
+    const int64_t total = (int64_t)P.n_clips * P.n_pix * (P.H * P.D / 8);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    fmc_launch<temporal_attn_bwd_one_frame_kernel<T>>(dim3((unsigned)blocks), dim3(256), 0, st, P);
+}
+
 template <typename T, int FT, int NK32, bool PART>
 void launch_ta_bwd(const TABwdParams& P, hipStream_t st) {
     const int CW = P.GH * P.D;
@@ -762,6 +792,7 @@ int dispatch_ta_bwd_k(const TABwdParams& P, hipStream_t st) {
 // frame tiles and partial flag from the real frame count: F = 16 / 32 take the whole-tile kernels they always took
 template <typename T>
 int dispatch_ta_bwd(const TABwdParams& P, hipStream_t st) {
+    if (P.F == 1) { launch_ta_bwd_one_frame<T>(P, st); return 0; }
     if (P.F == 16) return dispatch_ta_bwd_k<T, 1, false>(P, st);
     if (P.F == 32) return dispatch_ta_bwd_k<T, 2, false>(P, st);
     return P.F < 16 ? dispatch_ta_bwd_k<T, 1, true>(P, st) : dispatch_ta_bwd_k<T, 2, true>(P, st);
