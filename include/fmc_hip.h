@@ -451,6 +451,31 @@ int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* 
 int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide);
 int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
                                 float* gn_partials, int wide, void* stream);
+/* Backward-data of the two resampling convolutions (training, frozen filter; csrc/conv_resample_bwd.hip).  The filter is the forward's
+ * [Cout][3][3][Cin] (channels-last), Cin % 64 == 0 and Cout % 64 == 0, any n_img >= 1, every tensor below 2^31 bytes; dY and dX are channels-last bf16,
+ * fp32 accumulation on v_mfma_f32_16x16x32_bf16, bias-free (a bias has no data gradient).  No W % 8 / W % 32 rule: the tiles run over a flat pixel list.
+ *   down (3x3, stride 2, pad 1; the forward's input H x W even, >= 2; dY [n_img, H/2, W/2, Cout] -> dX [n_img, H, W, Cin]):
+ *     dX[2i+py, 2j+px] = sum over (ky, di) in T[py], (kx, dj) in T[px] of W[.][.][ky][kx]^T dY[i+di, j+dj], T[0] = {(1, 0)}, T[1] = {(2, 0), (0, +1)},
+ *     zero outside dY: four launches' worth of 1 / 2 / 2 / 4 taps in one grid, stored pixel-shuffled -- 2.25 taps per output on average, not 9.
+ *   up (conv3x3(nearest2x(src)), src Hs x Ws >= 1; dY [n_img, 2 Hs, 2 Ws, Cout] -> dX [n_img, Hs, Ws, Cin]):
+ *     dX[u, v] = sum_{r,c=0..3} G[r][c]^T dY[2u-1+r, 2v-1+c] with the rows of G from the rows of W: w[2], w[1] + w[2], w[0] + w[1], w[0] (columns
+ *     likewise) -- the transpose of the fold of fmc_conv3x3_upfold_pack_weight, summed in fp32 in the same order and rounded to bf16 once: 16 taps
+ *     per output against 36 of a full-resolution convolution followed by a 2x2 sum.
+ * `tile`: 0 = the launcher's choice by how many tiles fill the chip (what *_bwd_tile returns for the shape on the current device); down 1 / 2 / 3 = 32 x 64,
+ * 16 x 64, 16 x 32 (pixels x input channels) per wave; up 1 = 32 x 64 with all 16 taps per wave, 2 = the four rows of G on the four waves of a workgroup,
+ * summed in a fixed order.  Every choice computes every shape of the domain; another value is FMC_E_SHAPE.
+ * *_pack_weight writes `dst` = *_packed_bytes (9 resp. 16 x Cin x Cout x 2) in MFMA fragment order, once per weight version; the launches allocate nothing,
+ * use no atomics and no workspace (bit-reproducible) and never read outside dY.  Anything outside the domain: FMC_E_SHAPE (ask *_supported). */
+int fmc_conv3x3_down_bwd_supported(int n_img, int H, int W, int Cin, int Cout);
+int64_t fmc_conv3x3_down_bwd_packed_bytes(int Cin, int Cout);
+int fmc_conv3x3_down_bwd_pack_weight(const void* w, void* dst, int Cin, int Cout, void* stream);
+int fmc_conv3x3_down_bwd_tile(int n_img, int H, int W, int Cin, int Cout);
+int fmc_conv3x3_down_bwd_bf16(const void* dy, const void* w_packed, void* dx, int n_img, int H, int W, int Cin, int Cout, int tile, void* stream);
+int fmc_conv3x3_up_bwd_supported(int n_img, int Hs, int Ws, int Cin, int Cout);
+int64_t fmc_conv3x3_up_bwd_packed_bytes(int Cin, int Cout);
+int fmc_conv3x3_up_bwd_pack_weight(const void* w, void* dst, int Cin, int Cout, void* stream);
+int fmc_conv3x3_up_bwd_tile(int n_img, int Hs, int Ws, int Cin, int Cout);
+int fmc_conv3x3_up_bwd_bf16(const void* dy, const void* w_packed, void* dx, int n_img, int Hs, int Ws, int Cin, int Cout, int tile, void* stream);
 int fmc_groupnorm_coef(const float* partials, int part_splits, const float* gamma, const float* beta, float* coef, float* stats, int N, int HW,
                        int C, int G, float eps, void* stream);
 

@@ -83,6 +83,16 @@ SIGNATURES = {
     "fmc_conv3x3_halo_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fmc_conv3x3_halo4_fold_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fmc_conv3x3_halo4_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "fmc_conv3x3_down_bwd_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_down_bwd_packed_bytes": (c_int64, [c_int, c_int]),
+    "fmc_conv3x3_down_bwd_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_down_bwd_tile": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_down_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_up_bwd_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_up_bwd_packed_bytes": (c_int64, [c_int, c_int]),
+    "fmc_conv3x3_up_bwd_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_up_bwd_tile": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_up_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fmc_linear4_supported": (c_int, [c_int64, c_int, c_int, c_int64]),
     "fmc_vendor_linear_candidates": (c_int, [c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int]),
     "fmc_vendor_linear_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p,

@@ -2671,6 +2671,156 @@ def conv3x3_frozen(x, weight_cl, bias, temb=None, residual=None, temb_div: int =
     return _Conv3x3Frozen.apply(x, weight_cl, bias, temb, residual, temb_div)
 
 
+# the resampling convolutions and conv_out under a gradient (frozen filter): forward = the no-grad front-end, backward-data = csrc/conv_resample_bwd.hip
+# (stride 2: 1 / 2 / 2 / 4 taps per output parity; upsample: 16 taps of the transposed fold) resp. the stride-1 kernel on zero-padded channels
+RESAMPLE_BWD = os.environ.get("FMC_RESAMPLE_BWD", "1") != "0"     # A/B switch: 0 = F.interpolate / F.conv2d and torch's autograd, as before
+resample_bwd_calls = {"down": 0, "up": 0, "edge": 0}               # backward launches (tests assert on these)
+
+
+def conv3x3_down_bwd_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    """`h x w`: the forward's input (= dX)."""
+    return bool(_lib.load().fmc_conv3x3_down_bwd_supported(n, h, w, cin, cout))
+
+
+def conv3x3_up_bwd_supported(n: int, hs: int, ws: int, cin: int, cout: int) -> bool:
+    return bool(_lib.load().fmc_conv3x3_up_bwd_supported(n, hs, ws, cin, cout))
+
+
+def _w_resample_bwd_packed(weight_cl: torch.Tensor, up: bool) -> torch.Tensor:
+    """Channels-last 3x3 filter -> the fragment order of the backward-data kernels (stride 2: the 9 taps; upsample: the 16 taps of G, folded in fp32
+    and rounded once), cached on the weight per version like the other packs: a captured step never packs."""
+    return _w_packed(weight_cl, "up_bwd" if up else "down_bwd", 16 if up else 9,
+                     "fmc_conv3x3_up_bwd_pack_weight" if up else "fmc_conv3x3_down_bwd_pack_weight")
+
+
+def conv3x3_down_bwd(dy_nhwc: torch.Tensor, w_packed: torch.Tensor, cin: int, out: Optional[torch.Tensor] = None, tile: int = 0) -> torch.Tensor:
+    """dX `[N, 2 Ho, 2 Wo, Cin]` of the 3x3 / stride-2 / pad-1 convolution from dY `[N, Ho, Wo, Cout]` (contiguous bf16) and the packed filter.
+    `tile`: 0 = the launcher's choice (`fmc_conv3x3_down_bwd_tile`), 1 / 2 / 3 = that tile whatever the shape (tests, A/B)."""
+    _dev(dy_nhwc, w_packed, out)
+    n, ho, wo, cout = dy_nhwc.shape
+    assert dy_nhwc.is_contiguous() and dy_nhwc.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16 and w_packed.numel() == 9 * cin * cout
+    if out is None:
+        out = torch.empty(n, 2 * ho, 2 * wo, cin, dtype=dy_nhwc.dtype, device=dy_nhwc.device)
+    assert out.is_contiguous() and out.shape == (n, 2 * ho, 2 * wo, cin) and out.dtype == dy_nhwc.dtype
+    resample_bwd_calls["down"] += 1
+    if call_log is not None:
+        call_log.append(("conv_down_bwd", (n, 2 * ho, 2 * wo, cin, cout), 2.0 * n * ho * wo * 9 * cin * cout))
+    _lib.check(_lib.load().fmc_conv3x3_down_bwd_bf16(dy_nhwc.data_ptr(), w_packed.data_ptr(), out.data_ptr(), n, 2 * ho, 2 * wo, cin, cout, tile,
+                                                     _stream()),
+               "fmc_conv3x3_down_bwd_bf16")
+    return out
+
+
+def conv3x3_up_bwd(dy_nhwc: torch.Tensor, w_packed: torch.Tensor, cin: int, out: Optional[torch.Tensor] = None, tile: int = 0) -> torch.Tensor:
+    """dX `[N, Hs, Ws, Cin]` of conv3x3(nearest2x(x)) from dY `[N, 2 Hs, 2 Ws, Cout]` (contiguous bf16) and the packed folded filter.
+    `tile`: 0 = the launcher's choice (`fmc_conv3x3_up_bwd_tile`), 1 = unsplit, 2 = split over the rows of G."""
+    _dev(dy_nhwc, w_packed, out)
+    n, hd, wd, cout = dy_nhwc.shape
+    assert hd % 2 == 0 and wd % 2 == 0
+    hs, ws = hd // 2, wd // 2
+    assert dy_nhwc.is_contiguous() and dy_nhwc.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16 and w_packed.numel() == 16 * cin * cout
+    if out is None:
+        out = torch.empty(n, hs, ws, cin, dtype=dy_nhwc.dtype, device=dy_nhwc.device)
+    assert out.is_contiguous() and out.shape == (n, hs, ws, cin) and out.dtype == dy_nhwc.dtype
+    resample_bwd_calls["up"] += 1
+    if call_log is not None:
+        call_log.append(("conv_up_bwd", (n, hs, ws, cin, cout), 2.0 * n * hs * ws * 16 * cin * cout))
+    _lib.check(_lib.load().fmc_conv3x3_up_bwd_bf16(dy_nhwc.data_ptr(), w_packed.data_ptr(), out.data_ptr(), n, hs, ws, cin, cout, tile, _stream()),
+               "fmc_conv3x3_up_bwd_bf16")
+    return out
+
+
+def _nhwc(t: torch.Tensor) -> torch.Tensor:
+    """Logical NCHW -> a contiguous `[N, H, W, C]` tensor (a view when the storage is channels-last already)."""
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+class _Conv3x3DownFrozen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight_cl, bias):
+        ctx.save_for_backward(weight_cl)
+        with torch.no_grad():
+            return conv3x3(x, weight_cl, bias, None, None, (2, 2), (1, 1))
+
+    @staticmethod
+    def backward(ctx, dy):
+        (weight_cl,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        with torch.no_grad():
+            dx = conv3x3_down_bwd(_nhwc(dy), _w_resample_bwd_packed(weight_cl, False), weight_cl.shape[1])
+        return dx.permute(0, 3, 1, 2), None, None
+
+
+class _Conv3x3UpFrozen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight_cl, bias):
+        ctx.save_for_backward(weight_cl)
+        with torch.no_grad():
+            return conv3x3(x, weight_cl, bias, None, None, (1, 1), (1, 1), 1, True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (weight_cl,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        with torch.no_grad():
+            dx = conv3x3_up_bwd(_nhwc(dy), _w_resample_bwd_packed(weight_cl, True), weight_cl.shape[1])
+        return dx.permute(0, 3, 1, 2), None, None
+
+
+def conv3x3_down_frozen(x, weight_cl, bias):
+    """3x3 / stride 2 / pad 1 conv (even H, W) with frozen filter, differentiable w.r.t. x: nothing is saved but the weight."""
+    return _Conv3x3DownFrozen.apply(x, weight_cl, bias)
+
+
+def conv3x3_up_frozen(x, weight_cl, bias):
+    """conv3x3(nearest2x(x)) with frozen filter, differentiable w.r.t. x.  The forward may take the folded arms: they are the exact adjoint
+    partner of the backward's G (the same fp32 sums, rounded once)."""
+    return _Conv3x3UpFrozen.apply(x, weight_cl, bias)
+
+
+def _edge_flipped_filter(weight: torch.Tensor) -> torch.Tensor:
+    """Backward-data filter of a thin convolution (`Cout % 64 != 0`, conv_out 320 -> 4): `[Cin, Cout padded to 64, 3, 3]` with
+    `W'[ci, co, ky, kx] = W[co, ci, 2-ky, 2-kx]` and zero filters for the pad, channels-last; cached on the weight like `_flipped_filter`."""
+    def build():
+        cout, cin = weight.shape[:2]
+        wf = torch.zeros(cin, (cout + 63) // 64 * 64, 3, 3, dtype=weight.dtype, device=weight.device)
+        wf[:, :cout] = weight.detach().flip(2, 3).permute(1, 0, 2, 3)
+        return wf.contiguous(memory_format=torch.channels_last)
+    return derived_on_owner(weight, "_fmc_flipped", "edge", build)
+
+
+class _Conv3x3EdgeFrozen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, fwd):
+        ctx.save_for_backward(weight)
+        with torch.no_grad():
+            return fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (weight,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        with torch.no_grad():
+            wf = _edge_flipped_filter(weight)
+            n, cout, h, w = dy.shape
+            # (the zero fill and the scatter of a 64-channel dY, 16 x conv_out's real gradient, are what this route costs: forward + backward of
+            #  conv_out comes out level with F.conv2d under autograd at 32 x 48, profiles/resample_backward.md)
+            dyp = torch.zeros(n, h, w, wf.shape[1], dtype=dy.dtype, device=dy.device)
+            dyp[..., :cout] = dy.permute(0, 2, 3, 1)
+            resample_bwd_calls["edge"] += 1
+            dx = conv3x3(dyp.permute(0, 3, 1, 2), wf, None, own_only=True)
+        return dx, None, None
+
+
+def conv3x3_edge_frozen(x, weight, fwd):
+    """A thin 3x3 / stride 1 / pad 1 conv (conv_out) with frozen filter, differentiable w.r.t. x.  `fwd(x)`: the no-grad forward, whatever
+    `Conv2d.forward` takes for the shape without a gradient (`Conv2d.padded_conv3x3` where Cout is no multiple of 8); backward-data = the stride-1 kernel on dY zero-padded to 64 channels with the flipped padded filter."""
+    return _Conv3x3EdgeFrozen.apply(x, weight, fwd)
+
+
 def _transposed_weight(weight: torch.Tensor) -> torch.Tensor:
     """`W^T [K, N]` contiguous: the backward-data GEMM `dX = dY @ W` is `fmc_linear_bf16(dY, W^T)` -- both operands
     reduction-contiguous.  Cached on the tensor that owns the storage (`derived_on_owner`): frozen weights reached through a fresh view

@@ -172,6 +172,8 @@ PADDED_EDGE_CONVS = os.environ.get("FMC_PADDED_EDGE_CONVS", "1") != "0"      # A
 class Conv2d(nn.Conv2d):
     """MIOpen conv on channels-last storage; 1x1 stride-1 convs run as a token GEMM (hipBLASLt)."""
 
+    frozen_resample_bwd = True      # a frozen stride-2 / upsample / thin convolution under a gradient takes the own backward-data (the VAE opts out)
+
     def forward(self, x: torch.Tensor, scale: float = 1.0, temb: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, temb_div: int = 1, upsample: bool = False,
                 x2: Optional[torch.Tensor] = None, emit_gn: bool = False) -> torch.Tensor:
@@ -203,6 +205,22 @@ class Conv2d(nn.Conv2d):
                 and self.weight.requires_grad):
             # trainable filter under bf16 autocast (OMC Adapter / camera encoder): forward + backward-data on the gfx950 kernel
             return K.conv3x3_trainable(x, self.weight, self.bias)
+        if (needs_grad and K.RESAMPLE_BWD and self.frozen_resample_bwd and temb is None and residual is None and self.kernel_size == (3, 3) and self.padding == (1, 1)
+                and self.dilation == (1, 1) and self.groups == 1 and x.is_cuda and x.dtype == torch.bfloat16 and self.weight.dtype == torch.bfloat16
+                and not self.weight.requires_grad and (self.bias is None or not self.bias.requires_grad) and self.in_channels % 64 == 0):
+            # the frozen resampling convolutions and conv_out, activation gradient only: forward as without a gradient, backward-data on the
+            # gfx950 kernels (csrc/conv_resample_bwd.hip; conv_out: the stride-1 kernel on zero-padded channels) -- no vendor convolution in a step
+            n, c, h, w = x.shape
+            if (self.stride == (2, 2) and not upsample and self.out_channels % 64 == 0
+                    and K.conv3x3_down_bwd_supported(n, h, w, self.in_channels, self.out_channels)):
+                return K.conv3x3_down_frozen(x, self._weight_cl(), self.bias)
+            if (self.stride == (1, 1) and upsample and self.out_channels % 64 == 0
+                    and K.conv3x3_up_bwd_supported(n, h, w, self.in_channels, self.out_channels)):
+                return K.conv3x3_up_frozen(x, self._weight_cl(), self.bias)
+            if self.stride == (1, 1) and not upsample and self.out_channels % 64 and PADDED_EDGE_CONVS:
+                # (the forward is the no-grad forward of the shape, bit for bit: the padded route below where Cout % 8, the front-end otherwise)
+                fwd = self.padded_conv3x3 if self.out_channels % 8 else (lambda t: K.conv3x3(t, self._weight_cl(), self.bias))
+                return K.conv3x3_edge_frozen(x, self.weight, fwd)
         if (self.kernel_size == (3, 3) and self.dilation == (1, 1) and self.groups == 1 and x.is_cuda and not needs_grad
                 and self.stride == (1, 1) and self.padding == (1, 1) and x.dtype == torch.bfloat16 and self.weight.dtype == torch.bfloat16
                 and (self.in_channels % 64 or self.out_channels % 8) and temb is None and residual is None and not upsample and PADDED_EDGE_CONVS):

@@ -76,6 +76,8 @@ class _UpDecoderBlock(nn.Module):
         self.resnets = nn.ModuleList([ResnetBlock2D(in_channels=cin if i == 0 else cout, out_channels=cout, temb_channels=None,
                                                     groups=groups, eps=eps) for i in range(layers)])
         self.upsamplers = nn.ModuleList([Upsample2D(cout, use_conv=True, out_channels=cout)]) if add_upsample else None
+        if add_upsample:
+            self.upsamplers[0].conv.frozen_resample_bwd = False        # under a gradient the VAE stays on F.conv2d, like its edge convolutions
 
     def forward(self, x):
         for r in self.resnets:
