@@ -176,6 +176,31 @@ int fmc_feature_add_fwd(const void* h, const void* t, void* out, int64_t n_elems
 int fmc_cfg_ddim_step(const void* eps_uc, const float* x, float* x_out, int64_t n, int has_uncond,
                       float guidance, float alpha_t, float alpha_prev, int dtype, void* stream);
 
+/* CFG combine + one step of any sampler whose update is linear in (x, eps, history, noise), fused, plus the next step's model
+ * input (pipeline_animation_cm_om.py:696-720 with the schedulers the reference's pipelines are typed for: DDIM with eta /
+ * clipping / v-prediction, Euler, Euler-ancestral, DPM-Solver++ multistep).  Per element i < n, fp32 arithmetic:
+ *     e  = has_uncond ? eu + g (ec - eu) : e0
+ *     m  = m_x x + m_e e ;  if (m_clamp > 0) m = clamp(m, -m_clamp, +m_clamp)
+ *     x' = c_x x + c_e e + c_m m + sum_{j < n_hist} c_h[j] hist[j] + (noise ? c_n noise : 0)
+ *     x_out[i] = x' ;  m_out[i] = m ;  x_in[r][i] = (in_dtype)(in_scale x'),  r < in_reps
+ *   eps_uc : [2, n] (dtype) (uncond, cond) with has_uncond, else [1, n];   noise : [n] (dtype) or NULL
+ *   x, x_out : [n] fp32, x_out may alias x;   hist0..2 : [n] fp32, the first n_hist (0..3) are read
+ *   m_out : [n] fp32 or NULL, may alias any hist[j];   x_in : [in_reps, n] (in_dtype), in_reps 0..2, aliases nothing
+ * Pointers need the alignment of their element only: a stream that is not 16-byte aligned where x is (the conditional half
+ * of a bf16 eps_uc at odd n) moves element by element.  fmc_sampler_step_elems_per_trip(): elements one trip of the
+ * grid-stride loop covers once the grid is at its cap. */
+typedef struct fmc_sampler_coef {
+    float g;                 /* guidance scale */
+    float m_x, m_e, m_clamp; /* the converted model output m (x0 prediction), and its clamp (<= 0: none) */
+    float c_x, c_e, c_m, c_n;
+    float c_h[3];
+    float in_scale;
+} fmc_sampler_coef;
+int64_t fmc_sampler_step_elems_per_trip(void);
+int fmc_sampler_step(const void* eps_uc, const float* x, const void* noise, const float* hist0, const float* hist1,
+                     const float* hist2, float* x_out, float* m_out, void* x_in, int64_t n, int has_uncond, int n_hist,
+                     int in_reps, fmc_sampler_coef coef, int dtype, int in_dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue:  out = alpha * (x @ w^T + bias) + residual      (epilogue 0)
  *                                      out = (x @ wa^T + ba) * gelu_erf(x @ wg^T + bg)  (epilogue 1, GEGLU)

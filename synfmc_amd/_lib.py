@@ -16,6 +16,12 @@ FMC_BF16, FMC_F32 = 0, 1
 
 _ERRORS = {-1: ValueError, -2: TypeError, -3: ValueError, -4: RuntimeError, -5: ValueError}
 
+
+class SamplerCoef(ctypes.Structure):
+    """`fmc_sampler_coef` of include/fmc_hip.h: the coefficients of one `fmc_sampler_step`, passed by value."""
+    _fields_ = [("g", c_float), ("m_x", c_float), ("m_e", c_float), ("m_clamp", c_float), ("c_x", c_float), ("c_e", c_float),
+                ("c_m", c_float), ("c_n", c_float), ("c_h", c_float * 3), ("in_scale", c_float)]
+
 # name -> (restype, argtypes); mirrors include/fmc_hip.h one to one
 SIGNATURES = {
     "fmc_version": (c_int, []),
@@ -44,6 +50,8 @@ SIGNATURES = {
     "fmc_feature_add_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "fmc_cfg_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int,
                                   c_void_p]),
+    "fmc_sampler_step_elems_per_trip": (c_int64, []),
+    "fmc_sampler_step": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_int, c_int, SamplerCoef, c_int, c_int, c_void_p]),
     "fmc_linear_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                 c_int64, c_int64, c_float, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                 c_void_p, c_void_p]),

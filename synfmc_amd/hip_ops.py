@@ -10,6 +10,7 @@ Layout: activations are channels-last.  `[N, S, C]` "tokens" are what the kernel
 from __future__ import annotations
 
 import atexit
+import ctypes
 import math
 import os
 from typing import Optional, Tuple
@@ -892,6 +893,42 @@ def cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, guidance: float, alpha_t: 
                                              float(guidance), float(alpha_t), float(alpha_prev), _dt(eps), _stream()),
                "fmc_cfg_ddim_step")
     return out
+
+
+def sampler_step_elems_per_trip() -> int:
+    return int(_lib.load().fmc_sampler_step_elems_per_trip())
+
+
+def sampler_step(eps: torch.Tensor, x: torch.Tensor, *, guidance: float = 1.0, has_uncond: bool = False, m_x: float = 0.0,
+                 m_e: float = 0.0, m_clamp: float = 0.0, c_x: float = 1.0, c_e: float = 0.0, c_m: float = 0.0, c_n: float = 0.0,
+                 c_h=(), hist=(), noise: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                 m_out: Optional[torch.Tensor] = None, x_in: Optional[torch.Tensor] = None, in_scale: float = 1.0) -> torch.Tensor:
+    """Fused classifier-free-guidance combine + one sampler step (`fmc_sampler_step`; the formula is in include/fmc_hip.h).
+    eps `[2B, ...]` (uncond || cond) or `[B, ...]`, x fp32 latents `[B, ...]`, `hist` up to three fp32 tensors like x with their
+    coefficients `c_h`, `noise` like x in eps's dtype.  `x_out` may be x, `m_out` may be one of `hist`; `x_in` `[B or 2B, ...]`
+    receives `in_scale * x'` in its own dtype (the next model input).  Returns `x_out` (a new tensor when not given)."""
+    _dev(eps, x, noise, x_out, m_out, x_in, *hist)
+    n = x.numel()
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == (2 * n if has_uncond else n)
+    assert len(hist) == len(c_h) <= 3 and all(h.dtype == torch.float32 and h.is_contiguous() and h.numel() == n for h in hist)
+    assert noise is None or (noise.dtype == eps.dtype and noise.is_contiguous() and noise.numel() == n)
+    assert m_out is None or (m_out.dtype == torch.float32 and m_out.is_contiguous() and m_out.numel() == n)
+    if x_out is None:
+        x_out = torch.empty_like(x)
+    assert x_out.dtype == torch.float32 and x_out.is_contiguous() and x_out.numel() == n
+    in_reps = 0
+    if x_in is not None:
+        assert x_in.is_contiguous() and x_in.numel() in (n, 2 * n)
+        in_reps = x_in.numel() // n
+    coef = _lib.SamplerCoef(float(guidance), float(m_x), float(m_e), float(m_clamp), float(c_x), float(c_e), float(c_m), float(c_n),
+                            (ctypes.c_float * 3)(*[float(c) for c in c_h]), float(in_scale))
+    hp = [h.data_ptr() for h in hist] + [None] * (3 - len(hist))
+    _log_call("sampler_step", (n, int(has_uncond), len(hist), noise is not None, in_reps), 0.0)
+    _lib.check(_lib.load().fmc_sampler_step(eps.data_ptr(), x.data_ptr(), _p(noise), hp[0], hp[1], hp[2], x_out.data_ptr(), _p(m_out),
+                                            _p(x_in), n, int(has_uncond), len(hist), in_reps, coef, _dt(eps),
+                                            _dt(x_in) if x_in is not None else _dt(eps), _stream()), "fmc_sampler_step")
+    return x_out
 
 
 # --------------------------------------------------------------------------------------------

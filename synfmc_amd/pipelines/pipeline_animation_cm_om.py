@@ -12,7 +12,9 @@ What changes under the hood (one denoising step = one U-Net forward at CFG batch
   * OMC features are NOT zero-padded for the unconditional half (reference :671-676): `fmc_feature_add_fwd` simply
     skips that half;
   * `omcm_min_step` gating (:682-685) picks between two captured HIP graphs (with / without OMC features);
-  * CFG combine + DDIM update are one fused kernel on fp32 latents (:711-720);
+  * CFG combine + DDIM update are one fused kernel on fp32 latents (:711-720); with any other sampler of `synfmc_amd.schedulers` (DDIM
+    with eta / clipping / v-prediction, Euler, Euler-ancestral, DPM-Solver++) the step is `fmc_sampler_step`, which also writes the next
+    step's model input, so the loop launches no `cat` and no cast; `eta` and `generator` reach the scheduler (:335-351);
   * the captured graphs are kept on the pipeline between calls: text, camera and OMC features are copied into the
     graph's static buffers per clip (and the per-clip Camera-Adapter pose terms recomputed in place), so a second clip
     of the same shape costs no warm-up and no capture.
@@ -40,12 +42,13 @@ class _GraphedUNet:
     """Captures `unet(x, t, text[, pose_feats, traj])` into a HIP graph whose inputs are static buffers owned here;
     `set_conditioning` refills them for a new clip, `__call__` replays with new latents / timestep."""
 
-    def __init__(self, unet, latents_shape, text, pose_feats, traj_feats, dtype, cfg_shared_input: bool = False):
+    def __init__(self, unet, latents_shape, text, pose_feats, traj_feats, dtype, cfg_shared_input: bool = False, t_float: bool = False):
         self.unet = unet
+        self.t_float = bool(t_float)                        # a timestep table with a fractional entry (Euler, linspace spacing): a float32 scalar
         self.cfg_shared_input = bool(cfg_shared_input)      # the caller feeds `cat([latents] * 2)`: the U-Net may compute the shared prefix once
         dev = text.device
         self.x = torch.zeros(latents_shape, dtype=dtype, device=dev)
-        self.t = torch.zeros((), dtype=torch.int64, device=dev)
+        self.t = torch.zeros((), dtype=torch.float32 if self.t_float else torch.int64, device=dev)
         own = lambda v: v.detach().clone(memory_format=torch.preserve_format)
         self.text = own(text if text.dtype == dtype else text.to(dtype))   # (model dtype: the U-Net then hands THIS buffer to its cross-attention layers)
         self.pose = None if pose_feats is None else [own(p) for p in pose_feats]
@@ -131,7 +134,7 @@ class _GraphedUNet:
 
     def __call__(self, x, t):
         self.x.copy_(x)
-        self.t.fill_(int(t))
+        self.t.fill_(float(t) if self.t_float else int(t))
         self.graph.replay()
         return self.out
 
@@ -164,7 +167,7 @@ class AnimationPipeline:
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler):
         from ..schedulers import coerce_scheduler
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
-        self.unet, self.scheduler = unet, coerce_scheduler(scheduler)       # accepts a diffusers.DDIMScheduler as well
+        self.unet, self.scheduler = unet, coerce_scheduler(scheduler)       # accepts a diffusers DDIM / Euler / Euler-ancestral / DPM-Solver++ scheduler as well
         self._runners = {}
 
     # ---- pieces outside the metric ------------------------------------------------------------------
@@ -225,8 +228,6 @@ class AnimationPipeline:
     # ---- shared machinery of the two loops -----------------------------------------------------------
     def _prologue(self, prompt, height, width, callback_steps, latents, num_videos_per_prompt, guidance_scale,
                   negative_prompt, prompt_embeds, device, eta):
-        if eta != 0.0:
-            raise NotImplementedError("eta > 0 is never used by FMC")
         unet = self.unet
         if hasattr(unet, "invalidate_text_conditioning"):
             unet.invalidate_text_conditioning()     # a new clip: no text k | v of the previous prompt survives (they are re-made once below / by the runner)
@@ -251,8 +252,9 @@ class AnimationPipeline:
         text = prompt_embeds.to(device=device, dtype=unet.dtype)
         return height, width, do_cfg, batch_size, text
 
-    def _runner(self, x_shape, text, pose_feats, traj, use_graph):
-        """The U-Net step as a callable `(x, t) -> eps`: a cached HIP graph (refilled with this clip's conditioning) or eager."""
+    def _runner(self, x_shape, text, pose_feats, traj, use_graph, t_float: bool = False):
+        """The U-Net step as a callable `(x, t) -> eps`: a cached HIP graph (refilled with this clip's conditioning) or eager.
+        `t_float`: the timestep table has a fractional entry, which has to reach the U-Net untruncated."""
         unet = self.unet
         shared = bool(getattr(self, "_cfg_shared", False)) and getattr(unet, "_accepts_cfg_shared_input", False)   # (a foreign U-Net never sees the keyword)
         skw = {"cfg_shared_input": True} if shared else {}
@@ -265,20 +267,39 @@ class AnimationPipeline:
                     kw["pose_embedding_features"] = pose_feats
                     if traj is not None or getattr(unet, "_pass_traj_none", False):    # (UNet3DConditionModelPoseCond takes no traj_features)
                         kw["traj_features"] = traj
-                return unet(x, torch.tensor(int(t), device=x.device), encoder_hidden_states=text, **skw, **kw).sample
+                tt = torch.tensor(float(t), dtype=torch.float32, device=x.device) if t_float else torch.tensor(int(t), device=x.device)
+                return unet(x, tt, encoder_hidden_states=text, **skw, **kw).sample
             return eager
         key = (tuple(x_shape), tuple(text.shape), unet.dtype, pose_feats is not None, traj is not None,
-               shared, _weights_version(unet))
+               shared, bool(t_float), _weights_version(unet))
         r = self._runners.get(key)
         if r is None:
             for k in [k for k in self._runners if k[:-1] == key[:-1]]:      # same shapes, stale weights: drop the graph
                 del self._runners[k]
-            r = _GraphedUNet(unet, x_shape, text, pose_feats, traj, unet.dtype, cfg_shared_input=shared)
+            r = _GraphedUNet(unet, x_shape, text, pose_feats, traj, unet.dtype, cfg_shared_input=shared, t_float=t_float)
             r.capture()
             self._runners[key] = r
         else:
             r.set_conditioning(text, pose_feats, traj)
         return r
+
+    def _sampler_path(self, eta, generator, timesteps, x_shape, latents, do_cfg):
+        """`(fused, t_float, step keywords, x_in)`.  Every configuration but the plain DDIM one steps through `fmc_sampler_step`, which
+        also writes the next model input (scaled, CFG-duplicated, in the model's dtype) into `x_in`: only the first input of a clip is
+        made by torch ops.  `eta` and `generator` go to the scheduler, which uses what its family takes (reference :335-351)."""
+        sch = self.scheduler
+        t_float = any(not float(t).is_integer() for t in timesteps)
+        if not (hasattr(sch, "fused_input") and sch.fused_input(eta)):
+            if eta != 0.0:
+                raise NotImplementedError(f"{type(sch).__name__} takes no eta")
+            return False, t_float, {}, None
+        x_in = torch.empty(x_shape, dtype=self.unet.dtype, device=latents.device)
+        if tuple(x_shape) == (latents.shape[0] * (2 if do_cfg else 1),) + tuple(latents.shape[1:]):
+            first = sch.scale_model_input(latents, timesteps[0])
+            x_in.copy_(torch.cat([first] * 2) if do_cfg else first)
+        else:
+            x_in = None                                     # sliding windows: the inputs are slices, made per window
+        return True, t_float, dict(eta=eta, generator=generator), x_in
 
     def _finish(self, latents, output_type, return_dict):
         if output_type == "latent":
@@ -312,10 +333,13 @@ class AnimationPipeline:
         latents = self.prepare_latents(batch_size * num_videos_per_prompt, unet.in_channels, video_length, height,
                                        width, text.dtype, device, generator, latents).contiguous()
         x_shape = (latents.shape[0] * (2 if do_cfg else 1), latents.shape[1], single) + tuple(latents.shape[3:])
-        run = self._runner(x_shape, text, None, None, use_graph)
+        fused, t_float, step_kw, x_in = self._sampler_path(eta, generator, timesteps, x_shape, latents, do_cfg)
+        run = self._runner(x_shape, text, None, None, use_graph, t_float)
         stride = single - multidiff_overlaps
         for i, t in enumerate(timesteps):
-            if multidiff_total_steps == 1:
+            if multidiff_total_steps == 1 and fused:
+                latents = self.scheduler.step_cfg(run(x_in, t), t, latents, guidance_scale, do_cfg, x_in=x_in, **step_kw)
+            elif multidiff_total_steps == 1:
                 x = torch.cat([latents] * 2) if do_cfg else latents
                 eps = run(x.to(unet.dtype), t)
                 latents = self.scheduler.step_cfg(eps, t, latents, guidance_scale, do_cfg)
@@ -325,6 +349,8 @@ class AnimationPipeline:
                 for w in range(multidiff_total_steps):
                     s0 = w * stride
                     part = latents[:, :, s0:s0 + single].contiguous()
+                    if fused:
+                        part = self.scheduler.scale_model_input(part, t)
                     x = torch.cat([part] * 2) if do_cfg else part
                     eps = run(x.to(unet.dtype), t).float()
                     if do_cfg:
@@ -332,7 +358,7 @@ class AnimationPipeline:
                         eps = eu + guidance_scale * (ec - eu)
                     full[:, :, s0:s0 + single] += eps
                     count[:, :, s0:s0 + single] += 1
-                latents = self.scheduler.step_cfg((full / count).contiguous(), t, latents, 1.0, False)
+                latents = self.scheduler.step_cfg((full / count).contiguous(), t, latents, 1.0, False, **step_kw)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         return self._finish(latents, output_type, return_dict)
@@ -389,6 +415,7 @@ class CameraObjCtrlPipeline(AnimationPipeline):
         omcm_min_step = kwargs.get("omcm_min_step", 0)
         x_shape = (latents.shape[0] * (2 if do_cfg else 1),) + tuple(latents.shape[1:])
         runs = {}
+        fused, t_float, step_kw, x_in = self._sampler_path(eta, generator, timesteps, x_shape, latents, do_cfg)
 
         for i, t in enumerate(timesteps):
             traj = traj_features
@@ -396,10 +423,13 @@ class CameraObjCtrlPipeline(AnimationPipeline):
                 traj = None
             key = traj is not None
             if key not in runs:
-                runs[key] = self._runner(x_shape, text, pose_feats, traj, use_graph)
-            x = torch.cat([latents] * 2) if do_cfg else latents
-            eps = runs[key](x.to(unet.dtype), t)
-            latents = self.scheduler.step_cfg(eps, t, latents, guidance_scale, do_cfg)
+                runs[key] = self._runner(x_shape, text, pose_feats, traj, use_graph, t_float)
+            if fused:
+                latents = self.scheduler.step_cfg(runs[key](x_in, t), t, latents, guidance_scale, do_cfg, x_in=x_in, **step_kw)
+            else:
+                x = torch.cat([latents] * 2) if do_cfg else latents
+                eps = runs[key](x.to(unet.dtype), t)
+                latents = self.scheduler.step_cfg(eps, t, latents, guidance_scale, do_cfg)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         return self._finish(latents, output_type, return_dict)

@@ -291,6 +291,18 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None) -> N
             t.copy_(buf)
 
 
+def training_target(noise_scheduler, latents, noise, timesteps):
+    """What the model's output is compared with (train_cam_obj_ctrl.py:870-875): the noise under epsilon prediction (the tensor
+    itself, untouched), `get_velocity` under v-prediction."""
+    cfg = getattr(noise_scheduler, "config", None)
+    kind = (cfg.get("prediction_type", "epsilon") if isinstance(cfg, dict) else getattr(cfg, "prediction_type", "epsilon"))
+    if kind == "epsilon":
+        return noise
+    if kind == "v_prediction":
+        return noise_scheduler.get_velocity(latents, noise, timesteps)
+    raise ValueError(f"Unknown prediction type {kind}")
+
+
 def stage3_forward_backward(pose_adaptor, noise_scheduler, latents, noise, timesteps, encoder_hidden_states,
                             plucker_embedding, traj_features_fn, obj_masks, sd_loss_weight=0.3, mask_loss_weight=1.0):
     """add_noise -> Adapter -> U-Net -> loss -> backward (train_cam_obj_ctrl.py:802-915); returns the detached loss."""
@@ -298,7 +310,8 @@ def stage3_forward_backward(pose_adaptor, noise_scheduler, latents, noise, times
     traj_features = traj_features_fn()
     model_pred = pose_adaptor(noisy_latents, timesteps, encoder_hidden_states=encoder_hidden_states,
                               pose_embedding=plucker_embedding, traj_features=traj_features)
-    loss = masked_mse_loss(model_pred, noise, obj_masks, sd_loss_weight, mask_loss_weight)
+    target = training_target(noise_scheduler, latents, noise, timesteps)
+    loss = masked_mse_loss(model_pred, target, obj_masks, sd_loss_weight, mask_loss_weight)
     loss.backward()
     return loss.detach()
 
@@ -594,7 +607,8 @@ def stage2_training_step(pose_adaptor, trainable: Iterable[torch.nn.Parameter], 
     noisy_latents = noise_scheduler.add_noise(latents, noise, timesteps)
     model_pred = pose_adaptor(noisy_latents, timesteps, encoder_hidden_states=encoder_hidden_states,
                               pose_embedding=plucker_embedding)
-    loss = masked_mse_loss(model_pred, noise, obj_masks, sd_loss_weight, mask_loss_weight, invert=True)
+    target = training_target(noise_scheduler, latents, noise, timesteps)
+    loss = masked_mse_loss(model_pred, target, obj_masks, sd_loss_weight, mask_loss_weight, invert=True)
     loss.backward()
     if reducer is not None:
         reducer.finish()
@@ -639,7 +653,8 @@ def stage1_training_step(unet, trainable: Iterable[torch.nn.Parameter], noise_sc
     loadable with `from_pretrained_2d`): per frame the arithmetic of the reference's `UNet2DConditionModel`.  Returns the loss."""
     noisy_latents = noise_scheduler.add_noise(latents, noise, timesteps)
     model_pred = unet(noisy_latents.unsqueeze(2), timesteps, encoder_hidden_states).sample.squeeze(2)
-    loss = F.mse_loss(model_pred.float(), noise.float(), reduction="mean")
+    target = training_target(noise_scheduler, latents, noise, timesteps)
+    loss = F.mse_loss(model_pred.float(), target.float(), reduction="mean")
     loss.backward()
     if reducer is not None:
         reducer.finish()
