@@ -444,6 +444,23 @@ int fmc_conv3x3_halo_tiles_per_image(int H, int W);
 int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb, const void* residual,
                           void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x,
                           const float* gn_coef, int gn_act, float* gn_partials, void* stream);
+/* Shortcut mode (inference): conv2 of diffusers' ResnetBlock2D with the block's 1x1 `conv_shortcut` in the same reduction (unet_blocks.py:306-317 with
+ * in_channels != out_channels): out = conv3x3(x) + w_sc . [xs | xs2] + bias + temb, one sum over K = 9 Cin + Cin_sc whose last Cin_sc channels are
+ * multiplied at the centre tap only -- no shortcut GEMM, no [M, Cout] round trip, the shortcut product is not rounded.  Plain convolution of ONE source
+ * (no GroupNorm operand path, no upsample, no residual).  xs [n_img, H, W, Cin_sc1] (+ xs2 [n_img, H, W, Cin_sc - Cin_sc1] | NULL), raw, read in place;
+ * both % 64 channels, 16-byte aligned, < 2 GiB.  w_packed = fmc_conv3x3_halo_sc_pack_weight(filter [Cout][3][3][Cin], w_sc [Cout][Cin_sc]):
+ * [Cout / tile_channels][(Cin / 64) * 18 + (Cin_sc / 64) * 2 sub-tiles][tile_channels rows][32], the 1x1 filter's sub-tiles [Cin_sc / 64][2 halves]
+ * behind the 3x3 ones, chunk-swizzled like them; tile_channels = 160 for fmc_conv3x3_halo_sc_bf16 (80: the 4-wave tile, packed but not launched yet).
+ * The shortcut's bias goes in as `temb` (one row, temb_img_div = n_img): bias + temb are summed in fp32.  gn_partials as fmc_conv3x3_halo_bf16. */
+int fmc_conv3x3_halo_sc_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1);
+int64_t fmc_conv3x3_halo_sc_packed_bytes(int Cin, int Cout, int Cin_sc);
+/* (host only, no launch) 16-byte chunk `chunk` of the packed filter = the eight elements from the returned index on of the 3x3 filter, or of
+ * w_sc when *from_shortcut: the pack kernel's index map. */
+int64_t fmc_conv3x3_halo_sc_pack_source(int64_t chunk, int Cin, int Cin_sc, int tile_channels, int* from_shortcut);
+int fmc_conv3x3_halo_sc_pack_weight(const void* w, const void* w_sc, void* dst, int Cin, int Cout, int Cin_sc, int tile_channels, void* stream);
+int fmc_conv3x3_halo_sc_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs, const void* xs2,
+                             int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div,
+                             float* gn_partials, void* stream);
 /* The same convolution for the SMALL feature maps (csrc/conv_halo4.hip): image width a multiple of 8; the image is cut into row blocks of 10 x 16
  * pixels (W % 16 == 0) or 5 x 8; a tile is 320 pixels = 2 / 8 row blocks x 80 output channels, 4 waves with software-pipelined fragment reads.  Arguments as
  * fmc_conv3x3_halo_bf16 without the GroupNorm operand path; Cout % 80 == 0; w_packed = fmc_conv3x3_halo4_pack_weight(filter);

@@ -77,6 +77,12 @@ SIGNATURES = {
     "fmc_conv3x3_halo_packed_bytes": (c_int64, [c_int, c_int]),
     "fmc_conv3x3_halo_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fmc_conv3x3_halo_tiles_per_image": (c_int, [c_int, c_int]),
+    "fmc_conv3x3_halo_sc_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_sc_packed_bytes": (c_int64, [c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_sc_pack_source": (c_int64, [c_int64, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "fmc_conv3x3_halo_sc_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_halo_sc_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "fmc_conv3x3_halo_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "fmc_conv3x3_halo4_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -43,6 +43,12 @@ struct CHParams : halo::Params {
     int tiles_y, tiles_x, tiles_n;
     int64_t x_bytes, x2_bytes, w_bytes;
 };
+// SC: the block's 1x1 shortcut as a centre-tap segment of the same reduction (see conv_halo_kernel)
+struct CHParamsSC : CHParams {
+    const bf16_t* xs; const bf16_t* xs2;    // shortcut input [n_img, H, W, cs1] (+ [n_img, H, W, cin_sc - cs1]), raw
+    int cs1, cin_sc;                        // both % 64 == 0
+    int64_t xs_bytes, xs2_bytes;
+};
 
 __device__ __forceinline__ float silu_fast(float z) { return z * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z)); }
 
@@ -52,6 +58,11 @@ constexpr int nh(int i) { return (i >= 0 && i <= 12 && (i & 1) == 0) ? 1 : 0; }
 // phase mode (PH): halo pieces requested in sub-tile i of a chunk of 8 sub-tiles: pieces 2 i, 2 i + 1 at LOAD(i), i = 0 .. 3, written at LOAD(i + 3)
 constexpr int nhp(int i) { return (i >= 0 && i <= 3) ? (i < 3 ? 2 : 1) : 0; }
 
+// shortcut mode (SC): the interior of a shortcut chunk is 320 pixels x 8 channel groups = NSCP pieces per thread; those of shortcut chunk 1 are
+// requested in sub-tile 16 of every 3x3 chunk (nothing is fetched before the last one: the counted waits do not depend on the chunk)
+constexpr int NSCP = 5;
+template <bool SC> constexpr int nreq(int i) { return nh(i) + (SC && i == 16 ? NSCP : 0); }
+
 // GN: 0 = plain convolution, 1 = operand silu(x * scale + shift), 2 = operand x * scale + shift (compile-time: the normalisation has to sit in
 // the SAME basic block as the MFMAs it is interleaved with)
 //
@@ -60,9 +71,18 @@ constexpr int nhp(int i) { return (i >= 0 && i <= 3) ? (i < 3 ? 2 : 1) : 0; }
 // (source zero-padded by one pixel; Wf = sums of the filter's rows / columns, fmc_conv3x3_halo_fold_pack_weight).  The kernel then tiles the
 // SOURCE pixels (the halo is that of a plain convolution at source resolution), the channel-tile index becomes (phase, channel tile), a 64-channel
 // chunk is 4 taps x 2 k-halves = 8 sub-tiles instead of 18 (2.25 x fewer MFMAs for the same outputs), and the epilogue stores pixel-shuffled.
-template <int GN, bool PH = false>
+//
+// SC: the SHORTCUT MODE of a ResnetBlock2D's second convolution.  conv2(a) + Ws . [xs | xs2] + b2 + bs is one reduction over K = 9 cin + cin_sc whose
+// last cin_sc channels are multiplied at the centre tap only: behind the cin / 64 chunks of 18 sub-tiles the loop walks cin_sc / 64 shortcut chunks
+// of 2 sub-tiles (centre tap x 2 k-halves) on the same accumulators, fragment addresses and W ring (the packed filter carries the 1x1 filter's
+// sub-tiles behind the 3x3 ones: conv_halo_sc_pack_kernel).  The shortcut product is never rounded, written or read back; the two biases meet in
+// the epilogue's bias + temb sum.  Staging: shortcut chunk 0 takes the place of "the next chunk" of the last 3x3 chunk; chunk k + 1's interior
+// pieces are requested in the second sub-tile of chunk k - 1 and written in the second sub-tile of chunk k into the buffer chunk k - 1 released
+// -- one sub-tile ahead of their first read, so that sub-tile drains its LDS operations in front of its first barrier.
+template <int GN, bool PH = false, bool SC = false>
 __global__ __launch_bounds__(512, 2)
-void conv_halo_kernel(const CHParams P) {
+void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
+    static_assert(!SC || (GN == 0 && !PH), "the shortcut mode is a plain 9-tap convolution");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,7 +107,10 @@ void conv_halo_kernel(const CHParams P) {
     const int tn1 = P.cout / BN;
     const int phase = PH ? tile_n / tn1 : 0, py = phase >> 1, px_ = phase & 1;      // (PH: W tiles are [phase][channel tile])
     const int n0 = (tile_n - phase * tn1) * BN;
-    const int nchunk = P.cin >> 6, nsub = nchunk * NS;
+    const int nchunk = P.cin >> 6;
+    int nsc = 0;                                             // (SC) shortcut chunks
+    if constexpr (SC) nsc = P.cin_sc >> 6;
+    const int nsub = nchunk * NS + 2 * nsc;
 
     // ---- halo staging: my seven (pixel, channel group) pieces --------------------------------------------------------------------------
     // block b = 8 j + wave holds halo pixels 8 b .. 8 b + 7 x 8 channel groups; lane = 8 g + p takes pixel p, channel group (p + g) & 7: the eight
@@ -111,7 +134,34 @@ void conv_halo_kernel(const CHParams P) {
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)P.w, 0, (int)P.w_bytes, 0x00020000);
     const int c2 = P.cin - P.c1;
     u32x4 hreg[2];
-    auto halo_load = [&](int j, int ch64, u32x4& dst) { dst = halo::piece_load(rsX, rsX2, P.c1, c2, h_pix[j], pg, ch64 * 64, ch64, nchunk); };
+    // (SC) chunk indices run on through the shortcut chunks: nchunk + k is chunk k of xs | xs2
+    __amdgpu_buffer_rsrc_t rsS = rsX, rsS2 = rsX;
+    int cs1 = 0, cs2 = 0;
+    if constexpr (SC) {
+        rsS = __builtin_amdgcn_make_buffer_rsrc((void*)P.xs, 0, (int)P.xs_bytes, 0x00020000);
+        rsS2 = __builtin_amdgcn_make_buffer_rsrc((void*)(P.xs2 ? P.xs2 : P.xs), 0, (int)(P.xs2 ? P.xs2_bytes : P.xs_bytes), 0x00020000);
+        cs1 = P.cs1; cs2 = P.cin_sc - P.cs1;
+    }
+    auto halo_load = [&](int j, int ch64, u32x4& dst) {
+        if constexpr (SC) {
+            const bool sc = ch64 >= nchunk;
+            const int k = sc ? ch64 - nchunk : ch64;
+            dst = halo::piece_load(sc ? rsS : rsX, sc ? rsS2 : rsX2, sc ? cs1 : P.c1, sc ? cs2 : c2, h_pix[j], pg, k * 64, k, sc ? nsc : nchunk);
+        } else {
+            dst = halo::piece_load(rsX, rsX2, P.c1, c2, h_pix[j], pg, ch64 * 64, ch64, nchunk);
+        }
+    };
+    // (SC) interior piece j of shortcut chunk k: tile pixel 64 j + 8 wave + pp = row 2 j + (wave >> 2), column 8 (wave & 3) + pp; rows past the image
+    // and chunks outside [0, nsc) fetch nothing
+    const int sc_row = wave >> 2;
+    const int sc_pix0 = (img * P.H + y0 + sc_row) * P.W + x0 + 8 * (wave & 3) + pp;
+    const int sc_lds = pg * PLANE + ((sc_row + 1) * HWID + 8 * (wave & 3) + pp + 1) * 16;      // + j * 2 * HWID * 16 (+ buffer)
+    u32x4 hsc[NSCP];
+    auto sc_load = [&](int j, int k, u32x4& dst) {
+        const int hp = (k >= 0 && y0 + sc_row + 2 * j < P.H) ? sc_pix0 + 2 * j * P.W : -1;
+        dst = halo::piece_load(rsS, rsS2, cs1, cs2, hp, pg, k * 64, k, nsc);
+    };
+    auto sc_store = [&](int j, int buf, const u32x4& v) { *reinterpret_cast<u32x4*>(smem_raw + buf * HALO + sc_lds + j * (2 * HWID * 16)) = v; };
     // GroupNorm + SiLU of one staged piece, registers only (runs INSIDE an MFMA phase: its ~64 VALU instructions fill the issue slots between
     // the 25 matrix instructions instead of lengthening a LOAD phase); the 16 coefficients come from LDS ([64 channels][scale, shift] per chunk)
     auto halo_transform = [&](int j, int coefbuf, const u32x4& raw) -> u32x4 {
@@ -268,10 +318,14 @@ void conv_halo_kernel(const CHParams P) {
                 // 3. requests: one halo piece of the next chunk (even sub-tiles 0 .. 12), the coefficient of chunk c + 2, W sub-tile s + 3
                 if constexpr (nh(i) == 1) halo_load(i / 2, c + 1, hreg[(i / 2) & 1]);
                 if constexpr (i == 13) coef_next = coef_fetch(c + 2);
+                if constexpr (SC && i == 16) {
+#pragma unroll
+                    for (int j = 0; j < NSCP; ++j) sc_load(j, c + 2 - nchunk, hsc[j]);
+                }
                 w_issue(cls);
                 // 4. counted wait: W sub-tile s + 1 (requested two LOADs ago) and everything older has landed
                 {
-                    constexpr int extra = nh(i - 1) + nh(i) + (i == 13 || i == 14 ? 1 : 0);
+                    constexpr int extra = nreq<SC>(i - 1) + nreq<SC>(i) + (i == 13 || i == 14 ? 1 : 0);
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NW + extra) : "memory");
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -301,6 +355,60 @@ void conv_halo_kernel(const CHParams P) {
             sub(IC<6>{}); sub(IC<7>{}); sub(IC<8>{}); sub(IC<9>{}); sub(IC<10>{}); sub(IC<11>{});
             sub(IC<12>{}); sub(IC<13>{}); sub(IC<14>{}); sub(IC<15>{}); sub(IC<16>{}); sub(IC<17>{});
             cbuf = nbuf;
+        }
+        if constexpr (SC) {
+            for (int k = 0; k < nsc; ++k) {
+                const int abase = cbuf * HALO, nbuf = cbuf ^ 1;
+                auto subs = [&](auto ic) {
+                    constexpr int hk = decltype(ic)::value;
+                    constexpr int aimm = hk * 4 * PLANE + (HWID + 1) * 16;      // the centre tap
+                    // 1. (second sub-tile) chunk k + 1's pieces, requested two sub-tiles ago: only the two W requests behind them may be outstanding.
+                    //    nbuf was last read two sub-tiles ago
+                    if constexpr (hk == 1) {
+                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NW) : "memory");
+#pragma unroll
+                        for (int j = 0; j < NSCP; ++j) sc_store(j, nbuf, hsc[j]);
+                    }
+                    {
+                        const unsigned char* Wp = smem_raw + wfrag + rd_slot * WSUB;
+#pragma unroll
+                        for (int nb = 0; nb < 5; ++nb) wf[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(Wp + nb * 1024));
+#pragma unroll
+                        for (int mb = 0; mb < 5; ++mb)
+                            af[mb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(smem_raw + abase + afrag[mb] + aimm));
+                        rd_slot = rd_slot + 1 == NBW ? 0 : rd_slot + 1;
+                    }
+                    if constexpr (hk == 1) {
+#pragma unroll
+                        for (int j = 0; j < NSCP; ++j) sc_load(j, k + 2, hsc[j]);
+                    }
+                    w_issue(cls);
+                    // 2. counted wait: W sub-tile s + 1 and everything older has landed.  First sub-tile: the pieces of the sub-tile before stay in flight
+                    //    (chunk 0 follows sub-tile 17 of a 3x3 chunk, which requested none).  Second sub-tile: its stores are read one sub-tile on, so they
+                    //    (and the fragment reads) drain in front of the barrier
+                    if constexpr (hk == 0) {
+                        if (k == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NW) : "memory");
+                        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NW + NSCP) : "memory");
+                    } else {
+                        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * NW + NSCP) : "memory");
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                    for (int mb = 0; mb < 5; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < 5; ++nb)
+                            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nb], af[mb], acc[mb][nb], 0, 0, 0);
+                    __builtin_amdgcn_s_setprio(0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                subs(IC<0>{}); subs(IC<1>{});
+                cbuf = nbuf;
+            }
         }
     };
     if (clsA) main_loop(std::true_type{}); else main_loop(std::false_type{});
@@ -439,6 +547,18 @@ __global__ __launch_bounds__(256) void conv_halo_pack_kernel(const bf16_t* __res
     }
 }
 
+// ---- shortcut-mode filter: the 3x3 filter in the order above and, behind it in every channel tile, the 1x1 shortcut filter [Cout][Cin_sc] as
+// [Cin_sc / 64][2 halves][BN rows][32] with the same chunk swizzle: [Cout / BN][(Cin / 64) * 18 + (Cin_sc / 64) * 2 sub-tiles][BN rows][32] ------------------
+__global__ __launch_bounds__(256) void conv_halo_sc_pack_kernel(const bf16_t* __restrict__ w, const bf16_t* __restrict__ wsc, bf16_t* __restrict__ dst,
+                                                                int cout, int cin, int cin_sc, int BN) {
+    const int64_t total = (int64_t)cout * (9 * cin + cin_sc) / 8;      // 16-byte chunks
+    for (int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (int64_t)gridDim.x * blockDim.x) {
+        int from_sc;
+        const int64_t src = halo::sc_pack_source(id, cin, cin_sc, BN, &from_sc);
+        *reinterpret_cast<u32x4*>(dst + id * 8) = *reinterpret_cast<const u32x4*>((from_sc ? wsc : w) + src);
+    }
+}
+
 // ---- phase-mode filter: fold + pack in one pass.  [Cout][3][3][Cin] -> [4 phases (py, px)][Cout / BN][Cin / 64][4 taps (a, b)][2 halves][BN rows][32],
 // chunk-swizzled as above.  Wf[py][px][a][b] = sum of w[ky][kx] over ky in R(py, a), kx in R(px, b) with R(0, 0) = {0}, R(0, 1) = {1, 2},
 // R(1, 0) = {0, 1}, R(1, 1) = {2}: the filter rows / columns that fall on the same source pixel.  Summed in fp32 (fixed order), rounded to bf16 once. ----
@@ -548,6 +668,59 @@ extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, co
     else if (gn_act) fmc_launch<conv_halo_kernel<1>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     else fmc_launch<conv_halo_kernel<2>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo_bf16");
+    return 0;
+}
+
+// ---- shortcut mode: a ResnetBlock2D's conv2 with the block's 1x1 shortcut in the same reduction (see conv_halo_kernel) ------------------------------
+void halo::pack_filter_sc(const bf16_t* w, const bf16_t* w_sc, bf16_t* dst, int Cin, int Cout, int Cin_sc, int bn, hipStream_t st) {
+    const int64_t chunks = (int64_t)Cout * (9 * Cin + Cin_sc) / 8;
+    const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
+    hipLaunchKernelGGL(conv_halo_sc_pack_kernel, dim3(grid), dim3(256), 0, st, w, w_sc, dst, Cout, Cin, Cin_sc, bn);
+}
+
+extern "C" int64_t fmc_conv3x3_halo_sc_packed_bytes(int Cin, int Cout, int Cin_sc) { return (int64_t)Cout * (9 * Cin + Cin_sc) * 2; }
+
+extern "C" int fmc_conv3x3_halo_sc_pack_weight(const void* w, const void* w_sc, void* dst, int Cin, int Cout, int Cin_sc, int tile_channels, void* stream) {
+    if (!w || !w_sc || !dst) FMC_FAIL(FMC_E_NULL, "conv3x3_halo_sc_pack_weight: NULL pointer");
+    if ((tile_channels != 80 && tile_channels != 160) || Cin < 64 || Cin % 64 || Cin_sc < 64 || Cin_sc % 64 || Cout % tile_channels)
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo_sc_pack_weight: tile_channels 80 / 160, Cin %% 64, Cin_sc %% 64, Cout %% tile_channels (Cin=%d Cin_sc=%d Cout=%d tile=%d)",
+                 Cin, Cin_sc, Cout, tile_channels);
+    if (!fmc_aligned16(w) || !fmc_aligned16(w_sc) || !fmc_aligned16(dst)) FMC_FAIL(FMC_E_ALIGN, "conv3x3_halo_sc_pack_weight: pointers must be 16-byte aligned");
+    halo::pack_filter_sc((const bf16_t*)w, (const bf16_t*)w_sc, (bf16_t*)dst, Cin, Cout, Cin_sc, tile_channels, (hipStream_t)stream);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_sc_pack_weight");
+    return 0;
+}
+
+extern "C" int64_t fmc_conv3x3_halo_sc_pack_source(int64_t chunk, int Cin, int Cin_sc, int tile_channels, int* from_shortcut) {
+    int from_sc = 0;
+    const int64_t src = halo::sc_pack_source(chunk, Cin, Cin_sc, tile_channels, &from_sc);
+    if (from_shortcut) *from_shortcut = from_sc;
+    return src;
+}
+
+extern "C" int fmc_conv3x3_halo_sc_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
+    if (!fmc_conv3x3_halo_supported(n_img, H, W, Cin, Cin, Cout, 0)) return 0;      // the convolution's own conditions
+    return halo::sc_sources_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1);
+}
+
+extern "C" int fmc_conv3x3_halo_sc_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
+                                        const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout,
+                                        int64_t temb_row_stride, int temb_img_div, float* gn_partials, void* stream) {
+    if (!xs2) Cin_sc1 = Cin_sc;
+    if (int e = halo::check_args("conv3x3_halo_sc", true, x, nullptr, w_packed, bias, temb, nullptr, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_sc_supported(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1),
+                                 "%s: needs W %% 32 == 0, Cin %% 64 == 0, shortcut channels %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d Cout=%d shortcut=%d+%d)", n_img, H, W, Cin, Cout, Cin_sc1, Cin_sc - Cin_sc1))
+        return e;
+    if (int e = halo::check_sc_args("conv3x3_halo_sc", xs, xs2)) return e;
+    CHParamsSC P;
+    halo::fill_params(P, x, nullptr, Cin, w_packed, bias, temb, nullptr, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, 0, gn_partials, 9);
+    halo::fill_params_sc(P, xs, xs2, Cin_sc1, Cin_sc);
+    P.gn_coef = nullptr; P.gn_act = 0;
+    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = W / TW; P.tiles_n = Cout / BN;
+    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
+    fmc_launch<conv_halo_kernel<0, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_sc_bf16");
     return 0;
 }
 

@@ -68,6 +68,9 @@ template <int NBW, int WSUB, int SECOND> struct WStream {
 // The filter pack kernels are compiled once, in conv_halo.hip.  [Cout][3][3][Cin] (channels-last filter) -> [Cout / bn][Cin / 64][9 taps][2 halves]
 // [bn rows][32], chunk-swizzled; bn = 80 / 160 output channels per tile.
 void pack_filter(const bf16_t* w, bf16_t* dst, int Cin, int Cout, int bn, hipStream_t st);
+// Shortcut mode: the same order with the 1x1 filter w_sc [Cout][Cin_sc] behind it in every channel tile:
+// [Cout / bn][(Cin / 64) * 18 + (Cin_sc / 64) * 2 sub-tiles][bn rows][32], the shortcut sub-tiles [Cin_sc / 64][2 halves].
+void pack_filter_sc(const bf16_t* w, const bf16_t* w_sc, bf16_t* dst, int Cin, int Cout, int Cin_sc, int bn, hipStream_t st);
 
 // The argument checks of the four launch entry points, in their order: NULL, the entry point's own shape condition (`shape_ok`; its message and
 // arguments come behind), alignment, temb_img_div, the statistics-epilogue condition.  `name` heads every message.  `full`: the entry point has
@@ -86,6 +89,48 @@ int check_args(const char* name, bool full, const void* x, const void* x2, const
     if (gn_partials && (Cout % 64 || bn % (Cout / 32)))     // a channel tile must hold whole GroupNorm groups of an even number of channels
         FMC_FAIL(FMC_E_SHAPE, "%s: the statistics epilogue needs Cout %% 64 == 0 and %d %% (Cout / 32) == 0 (Cout=%d)", name, bn, Cout);
     return 0;
+}
+
+// The index map of that order (the pack kernel's, and fmc_conv3x3_halo_sc_pack_source's for the host): 16-byte chunk `id` of the packed filter holds the
+// eight elements from `return value` on of the 3x3 filter [Cout][3][3][Cin] or (*from_sc) of the 1x1 filter [Cout][Cin_sc].
+__host__ __device__ inline int64_t sc_pack_source(int64_t id, int cin, int cin_sc, int bn, int* from_sc) {
+    const int n3 = (cin >> 6) * 18, nsub = n3 + (cin_sc >> 6) * 2;
+    int64_t t = id;
+    const int p = (int)(t & 3); t >>= 2;
+    const int row = (int)(t % bn); t /= bn;
+    const int sub = (int)(t % nsub), nt = (int)(t / nsub);
+    const int lc = p ^ (3 * ((row >> 3) & 1));                           // physical chunk p of a row holds logical chunk lc
+    const int64_t co = (int64_t)nt * bn + row;
+    *from_sc = sub >= n3;
+    if (sub < n3) {
+        const int hk = sub & 1, tap = (sub >> 1) % 9, ch64 = sub / 18;
+        return (co * 9 + tap) * cin + ch64 * 64 + hk * 32 + lc * 8;
+    }
+    const int hk = (sub - n3) & 1, ch64 = (sub - n3) >> 1;
+    return co * cin_sc + ch64 * 64 + hk * 32 + lc * 8;
+}
+
+// Shortcut mode: the conditions on the two shortcut sources (channels % 64, each below 2 GiB, the combined filter below 2 GiB) ...
+inline int sc_sources_ok(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
+    if (Cin_sc < 64 || Cin_sc % 64 || Cin_sc1 <= 0 || Cin_sc1 > Cin_sc || Cin_sc1 % 64) return 0;
+    const int64_t px = (int64_t)n_img * H * W;
+    if (px * Cin_sc1 * 2 >= (1ll << 31) || px * (Cin_sc - Cin_sc1) * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)Cout * (9 * (int64_t)Cin + Cin_sc) * 2 >= (1ll << 31)) return 0;
+    return 1;
+}
+// ... their pointer checks, behind check_args ...
+inline int check_sc_args(const char* name, const void* xs, const void* xs2) {
+    if (!xs) FMC_FAIL(FMC_E_NULL, "%s: NULL shortcut input", name);
+    if (!fmc_aligned16(xs) || (xs2 && !fmc_aligned16(xs2))) FMC_FAIL(FMC_E_ALIGN, "%s: the shortcut inputs must be 16-byte aligned", name);
+    return 0;
+}
+// ... and their part of the parameter block (behind fill_params, which sets w_bytes for the 3x3 filter alone)
+template <class P_>
+void fill_params_sc(P_& P, const void* xs, const void* xs2, int Cin_sc1, int Cin_sc) {
+    P.xs = (const bf16_t*)xs; P.xs2 = (const bf16_t*)xs2; P.cs1 = Cin_sc1; P.cin_sc = Cin_sc;
+    const int64_t px = (int64_t)P.n_img * P.H * P.W;
+    P.xs_bytes = px * Cin_sc1 * 2; P.xs2_bytes = px * (Cin_sc - Cin_sc1) * 2;
+    P.w_bytes += (int64_t)P.cout * Cin_sc * 2;
 }
 
 // The common part of a parameter block.  H, W as in Params (phase mode: the source size, ups = 0); taps = 9, or 16 for the folded filter.

@@ -1903,6 +1903,47 @@ def _w_halo_packed(weight_cl: torch.Tensor) -> torch.Tensor:
     return _w_packed(weight_cl, "halo", 9, "fmc_conv3x3_halo_pack_weight")
 
 
+# ---- a ResnetBlock2D's 1x1 shortcut inside conv2's reduction (inference): conv2(a) + Ws [x | skip] + b2 + bs is one sum over K = 9 Cout + Cin_x
+# whose last Cin_x channels are multiplied at the centre tap only -- the shortcut GEMM, its [M, Cout] write and conv2's residual read go away, and
+# the shortcut product is not rounded to bf16 (include/fmc_hip.h: fmc_conv3x3_halo_sc_bf16; the 10 x 32-pixel-tile kernel only) ----
+SHORTCUT_FOLD = os.environ.get("FMC_SHORTCUT_FOLD", "1") != "0"   # A/B switch: 0 = the shortcut as its own GEMM, added in conv2's epilogue
+shortcut_fold_calls = {"folded": 0}
+
+
+def conv3x3_halo_sc_supported(n: int, h: int, w: int, cin: int, cout: int, cin_sc: int, cin_sc1: int) -> bool:
+    return bool(_lib.load().fmc_conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cin_sc1))
+
+
+def _w_halo_sc_packed(weight_cl: torch.Tensor, w_sc: torch.Tensor, bn: int = 160) -> torch.Tensor:
+    """The 3x3 filter and the 1x1 shortcut filter `[Cout, Cin_sc]` in one sub-tile order (`fmc_conv3x3_halo_sc_pack_weight`), cached on the 3x3
+    weight per version of both.  The entry holds the shortcut weight, so an equal pointer is the same live storage."""
+    def build():
+        cout, cin = weight_cl.shape[:2]
+        assert weight_cl.is_contiguous(memory_format=torch.channels_last) and w_sc.is_contiguous() and w_sc.shape[0] == cout
+        out = torch.empty(cout * (9 * cin + w_sc.shape[1]), dtype=weight_cl.dtype, device=weight_cl.device)
+        _lib.check(_lib.load().fmc_conv3x3_halo_sc_pack_weight(weight_cl.data_ptr(), w_sc.data_ptr(), out.data_ptr(), cin, cout, w_sc.shape[1], bn,
+                                                               _stream()), "fmc_conv3x3_halo_sc_pack_weight")
+        return out, w_sc
+    return derived_on_owner(weight_cl, "_fmc_wtm", ("halo_sc", bn, w_sc.data_ptr(), w_sc._version, w_sc.storage_offset(), tuple(w_sc.shape)), build)[0]
+
+
+def shortcut_fold_ok(x_nchw: torch.Tensor, weight_cl: torch.Tensor, xs: torch.Tensor, xs2: Optional[torch.Tensor]) -> bool:
+    """conv2 of a ResnetBlock2D takes the block's 1x1 shortcut into its reduction: inference on channels-last bf16 images where `conv3x3` routes
+    the convolution to the 10 x 32-pixel-tile kernel (the same conditions) and the shortcut sources fit it."""
+    if not (SHORTCUT_FOLD and CONV_HALO and not torch.is_grad_enabled() and x_nchw.is_cuda and weight_cl.dtype == torch.bfloat16
+            and all(t is None or (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()) for t in (x_nchw, xs, xs2))
+            and weight_cl.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    n, cin, h, w = x_nchw.shape
+    cout = weight_cl.shape[0]
+    if weight_cl.shape[1] != cin or xs.shape[0] != n or tuple(xs.shape[2:]) != (h, w) or (xs2 is not None and (xs2.shape[0] != n or tuple(xs2.shape[2:]) != (h, w))):
+        return False
+    cs1 = xs.shape[1]
+    cin_sc = cs1 + (xs2.shape[1] if xs2 is not None else 0)
+    return (conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
+            and n * _lib.load().fmc_conv3x3_halo_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES)
+
+
 def _gn_tagged(y, want: bool, cout: int):
     """A halo launch's result in `conv3x3` -- `(out, partials)` with `want`, else `out` -- as NCHW view; the statistics go with it as `_fmc_gn` for
     the GroupNorm that consumes it."""
@@ -2002,17 +2043,38 @@ def groupnorm_partials(x: torch.Tensor, groups: int, x2: Optional[torch.Tensor] 
 
 
 def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=None, residual_nhwc=None, temb_div: int = 1, upsample: bool = False,
-                 x2_nhwc: Optional[torch.Tensor] = None, gn_coef: Optional[torch.Tensor] = None, gn_act: bool = True, emit_gn: bool = False):
+                 x2_nhwc: Optional[torch.Tensor] = None, gn_coef: Optional[torch.Tensor] = None, gn_act: bool = True, emit_gn: bool = False,
+                 shortcut=None):
     """`conv3x3(act(x * scale + shift))` on channels-last bf16 images: x `[N, Hs, Ws, C1]` (+ `x2 [N, Hs, Ws, C2]`: channel concat read in place),
     filter `[Cout, C1 + C2, 3, 3]` channels-last, `gn_coef [N, C1 + C2, 2]` fp32 or None (plain convolution).  Returns out `[N, H, W, Cout]`, or
-    `(out, partials [N, tiles, 32, 2])` with `emit_gn` (statistics of the output for the GroupNorm that consumes it)."""
+    `(out, partials [N, tiles, 32, 2])` with `emit_gn` (statistics of the output for the GroupNorm that consumes it).
+    `shortcut = (xs [N, H, W, Cs1], xs2 [N, H, W, Cs2] | None, w_sc [Cout, Cs1 + Cs2], b_sc [Cout] | None)`: `+ w_sc . [xs | xs2] + b_sc` in the same
+    reduction (plain convolution of one source without temb / residual / upsample only)."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc, gn_coef)
     n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     assert gn_coef is None or (gn_coef.shape == (n, cin, 2) and gn_coef.dtype == torch.float32 and gn_coef.is_contiguous())
     L = _lib.load()
+    part = torch.empty(n, L.fmc_conv3x3_halo_tiles_per_image(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+    if shortcut is not None:
+        xs, xs2, w_sc, b_sc = shortcut
+        _dev(xs, xs2, w_sc, b_sc)
+        assert temb is None and residual_nhwc is None and x2_nhwc is None and gn_coef is None and not upsample
+        cs1, cin_sc = xs.shape[3], w_sc.shape[1]
+        assert xs.is_contiguous() and xs.dtype == torch.bfloat16 and xs.shape[:3] == (n, h, w) and w_sc.shape[0] == cout and w_sc.dtype == torch.bfloat16
+        assert (cs1 == cin_sc) if xs2 is None else (xs2.is_contiguous() and xs2.dtype == xs.dtype and xs2.shape == (n, h, w, cin_sc - cs1))
+        assert b_sc is None or (b_sc.shape == (cout,) and b_sc.dtype == torch.bfloat16 and b_sc.is_contiguous())
+        wp = _w_halo_sc_packed(weight_cl, w_sc)
+        out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
+        conv_halo_calls["conv"] += 1
+        shortcut_fold_calls["folded"] += 1
+        if call_log is not None:      # (a shape of its own: the longer launches do not enter the plain shapes' per-shape averages)
+            call_log.append(("conv_halo", (n, h, w, cin, cout, False, cin_sc), 2.0 * n * h * w * cout * (9 * cin + cin_sc)))
+        # the shortcut bias rides as a one-row "temb" shared by all images: bias + temb are summed in fp32
+        _lib.check(L.fmc_conv3x3_halo_sc_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), _p(b_sc), out.data_ptr(), xs.data_ptr(), _p(xs2), cs1, cin_sc,
+                                              n, h, w, cin, cout, cout, n, _p(part), _stream()), "fmc_conv3x3_halo_sc_bf16")
+        return (out, part) if emit_gn else out
     wp = _w_halo_packed(weight_cl)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
-    part = torch.empty(n, L.fmc_conv3x3_halo_tiles_per_image(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
     conv_halo_calls["conv"] += 1
     conv_halo_calls["gn_fused"] += gn_coef is not None
     if call_log is not None:
@@ -2584,10 +2646,25 @@ def geglu_linear(x: torch.Tensor, weight: torch.Tensor, bias, weight_il: torch.T
 
 
 def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, residual_nchw=None, stride=(1, 1),
-            padding=(1, 1), temb_div: int = 1, upsample: bool = False, emit_gn: bool = False, own_only: bool = False) -> torch.Tensor:
+            padding=(1, 1), temb_div: int = 1, upsample: bool = False, emit_gn: bool = False, own_only: bool = False, shortcut=None) -> torch.Tensor:
     """3x3 conv on a logical NCHW / physical channels-last tensor with `+ temb[:, :, None, None]` and `+ residual`.
-    Returns a logical NCHW view over channels-last storage.  `own_only`: the vendor library is not a candidate arm."""
+    Returns a logical NCHW view over channels-last storage.  `own_only`: the vendor library is not a candidate arm.
+    `shortcut = (xs, xs2 | None, w_sc [Cout, Cin_sc], b_sc | None)` (NCHW views like x): the block's 1x1 shortcut in the same reduction; the caller
+    has asked `shortcut_fold_ok` -- there is no other route for it."""
     import torch.nn.functional as F
+
+    if shortcut is not None:
+        n, cin, h, w = x_nchw.shape
+        cout = weight_cl.shape[0]
+        xs, xs2, w_sc, b_sc = shortcut
+        assert temb is None and residual_nchw is None and not upsample and tuple(stride) == (1, 1) and tuple(padding) == (1, 1)
+        if not shortcut_fold_ok(x_nchw, weight_cl, xs, xs2):
+            raise RuntimeError("conv3x3: no kernel takes this shape with the shortcut in the reduction")
+        want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0)
+        dispatch_calls["conv3x3"]["own"] += 1
+        y = conv3x3_halo(x_nchw.permute(0, 2, 3, 1), weight_cl, bias, emit_gn=want,
+                         shortcut=(xs.permute(0, 2, 3, 1), None if xs2 is None else xs2.permute(0, 2, 3, 1), w_sc, b_sc))
+        return _gn_tagged(y, want, cout)
 
     def lib():
         xin = F.interpolate(x_nchw, scale_factor=2.0, mode="nearest") if upsample else x_nchw

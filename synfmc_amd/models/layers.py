@@ -176,10 +176,17 @@ class Conv2d(nn.Conv2d):
 
     def forward(self, x: torch.Tensor, scale: float = 1.0, temb: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, temb_div: int = 1, upsample: bool = False,
-                x2: Optional[torch.Tensor] = None, emit_gn: bool = False) -> torch.Tensor:
+                x2: Optional[torch.Tensor] = None, emit_gn: bool = False, shortcut=None) -> torch.Tensor:
         """conv(x) [+ temb[:, :, None, None]] [+ residual]; the two extras ride in the kernel epilogue when the
         gfx950 implicit-GEMM conv / GEMM is used.  `temb_div` > 1: image i uses temb row i // temb_div.
-        `upsample`: conv(nearest-2x(x)) with the upsample folded into the kernel's operand addressing."""
+        `upsample`: conv(nearest-2x(x)) with the upsample folded into the kernel's operand addressing.
+        `shortcut = (xs, xs2 | None, conv1x1)`: `+ conv1x1(cat([xs, xs2], 1))` inside this convolution's reduction (the caller has asked
+        `ResnetBlock2D._shortcut_fold_ok`)."""
+        if shortcut is not None:
+            xs, xs2, sc = shortcut
+            assert temb is None and residual is None and not upsample and x2 is None
+            return K.conv3x3(x, self._weight_cl(), self.bias, emit_gn=emit_gn,
+                             shortcut=(xs, xs2, sc.weight.view(sc.out_channels, sc.in_channels), sc.bias))
         if self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0):
             n, c, h, w = x.shape
             assert temb is None
@@ -407,10 +414,24 @@ class ResnetBlock2D(nn.Module):
         # both convolutions feed a GroupNorm (norm2 here, the next module's norm behind conv2): where that norm would read its input
         # twice (the 40x64 level) the conv's epilogue emits its statistics (`emit_gn`, hip_ops.gn_emit_ok)
         h = self.conv1(self.norm1(input_tensor, act=True, x2=skip), temb=t, temb_div=div, emit_gn=True)
+        a2 = self.norm2(h, act=True)
+        if self.conv_shortcut is not None and self._shortcut_fold_ok(a2, input_tensor, skip):
+            # the 1x1 shortcut as a centre-tap segment of conv2's reduction: no shortcut GEMM, no [M, Cout] round trip (hip_ops.SHORTCUT_FOLD)
+            out = self.conv2(a2, emit_gn=True, shortcut=(input_tensor, skip, self.conv_shortcut))
+            return out if self.output_scale_factor == 1.0 else out / self.output_scale_factor
         if self.conv_shortcut is not None:
             input_tensor = self.conv_shortcut(input_tensor, x2=skip)
-        out = self.conv2(self.norm2(h, act=True), residual=input_tensor, emit_gn=True)   # `input + h` rides in conv2's epilogue
+        out = self.conv2(a2, residual=input_tensor, emit_gn=True)   # `input + h` rides in conv2's epilogue
         return out if self.output_scale_factor == 1.0 else out / self.output_scale_factor
+
+    def _shortcut_fold_ok(self, a2, x, skip) -> bool:
+        c2, sc = self.conv2, self.conv_shortcut
+        if not (a2.is_cuda and a2.dtype == torch.bfloat16 and c2.weight.dtype == torch.bfloat16 and sc.weight.dtype == torch.bfloat16
+                and not torch.is_grad_enabled() and sc.kernel_size == (1, 1) and sc.stride == (1, 1) and sc.padding == (0, 0)
+                and sc.weight.is_contiguous() and c2.kernel_size == (3, 3) and c2.stride == (1, 1) and c2.padding == (1, 1)
+                and c2.dilation == (1, 1) and c2.groups == 1 and a2.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        return K.shortcut_fold_ok(a2, c2._weight_cl(), x, skip)
 
 
     # ---- GroupNorm + SiLU inside the convolutions' operand path (opt-in: hip_ops.CONV_GN_FUSED) ---------------------------
