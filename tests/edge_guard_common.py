@@ -14,7 +14,10 @@ the tensor `row stride = width + col_pad` elements apart (the pad columns belong
 is given in ROWS of the tensor: the case tables choose it at least as large as the largest tile, in rows, of the kernel under
 test, so that a reach of one tile past either end lands in memory of the test's own.
 
-Used by test_edge_guard_host.py (CPU) and test_gpu_edge_guards.py.
+An output that the ABI ACCUMULATES into (dgamma / dbeta, `out` with `accumulate != 0`, a running amax) cannot start as sentinel: `Guard.out(...,
+init=...)` initialises the view as the ABI demands and leaves the sentinel around it; of such an output only the outside of the view is checked.
+
+Used by test_edge_guard_host.py (CPU), test_gpu_edge_guards.py, test_gpu_edge_guards_fused.py and test_gpu_edge_guards_training.py.
 """
 import math
 
@@ -23,8 +26,8 @@ import torch
 POISONS = ("zeros", "nan", "inf")
 _POISON_VALUE = {"zeros": 0.0, "nan": float("nan"), "inf": float("inf")}
 
-# the sentinels of test_gpu_attn_backward.py
-SENTINEL = {torch.bfloat16: (torch.int16, 0x5A5A), torch.float32: (torch.int32, 0x5A5A5A5A)}
+# the sentinels of test_gpu_attn_backward.py; one byte of the same pattern for byte outputs (e4m3: 0x5A = 104.0, finite)
+SENTINEL = {torch.bfloat16: (torch.int16, 0x5A5A), torch.float32: (torch.int32, 0x5A5A5A5A), torch.uint8: (torch.uint8, 0x5A)}
 
 
 def poison_value(poison, dtype):
@@ -72,7 +75,7 @@ def _bits(t):
 
 def guarded_output(shape, dtype, rows_before, rows_after, col_pad=0, device="cpu"):
     """`(arena, view)` in the layout of `guarded_input`, every word of the arena holding the sentinel of `dtype` (bf16: 0x5A5A,
-    fp32 -- outputs, LSE, statistics partials, workspaces --: 0x5A5A5A5A)."""
+    fp32 -- outputs, LSE, statistics partials, workspaces --: 0x5A5A5A5A, uint8 -- e4m3 bytes --: 0x5A)."""
     total, lead, strides = _layout(tuple(shape), torch.empty((), dtype=dtype).element_size(), rows_before, rows_after, col_pad)
     arena = torch.empty((total,), dtype=dtype, device=device)
     _bits(arena).fill_(SENTINEL[dtype][1])
@@ -166,9 +169,14 @@ class Guard:
         self.bands.append((name, before, after, col_pad))
         return view
 
-    def out(self, shape, dtype, band, col_pad=0, name="out", written=True):
+    def out(self, shape, dtype, band, col_pad=0, name="out", written=True, init=None):
+        """`init` (a number or a tensor of the view's shape): an output the ABI accumulates into.  The view starts as `init`, the sentinel
+        stays around it, and only the outside of the view is checked (what is inside is for the reference to judge)."""
         before, after = band if isinstance(band, tuple) else (band, band)
         arena, view = guarded_output(shape, dtype, before, after, col_pad, self.device)
+        if init is not None:
+            view.copy_(init) if torch.is_tensor(init) else view.fill_(init)
+            written = False
         self.outputs.append((name, arena, view, written))
         self.bands.append((name, before, after, col_pad))
         return view

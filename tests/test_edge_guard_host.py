@@ -1,7 +1,7 @@
 """The helpers of tests/edge_guard_common.py do what they say, and each assertion catches the fault it is written for (CPU).
 
 The "kernels" here are plain-torch stand-ins that reach into the arena the way a HIP kernel with a partial last tile does: through
-`as_strided` past the end of the view they were given.  Six of them are wrong, each in one way, and each must fail exactly its own one of
+`as_strided` past the end of the view they were given.  Nine of them are wrong, each in one way, and each must fail exactly its own one of
 
     bits       `assert_same_bits`: finite and bit-identical under zeros, NaN and +Inf around the inputs
     outside    `assert_contained`: a word outside the output view was written
@@ -115,6 +115,44 @@ def test_assert_same_bits():
         EG.assert_same_bits(nan)
 
 
+def test_byte_sentinel_and_byte_output():
+    """e4m3 outputs are bytes: a one-byte sentinel, the same containment rules."""
+    itype, sent = EG.SENTINEL[torch.uint8]
+    assert itype == torch.uint8 and sent == 0x5A
+    arena, view = EG.guarded_output((5, 48), torch.uint8, 2, 2, col_pad=16)
+    assert view.data_ptr() % 16 == 0 and view.stride() == (64, 1) and bool((arena == sent).all())
+    with pytest.raises(EG.InsideUnwritten):
+        EG.assert_contained(arena, view)
+    view.fill_(3)
+    EG.assert_contained(arena, view)
+    arena[-1] = 0
+    with pytest.raises(EG.OutsideTouched):
+        EG.assert_contained(arena, view)
+    same = {p: {"y": view.clone()} for p in EG.POISONS}
+    EG.assert_same_bits(same)
+    same["nan"]["y"][0, 0] = 4
+    with pytest.raises(EG.SurroundingsMoved):
+        EG.assert_same_bits(same)
+
+
+@pytest.mark.parametrize("init", [0.0, "tensor"])
+def test_initialised_view_checks_outside_only(init):
+    """`Guard.out(init=...)`: the view starts as the ABI demands (also when that happens to be the sentinel's value), is not asked to have been
+    written, and the words around it still are checked."""
+    g = EG.Guard("zeros")
+    start = _rnd((3, 8), 5, torch.float32) if init == "tensor" else init
+    acc = g.out((3, 8), torch.float32, 2, 8, "acc", init=start)
+    assert torch.equal(acc, start if init == "tensor" else torch.zeros(3, 8))
+    name, arena, view, written = g.outputs[0]
+    assert written is False and bool((arena[~EG.owned_mask(arena, view)].view(torch.int32) == EG.SENTINEL[torch.float32][1]).all())
+    g.check()                                                           # nothing written: fine for an accumulator
+    acc[0, 0] = torch.zeros((), dtype=torch.int32).fill_(EG.SENTINEL[torch.float32][1]).view(torch.float32)
+    g.check()                                                           # ... and a sum that equals the sentinel is no finding
+    arena[arena.numel() - 1] = 1.0
+    with pytest.raises(EG.OutsideTouched):
+        g.check()
+
+
 # ---- stand-in kernels ---------------------------------------------------------------------------------------------------------
 def _past(view, extra_rows=0, extra_cols=0):
     """The view with more rows / columns than it has: what a kernel's address arithmetic reaches past a partial tile."""
@@ -199,6 +237,62 @@ def copy_standin(fault, col_pad=8):
     return run, {"y": ref}, 2.0 ** -8
 
 
+def column_sum_standin(fault):
+    """out = sum over the 11 rows of x [11, 16], rows summed a tile of 8 at a time: the training side's reductions."""
+    M, N = 11, 16
+    x = _rnd((M, N), 40, torch.float32)
+    ref = x.double().sum(0)
+
+    def run(g):
+        xv = g.inp(x, TILE)
+        out = g.out((N,), torch.float32, 2)
+        xs = _past(xv, 1) if fault == "pad_row" else xv                 # the last tile's row guard is one row too generous
+        out.copy_(xs.double().sum(0).float())
+        return {"out": out}
+
+    return run, {"out": ref}, 1e-5
+
+
+def accumulate_standin(fault):
+    """out += x.sum(rows) into an accumulator the ABI wants initialised (here: to `base`); stores go four words at a time."""
+    M, N = 11, 12
+    x, base = _rnd((M, N), 41, torch.float32), _rnd((N,), 42, torch.float32)
+    ref = base.double() + x.double().sum(0)
+
+    def run(g):
+        xv = g.inp(x, TILE)
+        out = g.out((N,), torch.float32, 2, name="out", init=base)
+        add = xv.double().sum(0).float()
+        if fault == "spill":                                           # one word past the view gets the "accumulated" 0 + old value
+            wide = out.as_strided((N + 1,), (1,), out.storage_offset())
+            wide += torch.cat([add, torch.zeros(1)])
+            wide[N] = 0.0
+        else:
+            out += add
+        return {"out": out}
+
+    return run, {"out": ref}, 1e-5
+
+
+def byte_standin(fault):
+    """y = byte(x) on [R, W] rows of bytes, rows `W + 16` apart: an fp8 epilogue's output."""
+    R, W = 11, 32
+    x = torch.randint(1, 0x5A, (R, W), generator=torch.Generator().manual_seed(43), dtype=torch.uint8)      # (below the sentinel: a byte has no spare pattern,
+                                                                                                          # so a case keeps its values off 0x5A)
+    ref = x.double()
+
+    def run(g):
+        xv = g.inp(x, TILE, 16)
+        y = g.out((R, W), torch.uint8, TILE, 16)
+        if fault == "row_past":                                        # one row too many
+            _past(y, 1)[:R + 1] = torch.cat([xv, torch.zeros(1, W, dtype=torch.uint8)])
+        else:
+            y.copy_(xv)
+        return {"y": y}
+
+    return run, {"y": ref}, 2.0 ** -8
+
+
 def verdicts(run, refs, tol):
     """Which of the three guard assertions a stand-in fails, and "gate" when it misses the reference under zeros."""
     failed, results = set(), {}
@@ -232,6 +326,9 @@ WRONG = [
     ("one column written past a strided row", lambda: copy_standin("col_past"), {"outside"}),
     ("last row left unwritten", lambda: copy_standin("last_row"), {"unwritten", "gate"}),       # (the gate too: the row holds the sentinel here; in a
                                                                                                 # fresh allocation it would hold the previous call's right result)
+    ("reduction over one pad row", lambda: column_sum_standin("pad_row"), {"bits"}),
+    ("accumulate-output spills one word past its view", lambda: accumulate_standin("spill"), {"outside"}),
+    ("byte output one row too long", lambda: byte_standin("row_past"), {"outside"}),
 ]
 
 
@@ -242,8 +339,9 @@ def test_wrong_standin_fails_exactly_its_assertion(what, make, expected):
     assert got == expected, f"{what}: failed {sorted(got)}, expected {sorted(expected)}"
 
 
-@pytest.mark.parametrize("make", [lambda: attn_standin(None), lambda: groupnorm_standin(None), lambda: copy_standin(None), lambda: copy_standin(None, 0)],
-                         ids=["attention", "groupnorm", "strided_copy", "dense_copy"])
+@pytest.mark.parametrize("make", [lambda: attn_standin(None), lambda: groupnorm_standin(None), lambda: copy_standin(None), lambda: copy_standin(None, 0),
+                                  lambda: column_sum_standin(None), lambda: accumulate_standin(None), lambda: byte_standin(None)],
+                         ids=["attention", "groupnorm", "strided_copy", "dense_copy", "column_sum", "accumulate", "byte_copy"])
 def test_correct_standin_passes_under_all_surroundings(make):
     run, refs, tol = make()
     assert verdicts(run, refs, tol) == set()
