@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from oracle import conditioning as OC
 from oracle import diffusers_restated as OD
+from tests.conv_fwd_common import assert_bf16_close, assert_f32_close      # (the element-wise bounds; other test files import them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,27 +38,6 @@ def K():
 def rel_inf(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
-
-
-def assert_bf16_close(got, ref, mag, what=""):
-    """Element-wise bound for a kernel that rounds ONCE to bf16 from an fp32 accumulator: |got - ref| <= 2^-8 |ref| + 1e-5 mag,
-    `ref` the exact result on the same (rounded) inputs, `mag` the sum of |terms| behind every element (fp32 accumulation error of
-    kernel and reference).  A mis-indexed tile / row / column fails this where a max-norm `rel_inf` can hide it."""
-    got, ref, mag = got.detach().double().cpu(), ref.detach().double().cpu(), mag.detach().double().cpu()
-    err = (got - ref).abs()
-    bound = 2.0 ** -8 * ref.abs() + 1e-5 * mag
-    bad = err > bound
-    assert not bool(bad.any()), (f"{what}: {int(bad.sum())} / {bad.numel()} elements beyond the bf16 bound, worst "
-                                 f"err {float((err - bound).max()):.3e} at {tuple(int(i) for i in (err - bound).flatten().argmax().unsqueeze(0))}")
-
-
-def assert_f32_close(got, ref, mag, what=""):
-    """fp32-storage (split-bf16 x3) kernels: every product carries <= ~3 * 2^-18 relative error (dropped lo*lo + the two split
-    remainders), so |got - ref| <= 2e-5 * sum |terms| element by element."""
-    got, ref, mag = got.detach().double().cpu(), ref.detach().double().cpu(), mag.detach().double().cpu()
-    err = (got - ref).abs()
-    bad = err > 2e-5 * mag
-    assert not bool(bad.any()), f"{what}: {int(bad.sum())} / {bad.numel()} elements beyond 2e-5 * |terms|, worst {float((err / mag.clamp_min(1e-30)).max()):.3e}"
 
 
 def rnd(shape, seed, dtype, scale=1.0, shift=0.0):
