@@ -797,6 +797,26 @@ int fmc_optim_grad_norm(const fmc_optim_tensor* tensors, int n_tensors, const fm
 int fmc_optim_adamw_step(const fmc_optim_tensor* tensors, int n_tensors, const fmc_optim_chunk* chunks, int n_chunks, const float* hyper,
                          int n_hyper, int n_clip_groups, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The small bf16 passes of a Camera-Encoder / OMC-Adapter training step (csrc/train_elementwise.hip): what the chain of
+ * trainable ResNet blocks and the Camera-Adapter merge needs next to its GEMMs and convolutions.  bf16 only; pure HBM passes; every
+ * output element is written once by one thread (no atomics, no workspace, bit-reproducible).  Pointers need the alignment of their
+ * element (2 bytes; FMC_E_ALIGN otherwise): a tensor that is 16-byte aligned moves as 16-byte vectors, any other element by element
+ * (the flat kernels bring the OUTPUT to a 16-byte boundary with up to 7 leading scalar elements first).  An output may alias an input.
+ *
+ * fmc_avgpool2x2_fwd: AvgPool2d(kernel 2, stride 2) on NHWC.  x [n_img, H, W, C] -> y [n_img, H / 2, W / 2, C] (floor: the last row /
+ *   column of an odd size is not read); C % 8 == 0 (FMC_E_SHAPE otherwise).  y = bf16(0.25f * (((x00 + x01) + x10) + x11)), the sum in
+ *   fp32, rounded once.  H or W of 1: an empty output, nothing is launched (y may be NULL).
+ * fmc_avgpool2x2_bwd: dy [n_img, H / 2, W / 2, C] -> dx [n_img, H, W, C], ALL of it: dx = bf16(0.25f * dy) under a window, +0 in the
+ *   last row / column of an odd size (dy may be NULL where it is empty).
+ * fmc_relu_fwd: y = x < 0 ? +0 : x  (std::max(x, 0): -0 and NaN pass through);  fmc_relu_bwd: dx = y > 0 ? dy : +0.
+ * fmc_add_bf16: out = bf16(float(a) + float(b)).   n >= 1 elements each. */
+int fmc_avgpool2x2_fwd(const void* x, void* y, int n_img, int H, int W, int C, void* stream);
+int fmc_avgpool2x2_bwd(const void* dy, void* dx, int n_img, int H, int W, int C, void* stream);
+int fmc_relu_fwd(const void* x, void* y, int64_t n, void* stream);
+int fmc_relu_bwd(const void* dy, const void* y, void* dx, int64_t n, void* stream);
+int fmc_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

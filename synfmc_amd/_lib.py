@@ -154,6 +154,11 @@ SIGNATURES = {
     "fmc_optim_check_tables": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
     "fmc_optim_grad_norm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "fmc_optim_adamw_step": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "fmc_avgpool2x2_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fmc_avgpool2x2_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fmc_relu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "fmc_relu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "fmc_add_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "fmc_temporal_block_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fmc_temporal_block_set_debug": (c_int, [c_void_p]),

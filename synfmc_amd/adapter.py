@@ -13,7 +13,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import hip_ops as K
-from .models.layers import Conv2d, from_tokens, to_tokens
+from .models.layers import OWN_MARK, Conv2d, from_tokens, shadow_twin, to_tokens
+from .models.pose_adaptor import _own_elementwise
 
 
 class Downsample(nn.Module):
@@ -31,6 +32,8 @@ class Downsample(nn.Module):
         assert x.shape[1] == self.channels
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
+        if not self.use_conv and _own_elementwise(self, x) and x.shape[1] % 8 == 0:
+            return K.avg_pool2x2(x)
         return self.op(x)
 
 
@@ -54,6 +57,9 @@ class ResnetBlock(nn.Module):
             x = self.down_opt(x)
         if self.in_conv is not None:
             x = self.in_conv(x)
+        if _own_elementwise(self, x):
+            h = self.block2(K.relu(self.block1(x)))
+            return K.add(h, self.skep(x) if self.skep is not None else x)
         h = self.block2(F.relu(self.block1(x)))
         return h + (self.skep(x) if self.skep is not None else x)
 
@@ -93,15 +99,24 @@ class Adapter(nn.Module):
         `mask_feat` is 3-D `[(b f), H, W]`, x is `[(b f), H/8, W/8, cin]` as `fmc_omc_rasterize_fwd(layout=2)` writes it."""
         if mask_feat is not None and mask_feat.ndim == 3:
             return self.forward_unshuffled(x, mask_feat)
-        dtype = self.conv_in.weight.dtype
-        return self._encode(self.unshuffle(x).to(dtype), None if mask_feat is None else mask_feat[:, 0])
+        return self._encode(self.unshuffle(x).to(self._act_dtype(x)), None if mask_feat is None else mask_feat[:, 0])
+
+    def _act_dtype(self, x) -> torch.dtype:
+        """What the input is cast to: the parameter dtype; for a marked Adapter (fp32 masters, `training.omc_trainable_parameters`) fed
+        bf16 device activations, bf16 -- the own training route runs without autocast."""
+        if self.__dict__.get(OWN_MARK, False) and x.is_cuda and x.dtype == torch.bfloat16:
+            return torch.bfloat16
+        return self.conv_in.weight.dtype
 
     def forward_unshuffled(self, x_cl, mask):
         """x_cl `[(b f), H/8, W/8, cin]` channels-last with PixelUnshuffle(8) applied and mask `[(b f), H, W]` fp32:
         exactly what `fmc_omc_rasterize_fwd(layout=2)` writes."""
-        return self._encode(x_cl.permute(0, 3, 1, 2).to(self.conv_in.weight.dtype), mask)
+        return self._encode(x_cl.permute(0, 3, 1, 2).to(self._act_dtype(x_cl)), mask)
 
     def _encode(self, x, mask):
+        if (not torch.is_grad_enabled() and self.__dict__.get(OWN_MARK, False) and x.is_cuda and x.dtype == torch.bfloat16
+                and self.conv_in.weight.dtype == torch.float32):
+            return shadow_twin(self)._encode(x, mask)       # fp32 masters without a gradient: the forward of their bf16 shadows
         features = []
         x = self.conv_in(self.zero_conv_in(x))
         if mask is not None:

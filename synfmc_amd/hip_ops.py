@@ -2999,12 +2999,13 @@ class _LinearTrainable(torch.autograd.Function):
     Gradients come back in each parameter's dtype; the residual's is dY."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, w_run, b_run):
+    def forward(ctx, x, weight, bias, residual, w_run, b_run, alpha=1.0):
         with torch.no_grad():
-            y = linear(x, w_run, b_run, residual)
+            y = linear(x, w_run, b_run, residual, alpha)
         ctx.save_for_backward(x, w_run)
         ctx.has_res = residual is not None and residual.requires_grad
         ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+        ctx.alpha = float(alpha)
         return y
 
     @staticmethod
@@ -3018,23 +3019,24 @@ class _LinearTrainable(torch.autograd.Function):
         dx = dw = db = None
         with torch.no_grad():
             if ctx.needs_input_grad[0]:
-                dx = linear_backward_data(dy, w_run).view(x.shape)
+                dx = linear_backward_data(dy, w_run, ctx.alpha).view(x.shape)
             if ctx.needs_input_grad[1]:
-                dw = linear_wgrad(dy2, x2).to(ctx.dtypes[0])
+                dw = linear_wgrad(dy2, x2, ctx.alpha).to(ctx.dtypes[0])
             if ctx.needs_input_grad[2]:
-                db = column_sum(dy2).to(ctx.dtypes[1])
-        return dx, dw, db, (dy if ctx.has_res else None), None, None
+                db = column_sum(dy2, ctx.alpha).to(ctx.dtypes[1])
+        return dx, dw, db, (dy if ctx.has_res else None), None, None, None
 
 
 def linear_trainable(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-                     w_run: Optional[torch.Tensor] = None, b_run: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`x @ weight^T + bias + residual`, differentiable in x, weight, bias and the residual, on this library's kernels (see
-    `_LinearTrainable`).  `w_run` / `b_run`: the weight / bias in x's dtype (cached bf16 shadows of fp32 masters); default: a cast per call."""
+                     w_run: Optional[torch.Tensor] = None, b_run: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
+    """`alpha * (x @ weight^T + bias) + residual`, differentiable in x, weight, bias and the residual, on this library's kernels (see
+    `_LinearTrainable`).  `w_run` / `b_run`: the weight / bias in x's dtype (cached bf16 shadows of fp32 masters); default: a cast per call.
+    `alpha` (the Camera-Adapter merge's scale) multiplies dX, dW and db; the residual's gradient is dY."""
     if w_run is None:
         w_run = weight.detach() if weight.dtype == x.dtype else weight.detach().to(x.dtype)
     if b_run is None and bias is not None:
         b_run = bias.detach() if bias.dtype == x.dtype else bias.detach().to(x.dtype)
-    return _LinearTrainable.apply(x, weight, bias, residual, w_run, b_run)
+    return _LinearTrainable.apply(x, weight, bias, residual, w_run, b_run, float(alpha))
 
 
 def conv3x3_weight_grad(x_nhwc: torch.Tensor, dy_nhwc: torch.Tensor) -> torch.Tensor:
@@ -3075,13 +3077,19 @@ class _Conv3x3Trainable(torch.autograd.Function):
     it changes every step and is small next to the activations), dW as pixel-reduction GEMMs (`conv3x3_weight_grad`)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
+    def forward(ctx, x, weight, bias, w_run=None, b_run=None):
         ctx.has_bias = bias is not None
+        ctx.shadow = w_run is not None
         with torch.no_grad():
-            w_cl = weight.detach().to(x.dtype).contiguous(memory_format=torch.channels_last)
-            b = None if bias is None else bias.detach().to(x.dtype)
-            return conv3x3(x, w_cl, b)
+            if w_run is None:
+                w_run = weight.detach().to(x.dtype)
+                b_run = None if bias is None else bias.detach().to(x.dtype)
+                w_cl = w_run.contiguous(memory_format=torch.channels_last)
+            else:       # the cached bf16 shadow of an fp32 master: its channels-last form is derived once per version
+                w_cl = derived_on_owner(w_run, "_fmc_w_cl", None, lambda: w_run.contiguous(memory_format=torch.channels_last))
+            ctx.save_for_backward(x, weight if not ctx.shadow else w_run)
+            ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+            return conv3x3(x, w_cl, b_run)
 
     @staticmethod
     def backward(ctx, dy):
@@ -3090,17 +3098,129 @@ class _Conv3x3Trainable(torch.autograd.Function):
         dx = dw = db = None
         with torch.no_grad():
             if ctx.needs_input_grad[0]:
-                w_flip = weight.detach().to(dy.dtype).flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last)
-                dx = conv3x3(dy, w_flip, None)
+                flip = lambda: weight.detach().to(dy.dtype).flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last)
+                dx = conv3x3(dy, derived_on_owner(weight, "_fmc_w_flip", None, flip) if ctx.shadow else flip(), None)
             if ctx.needs_input_grad[1]:
-                dw = conv3x3_weight_grad(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)).to(weight.dtype)
+                dw = conv3x3_weight_grad(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)).to(ctx.dtypes[0])
             if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = dy.sum(dim=(0, 2, 3), dtype=torch.float32).to(weight.dtype)
-        return dx, dw, (db if ctx.has_bias else None)
+                if ctx.shadow and dy.dtype == torch.bfloat16:
+                    db = column_sum(dy.permute(0, 2, 3, 1).reshape(-1, dy.shape[1])).to(ctx.dtypes[1])
+                else:
+                    db = dy.sum(dim=(0, 2, 3), dtype=torch.float32).to(ctx.dtypes[1])
+        return dx, dw, (db if ctx.has_bias else None), None, None
 
 
-def conv3x3_trainable(x, weight, bias=None):
-    return _Conv3x3Trainable.apply(x, weight, bias)
+def conv3x3_trainable(x, weight, bias=None, w_run=None, b_run=None):
+    """3x3 / stride 1 / pad 1 convolution whose filter trains (see `_Conv3x3Trainable`).  `w_run` / `b_run`: the filter / bias in x's dtype
+    (cached bf16 shadows of fp32 masters, `layers.bf16_param`): their channels-last and flipped forms are then derived once per version
+    and the bias gradient is `column_sum`; default: a cast per call."""
+    return _Conv3x3Trainable.apply(x, weight, bias, w_run, b_run)
+
+
+# --------------------------------------------------------------------------------------------
+# the small passes of a Camera-Encoder / OMC-Adapter training step (csrc/train_elementwise.hip)
+# --------------------------------------------------------------------------------------------
+def _avgpool2x2_raw(x_nhwc: torch.Tensor) -> torch.Tensor:
+    n, h, w, c = x_nhwc.shape
+    y = torch.empty(n, h // 2, w // 2, c, dtype=x_nhwc.dtype, device=x_nhwc.device)
+    _lib.check(_lib.load().fmc_avgpool2x2_fwd(x_nhwc.data_ptr(), y.data_ptr(), n, h, w, c, _stream()), "fmc_avgpool2x2_fwd")
+    return y
+
+
+class _AvgPool2x2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_nhwc):
+        ctx.shape = tuple(x_nhwc.shape)
+        return _avgpool2x2_raw(x_nhwc)
+
+    @staticmethod
+    def backward(ctx, dy):
+        n, h, w, c = ctx.shape
+        dy = dy.contiguous()
+        dx = torch.empty(ctx.shape, dtype=dy.dtype, device=dy.device)
+        _lib.check(_lib.load().fmc_avgpool2x2_bwd(dy.data_ptr(), dx.data_ptr(), n, h, w, c, _stream()), "fmc_avgpool2x2_bwd")
+        return dx
+
+
+def avg_pool2x2(x: torch.Tensor) -> torch.Tensor:
+    """`AvgPool2d(kernel_size=2, stride=2)` of a logical NCHW / physical channels-last bf16 tensor (C % 8 == 0; odd sizes floor), with its
+    backward, on `fmc_avgpool2x2_fwd / _bwd`.  Returns a logical NCHW view over channels-last storage."""
+    _dev(x)
+    assert x.dtype == torch.bfloat16 and x.ndim == 4 and x.shape[1] % 8 == 0, "avg_pool2x2: bf16 [N, C, H, W] with C % 8 == 0"
+    t = x.permute(0, 2, 3, 1)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    y = _AvgPool2x2.apply(t) if (torch.is_grad_enabled() and t.requires_grad) else _avgpool2x2_raw(t)
+    return y.permute(0, 3, 1, 2)
+
+
+def _dense(t: torch.Tensor) -> torch.Tensor:
+    """t itself when its elements fill one block of memory in some order (contiguous or channels-last), else a contiguous copy."""
+    return t if (t.is_contiguous() or (t.ndim == 4 and t.is_contiguous(memory_format=torch.channels_last))) else t.contiguous()
+
+
+def _relu_raw(x: torch.Tensor) -> torch.Tensor:
+    y = torch.empty_like(x)              # (preserve_format: the strides of a dense x)
+    _lib.check(_lib.load().fmc_relu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "fmc_relu_fwd")
+    return y
+
+
+class _Relu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        y = _relu_raw(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        if dy.stride() != y.stride():
+            dy = torch.empty_like(y).copy_(dy)
+        dx = torch.empty_like(y)
+        _lib.check(_lib.load().fmc_relu_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), y.numel(), _stream()), "fmc_relu_bwd")
+        return dx
+
+
+def relu(x: torch.Tensor) -> torch.Tensor:
+    """ReLU of a bf16 device tensor (contiguous or channels-last: the output keeps the layout) with `dx = dy * (y > 0)`, on
+    `fmc_relu_fwd / _bwd`."""
+    _dev(x)
+    assert x.dtype == torch.bfloat16, "relu: bf16 only"
+    x = _dense(x)
+    if x.numel() == 0:
+        return x
+    return _Relu.apply(x) if (torch.is_grad_enabled() and x.requires_grad) else _relu_raw(x)
+
+
+def _add_raw(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    out = torch.empty_like(a)
+    _lib.check(_lib.load().fmc_add_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream()), "fmc_add_bf16")
+    return out
+
+
+class _Add(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        return _add_raw(a, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (dy if ctx.needs_input_grad[0] else None), (dy if ctx.needs_input_grad[1] else None)
+
+
+def add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """`a + b` for two bf16 device tensors of one shape (the fp32 sum rounded once) on `fmc_add_bf16`; both gradients are dY."""
+    _dev(a, b)
+    assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.shape == b.shape, "add: two bf16 tensors of one shape"
+    a = _dense(a)
+    if b.stride() != a.stride():
+        b = torch.empty_like(a).copy_(b)
+    if a.numel() == 0:
+        return a
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        return _Add.apply(a, b)
+    return _add_raw(a, b)
 
 
 # --------------------------------------------------------------------------------------------

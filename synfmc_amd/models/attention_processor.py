@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import hip_ops as K
-from .layers import LoRALinearLayer, linear_op
+from .layers import OWN_MARK, TRAINABLE_OWN, LoRALinearLayer, bf16_param, linear_op, own_linear, own_trainable, shadow_twin
 
 
 _POSE_TERM = os.environ.get("FMC_NO_POSE_TERM", "0") != "1"      # A/B switch for the pre-computed Camera-Adapter term
@@ -44,6 +44,21 @@ def _attention_core(attn, q_in: torch.Tensor, kv_in: Optional[torch.Tensor], tem
     """Fused projection -> attention kernel -> output projection (bias, dropout p=0) [+ residual].  `qkv_fold` = (W', term) of
     `_PoseMerge._qkv_fold`: q | k | v = `q_in W'^T + term` (q_in = the UN-merged tokens)."""
     heads = attn.heads
+    if own_trainable(attn.to_q, q_in) and attn.__dict__.get(OWN_MARK, False):
+        # a marked attention module with fp32 masters on bf16 tokens (the Camera Encoder's temporal blocks, `training.camera_trainable_parameters`)
+        assert lora is None and qkv_fold is None, "a marked attention module takes plain processors"
+        if not torch.is_grad_enabled():
+            real, attn = attn, shadow_twin(attn)        # the forward of the bf16 shadows: everything below as for bf16 storage
+            for k in ("_next_ln", "_lazy_res"):         # (what the block has set on the module for this call)
+                attn.__dict__[k] = real.__dict__.get(k)
+        elif kv_in is None and not attn.is_cross and attn.to_q.bias is None:
+            w_qkv, w_qkv_run, w_o_run, b_o_run = attn.fused_trainable()
+            qkv = own_linear(q_in, w_qkv, None, w_qkv_run, None)
+            o = K.self_attention_qkv(qkv, heads, attn.scale, temporal)
+            out = attn.to_out[0]
+            return own_linear(o, out.weight, out.bias, w_o_run, b_o_run, residual)
+        else:
+            raise NotImplementedError("a marked attention module under a gradient: self attention without projection biases only")
     w_a, w_b, w_o = attn.fused_weights(lora, lora_scale)
     if qkv_fold is not None:
         assert kv_in is None
@@ -199,10 +214,25 @@ class _PoseMerge:
         nn.init.zeros_(layer.bias)
         setattr(self, name, layer)
 
+    def merge_wb(self, x):
+        """`qkv_merge`'s weight and bias as the kernels read them: the bf16 shadows of marked fp32 masters on bf16 tokens
+        (`training.camera_trainable_parameters`), else the parameters themselves."""
+        mrg = self.qkv_merge
+        if own_trainable(mrg, x):
+            return bf16_param(mrg, "weight"), bf16_param(mrg, "bias")
+        return mrg.weight, mrg.bias
+
     def _merge(self, hidden_states, encoder_hidden_states, pose_feature, s):
         """`merge(h + pose) * s + h` (attention_processor.py:256-265)."""
         if self.query_condition and self.key_value_condition:
-            w, b = self.qkv_merge.weight, self.qkv_merge.bias
+            if torch.is_grad_enabled() and own_trainable(self.qkv_merge, hidden_states) and pose_feature.dtype == torch.bfloat16 \
+                    and pose_feature.shape == hidden_states.shape:
+                # a marked merge with fp32 masters under a gradient: m = s ((h + pose) W^T + b) + h as one add and one GEMM with the scale and the
+                # residual in its epilogue; dW = s dm^T hp, db = s colsum(dm), d(hp) = s dm W feeds h and pose, h also receives dm (linear_trainable)
+                hp = K.add(hidden_states, pose_feature) if TRAINABLE_OWN else hidden_states + pose_feature
+                mrg = self.qkv_merge
+                return own_linear(hp, mrg.weight, mrg.bias, bf16_param(mrg, "weight"), bf16_param(mrg, "bias"), hidden_states, s), None
+            w, b = (self.qkv_merge.weight, self.qkv_merge.bias) if torch.is_grad_enabled() else self.merge_wb(hidden_states)
             if (_POSE_TERM and not torch.is_grad_enabled() and hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16
                     and w.dtype == torch.bfloat16 and pose_feature.shape == hidden_states.shape
                     and pose_feature.dtype == torch.bfloat16 and hidden_states.is_contiguous()):
@@ -242,7 +272,7 @@ def _qkv_fold_impl(self, attn, x, pose_feature, s, lora=None, lora_scale: float 
     per block and step) and the round trip of m are gone: 96.9 -> 62.1 us at M = 5120, 47.5 -> 22.0 us at M = 1280 (tools/scratch/r05/bench_fold.py).
     Returns (W', term) or None where the plain chain must run (training, fp32, fp8 projections, a layout mismatch, FMC_MERGE_FOLD=0).  The entry keeps
     the tensors the graph runner refreshes in place for a new clip (`_GraphedUNet.set_conditioning`)."""
-    w, b = self.qkv_merge.weight, self.qkv_merge.bias
+    w, b = self.merge_wb(x)
     if not (_MERGE_FOLD and _POSE_TERM and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
             and pose_feature.shape == x.shape and pose_feature.dtype == torch.bfloat16 and x.is_contiguous()
             and attn.inner_dim >= MERGE_FOLD_MIN_DIM and attn.__dict__.get("_fp8_scales") is None):

@@ -103,6 +103,108 @@ def bf16_shadow_mark_fresh(mod: nn.Module, name: str) -> None:
         hit[0] = (p.data_ptr(), p._version)
 
 
+# ----------------------------------------------------------------------------
+# trainable modules on the own kernels (Camera Encoder, Camera-Adapter merges, OMC Adapter: training.camera_trainable_parameters /
+# omc_trainable_parameters): fp32 masters, bf16 activations, no autocast
+# ----------------------------------------------------------------------------
+TRAINABLE_OWN = os.environ.get("FMC_TRAINABLE_OWN", "1") != "0"      # A/B switch: marked modules train on the own kernels (else torch ops on cast weights)
+OWN_MARK = "_fmc_train_own"                                          # the attribute `training.mark_trainable_own` sets on every module of the subtree
+
+
+def own_trainable(mod: nn.Module, x: torch.Tensor, p: Optional[torch.Tensor] = None) -> bool:
+    """`mod` is marked, x is a bf16 device tensor and the parameter `p` (default `mod.weight`) is an fp32 master: the new route's domain."""
+    if not mod.__dict__.get(OWN_MARK, False) or not (x.is_cuda and x.dtype == torch.bfloat16):
+        return False
+    p = getattr(mod, "weight", None) if p is None else p
+    return p is not None and p.dtype == torch.float32
+
+
+def own_linear(x, weight, bias, w_run, b_run, residual=None, alpha: float = 1.0, x2=None, **kw):
+    """`alpha * (x W^T + b) + residual` of a marked projection: fp32 masters `weight` / `bias` (or a tensor built from masters inside
+    autograd), their bf16 shadows `w_run` / `b_run`.  Without a gradient the bf16 route of `linear_op` on the shadows: what the same
+    values stored in bf16 compute.  Under a gradient `hip_ops.linear_trainable` (forward, dX, dW, db on the own kernels), or, with
+    FMC_TRAINABLE_OWN=0, torch ops on differentiably cast weights."""
+    if not torch.is_grad_enabled():
+        return linear_op(x, w_run, b_run, residual, alpha, x2, **kw)
+    x = K.resolve_pending_ln(K.resolve_pending_add(x)) if getattr(x, "_fmc_pending_ln", None) is not None else K.resolve_pending_add(x)
+    if residual is not None:
+        residual = K.resolve_pending_add(residual)
+    if x2 is not None:
+        x = torch.cat([x, x2], dim=-1)
+    if not TRAINABLE_OWN:
+        y = F.linear(x, weight.to(x.dtype), None if bias is None else bias.to(x.dtype))
+        if alpha != 1.0:
+            y = y * alpha
+        return y if residual is None else y + residual
+    if x.ndim > 2 and not x.is_contiguous():
+        x = x.contiguous()
+    return K.linear_trainable(x, weight, bias, residual, w_run=w_run, b_run=b_run, alpha=alpha)
+
+
+_MODULE_INTERNALS = frozenset(nn.Module().__dict__)        # nn.Module's own bookkeeping (`_parameters`, hooks, `training` ...)
+
+
+def _plain(v) -> bool:
+    """A configuration value (number, string, None, or a tuple / list of such): what a twin may copy from a private attribute."""
+    return isinstance(v, (int, float, str, bool, type(None), torch.dtype)) or (isinstance(v, (tuple, list)) and all(_plain(e) for e in v))
+
+
+def _twin_attrs(m: nn.Module) -> dict:
+    """What a twin of `m` carries over from `m.__dict__`: every public attribute, and the private ones that hold plain configuration
+    (`nn.Conv2d._reversed_padding_repeated_twice` ...).  Not the mark, and no private attribute that holds tensors or objects: those are
+    this library's per-module caches (`derived`, `_bf16_shadow`, `_pose_term_cache` ...) and per-call notes (`_next_ln`), which belong to
+    the module they were made for.  A class that needs another private attribute in its no-grad forward has to be added here."""
+    return {k: v for k, v in m.__dict__.items()
+            if k not in _MODULE_INTERNALS and k != OWN_MARK and (not k.startswith("_") or _plain(v))}
+
+
+def _twin_signature(mod: nn.Module):
+    """Everything a twin was built from, by identity: the modules, their carried attributes, buffers and parameters.  A processor that
+    was replaced, a changed `scale` or `training` flag, a buffer or parameter that `.to(...)` replaced: the twin is rebuilt."""
+    sig = []
+    for m in mod.modules():
+        sig.append((id(m), m.training,
+                    tuple((k, v if _plain(v) else id(v)) for k, v in _twin_attrs(m).items()),
+                    tuple((k, id(b)) for k, b in m._buffers.items()),
+                    tuple((k, id(p), None if p is None else (p.dtype, p.device)) for k, p in m._parameters.items())))
+    return sig
+
+
+def shadow_twin(mod: nn.Module) -> nn.Module:
+    """The no-grad forward of a marked module with fp32 masters: a twin of the module tree -- same classes, the attributes of
+    `_twin_attrs`, the same buffers -- whose fp32 parameters are replaced by their in-place refreshed bf16 shadows (`bf16_param`).  Its
+    forward is the forward of the same values stored in bf16, bit for bit, fused kernels included; every derived-weight cache of the
+    twin is keyed on the shadows' versions, which a refresh bumps.  Cached on the module and rebuilt when `_twin_signature` moves.
+    A twin is for `forward` only: its parameters are plain attributes (the shadows are not `nn.Parameter`s of anything), so
+    `parameters()`, `state_dict()` and `.to()` of a twin are empty / no-ops by design."""
+    sig = _twin_signature(mod)
+    hit = mod.__dict__.get("_own_twin")
+    if hit is None or hit[2] != sig:
+        links = []
+
+        def build(m):
+            t = m.__class__.__new__(m.__class__)
+            nn.Module.__init__(t)
+            t.__dict__.update(_twin_attrs(m))
+            t.training = m.training
+            for k, b in m._buffers.items():
+                t._buffers[k] = b
+            for k, p in m._parameters.items():
+                if p is not None and p.dtype == torch.float32:
+                    links.append((m, k, t))
+                else:
+                    t.__dict__[k] = p
+            for k, c in m._modules.items():
+                t._modules[k] = None if c is None else build(c)
+            return t
+        hit = (build(mod), links, sig)
+        mod.__dict__["_own_twin"] = hit
+    twin, links, _ = hit
+    for m, k, t in links:
+        t.__dict__[k] = bf16_param(m, k)
+    return twin
+
+
 class GroupNorm(nn.GroupNorm):
     """nn.GroupNorm on a `[N, C, h, w]` tensor, optionally fused with SiLU (`fmc_groupnorm_silu_fwd`)."""
 
@@ -187,6 +289,8 @@ class Conv2d(nn.Conv2d):
             assert temb is None and residual is None and not upsample and x2 is None
             return K.conv3x3(x, self._weight_cl(), self.bias, emit_gn=emit_gn,
                              shortcut=(xs, xs2, sc.weight.view(sc.out_channels, sc.in_channels), sc.bias))
+        if own_trainable(self, x):
+            return self._forward_own(x, temb, residual, temb_div, upsample, x2, emit_gn)
         if self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0):
             n, c, h, w = x.shape
             assert temb is None
@@ -243,6 +347,34 @@ class Conv2d(nn.Conv2d):
         if residual is not None:
             y = y + residual
         return y
+
+    def _forward_own(self, x, temb, residual, temb_div, upsample, x2, emit_gn):
+        """A marked convolution with fp32 masters on bf16 activations (`own_trainable`).  Without a gradient: the forward of the bf16
+        shadows (`shadow_twin`).  Under a gradient: a 1x1 as a token GEMM on `linear_trainable`, a 3x3 / stride 1 / pad 1 with channel
+        counts that are multiples of 64 on `conv3x3_trainable`, both reading the cached shadows; any other form (a stride-2 3x3, thin
+        channels, a time embedding) and FMC_TRAINABLE_OWN=0 take torch ops on differentiably cast weights."""
+        if not torch.is_grad_enabled():
+            return shadow_twin(self)(x, temb=temb, residual=residual, temb_div=temb_div, upsample=upsample, x2=x2, emit_gn=emit_gn)
+        if self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and temb is None and not upsample:
+            n, c, h, w = x.shape
+            y = own_linear(to_tokens(x), self.weight.view(self.out_channels, self.in_channels), self.bias,
+                           bf16_param(self, "weight").view(self.out_channels, self.in_channels), bf16_param(self, "bias"),
+                           None if residual is None else to_tokens(residual), 1.0, None if x2 is None else to_tokens(x2))
+            return from_tokens(y, h, w)
+        assert x2 is None, "two-source input: 1x1 convs only"
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        if (TRAINABLE_OWN and not upsample and temb is None and residual is None and self.kernel_size == (3, 3) and self.stride == (1, 1)
+                and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and self.in_channels % 64 == 0
+                and self.out_channels % 64 == 0):
+            return K.conv3x3_trainable(x, self.weight, self.bias, bf16_param(self, "weight"), bf16_param(self, "bias"))
+        if upsample:
+            x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+        y = F.conv2d(x, self.weight.to(x.dtype), None if self.bias is None else self.bias.to(x.dtype), self.stride, self.padding,
+                     self.dilation, self.groups)
+        if temb is not None:
+            y = y + (temb if temb_div == 1 else temb.repeat_interleave(temb_div, dim=0))[:, :, None, None]
+        return y if residual is None else y + residual
 
     def padded_conv3x3(self, x: torch.Tensor) -> torch.Tensor:
         """The edge convolutions (U-Net conv_in 4 -> 320 / conv_out 320 -> 4, VAE conv_in / conv_out) on the hand-written implicit-GEMM kernel:
@@ -306,6 +438,8 @@ def linear_op(x, weight, bias=None, residual=None, alpha: float = 1.0, x2=None, 
 
 class Linear(nn.Linear):
     def forward(self, x: torch.Tensor, scale: float = 1.0, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if own_trainable(self, x):
+            return own_linear(x, self.weight, self.bias, bf16_param(self, "weight"), bf16_param(self, "bias"), residual)
         return linear_op(x, self.weight, self.bias, residual)
 
 
@@ -612,6 +746,16 @@ class Attention(nn.Module):
         self.__dict__["_text_kv"] = entry
         return entry
 
+    def fused_trainable(self):
+        """Self attention with fp32 masters on the own training route: `(W_qkv, its bf16 shadow, shadow of W_out, shadow of b_out)`.
+        The `cat` of the three masters is built inside autograd, so the fused dW splits back into `to_q` / `to_k` / `to_v` there; the
+        kernels read ONE cached bf16 shadow of the fused weight, keyed on the three per-parameter shadows, which `bf16_param` (or the
+        fused optimizer) refreshes in place when a master's version moves."""
+        sq, sk, sv = (bf16_param(m, "weight") for m in (self.to_q, self.to_k, self.to_v))
+        w_run = derived(self, "_fused_run", [sq, sk, sv], lambda: torch.cat([sq, sk, sv], dim=0).contiguous())
+        w = torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0)
+        return w, w_run, bf16_param(self.to_out[0], "weight"), bf16_param(self.to_out[0], "bias")
+
     # ---- fused projection weights (cached; rebuilt when any source parameter changes) ----------------
     def fused_weights(self, lora=None, lora_scale: float = 1.0):
         """(W_qkv `[3C, Cin]` for self attention | (W_q, W_kv) for cross attention, W_out, b_out) with an
@@ -720,6 +864,8 @@ class FeedForward(nn.Module):
 
     def forward(self, hidden_states, scale: float = 1.0, residual: Optional[torch.Tensor] = None):
         proj, out = self.net[0], self.net[2]
+        if not torch.is_grad_enabled() and own_trainable(out, hidden_states):
+            return shadow_twin(self)(hidden_states, residual=residual)      # marked fp32 masters without a gradient: the forward of the bf16 shadows
         il = proj.interleaved() if (hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16 and not torch.is_grad_enabled()) else None
         if il is not None and K.ff_blocked_ok(hidden_states, il[2], out.weight, residual):
             # the [M, 4C] intermediate stays tile-major between the two GEMMs: contiguous 10-KiB operand blocks for the second one

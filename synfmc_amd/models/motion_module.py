@@ -161,7 +161,7 @@ class TemporalTransformerBlock(nn.Module):
                 return False
             if isinstance(proc, (PoseAdaptorAttnProcessor, LORAPoseAdaptorAttnProcessor)):
                 pf = cross_attention_kwargs.get("pose_feature")
-                if pf is None or not (proc.query_condition and proc.key_value_condition) or proc.qkv_merge.weight.dtype != torch.bfloat16:
+                if pf is None or not (proc.query_condition and proc.key_value_condition) or proc.merge_wb(hidden_states)[0].dtype != torch.bfloat16:
                     return False
                 # (what the un-fused `_merge` falls back on -- a pose feature of another dtype or shape -- must fall back here too)
                 if pf.dtype != torch.bfloat16 or not pf.is_cuda:
@@ -226,7 +226,7 @@ class TemporalTransformerBlock(nn.Module):
                 s = proc.scale if isinstance(proc, LORAPoseAdaptorAttnProcessor) else (cross_attention_kwargs.get("scale") or proc.scale)
                 pose = _pose_tokens(cross_attention_kwargs["pose_feature"], h)
                 assert pose.shape == h.shape, "pose_feature does not match the hidden states"
-                wm, bm = proc.qkv_merge.weight, proc.qkv_merge.bias
+                wm, bm = proc.merge_wb(h)               # (the bf16 shadows of marked fp32 masters)
                 kw = dict(w_merge_tm=self._merge_packed(proc, wm), pose_term=proc._pose_term(pose, wm, bm, s), merge_scale=s)
             # (row statistics for the feed-forward's LayerNorm-in-GEMM: the 40x64 level, and only while the feed-forward does not normalise its input itself)
             last = i == n_blocks - 1 and h.shape[-1] == 320 and not K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight)

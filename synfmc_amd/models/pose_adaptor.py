@@ -14,7 +14,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .layers import Conv2d, from_tokens, to_tokens
+from .. import hip_ops as K
+from .layers import OWN_MARK, TRAINABLE_OWN, Conv2d, from_tokens, shadow_twin, to_tokens
 from .motion_module import TemporalTransformerBlock
 from .resnet import _frames_first
 
@@ -39,6 +40,13 @@ def avg_pool_nd(dims, *args, **kwargs):
     raise ValueError(f"unsupported dimensions: {dims}")
 
 
+def _own_elementwise(mod: nn.Module, x: torch.Tensor) -> bool:
+    """The average pool, ReLU and residual add of a marked module (`training.camera_trainable_parameters` / `omc_trainable_parameters`)
+    run on `csrc/train_elementwise.hip`: bf16 device activations under a gradient.  Everything else -- and every forward without a
+    gradient, which must equal the bf16-stored model bit for bit -- keeps the torch ops."""
+    return (TRAINABLE_OWN and mod.__dict__.get(OWN_MARK, False) and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16)
+
+
 class Downsample(nn.Module):
     """stride-2 conv or 2x2 average pool (pose_adaptor.py:75-99)."""
 
@@ -56,6 +64,8 @@ class Downsample(nn.Module):
         assert x.shape[1] == self.channels
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
+        if not self.use_conv and _own_elementwise(self, x) and x.shape[1] % 8 == 0:
+            return K.avg_pool2x2(x)
         return self.op(x)
 
 
@@ -80,6 +90,9 @@ class ResnetBlock(nn.Module):
             x = self.down_opt(x)
         if self.in_conv is not None:
             x = self.in_conv(x)
+        if _own_elementwise(self, x):
+            h = self.block2(K.relu(self.block1(x)))
+            return K.add(h, self.skep(x) if self.skep is not None else x)
         h = self.block2(F.relu(self.block1(x)))
         return h + (self.skep(x) if self.skep is not None else x)
 
@@ -128,13 +141,23 @@ class CameraPoseEncoder(nn.Module):
         bs = x.shape[0]
         x4, _, _ = _frames_first(x)
         x4 = self.unshuffle(x4)
-        return self._encode(x4.to(self.dtype), bs)
+        return self._encode(x4.to(self._act_dtype(x4)), bs)
+
+    def _act_dtype(self, x) -> torch.dtype:
+        """What the input is cast to: the parameter dtype; for a marked encoder (fp32 masters, `training.camera_trainable_parameters`)
+        fed bf16 device activations, bf16 -- the own training route runs without autocast."""
+        if self.__dict__.get(OWN_MARK, False) and x.is_cuda and x.dtype == torch.bfloat16:
+            return torch.bfloat16
+        return self.dtype
 
     def forward_unshuffled(self, x_cl: torch.Tensor, bs: int):
         """x_cl: `[(b f), h, w, cin]` channels-last, PixelUnshuffle already applied (`fmc_plucker_fwd` layout 2)."""
-        return self._encode(x_cl.permute(0, 3, 1, 2).to(self.dtype), bs)
+        return self._encode(x_cl.permute(0, 3, 1, 2).to(self._act_dtype(x_cl)), bs)
 
     def _encode(self, x4, bs):
+        if (not torch.is_grad_enabled() and self.__dict__.get(OWN_MARK, False) and x4.is_cuda and x4.dtype == torch.bfloat16
+                and self.dtype == torch.float32):
+            return shadow_twin(self)._encode(x4, bs)        # fp32 masters without a gradient: the forward of their bf16 shadows
         features = []
         x4 = self.encoder_conv_in(x4)
         for res_block, attention_block in zip(self.encoder_down_conv_blocks, self.encoder_down_attention_blocks):

@@ -697,3 +697,63 @@ def motion_module_state_dict(unet) -> dict:
     `load_state_dict(..., strict=False)` and no unexpected keys.  (The reference's `mm_state_dict`, train_cam_ctrl.py:679-681, compares
     state-dict keys with module names and therefore saves an empty dict; this writes what it evidently intends.)"""
     return {name: p.detach().clone() for name, p in _motion_module_parameters(unet)}
+
+
+# ---- stages 2 and 3 on the own kernels: Camera Encoder, Camera-Adapter merges, OMC Adapter as fp32 masters ------------------------------
+def mark_trainable_own(module: torch.nn.Module) -> None:
+    """Set the mark (`layers.OWN_MARK`) on `module` and every module below it: their forward then takes the own training route for bf16
+    device activations -- fp32 masters read through bf16 shadows, no autocast (`layers.own_trainable`).  `FMC_TRAINABLE_OWN=0` sends
+    the marked modules back to torch ops on cast weights."""
+    from .models.layers import OWN_MARK
+    for m in module.modules():
+        m.__dict__[OWN_MARK] = True
+
+
+def _masters(params) -> List[torch.nn.Parameter]:
+    for p in params:
+        if p.dtype != torch.float32:
+            p.data = p.data.float()
+        p.requires_grad_(True)
+    return params
+
+
+def camera_trainable_parameters(unet, pose_encoder) -> List[torch.nn.Parameter]:
+    """The stage-2 parameters -- the same tensors in the same order as `stage2_trainable_parameters` -- turned into fp32 masters that
+    require grad, and their modules (the whole Camera Encoder, every attention processor that owns a merge layer) marked for the own
+    training route: run the step with bf16 activations and NO autocast.  The encoder then casts its input to bf16; forward, dX, dW and db of
+    every projection, 1x1 and 3x3 convolution, the GEGLU feed-forwards, the average pools, ReLUs and the merges run on this library's
+    kernels, reading cached bf16 shadows (`layers.bf16_param`) that `FusedAdamW.attach(unet, pose_encoder)` refreshes in its update.
+    Buffers keep their dtype.  Not covered: `Downsample(use_conv=True)` (torch ops on cast weights), fp32 activations (the torch route as before); a U-Net with `q_merge` / `kv_merge`
+    processors is refused."""
+    partial = [n for n, m in unet.named_modules() if hasattr(m, "q_merge") or hasattr(m, "kv_merge")]
+    if partial:
+        raise NotImplementedError("camera_trainable_parameters: the q-only / kv-only Camera-Adapter merges (`q_merge` / `kv_merge`, configurations "
+                                  f"that do not ship) have no own training route, e.g. {partial[0]}; train them with `stage2_trainable_parameters` "
+                                  "under autocast")
+    params = _masters(stage2_trainable_parameters(unet, pose_encoder))
+    mark_trainable_own(pose_encoder)
+    for m in unet.modules():
+        if hasattr(m, "qkv_merge"):
+            mark_trainable_own(m)
+    return params
+
+
+def omc_trainable_parameters(omcm) -> List[torch.nn.Parameter]:
+    """The OMC Adapter's parameters (stage 3) as fp32 masters that require grad, the Adapter marked for the own training route (see
+    `camera_trainable_parameters`): `get_traj_features_v2(..., omcm, ..., dtype=torch.bfloat16)` without autocast."""
+    params = _masters(list(omcm.parameters()))
+    mark_trainable_own(omcm)
+    return params
+
+
+def camera_state_dict(unet, pose_encoder) -> dict:
+    """The stage-2 checkpoint in the reference's keys and split (train_cam_ctrl.py:671-678): `pose_encoder_state_dict` is the encoder's
+    `state_dict()`, `attention_processor_state_dict` the U-Net entries of the trainable merge layers (names containing `merge`, no
+    `lora`).  Both load into a bf16 model with `load_state_dict(..., strict=False)` and no unexpected keys."""
+    return {"pose_encoder_state_dict": {k: v.detach().clone() for k, v in pose_encoder.state_dict().items()},
+            "attention_processor_state_dict": {k: v.detach().clone() for k, v in unet.state_dict().items() if "merge" in k and "lora" not in k}}
+
+
+def omc_state_dict(omcm) -> dict:
+    """The stage-3 checkpoint entry `omcm_state_dict` (train_cam_obj_ctrl.py:963-968): the Adapter's `state_dict()`."""
+    return {"omcm_state_dict": {k: v.detach().clone() for k, v in omcm.state_dict().items()}}
