@@ -719,6 +719,27 @@ int fmc_xattn_block320_bf16(const void* h, void* out, const float* ln_gamma, con
                             const void* kvfrag, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images, int hw,
                             int n_keys, int images_per_text, float scale, void* stream);
 int fmc_xattn_pack_kv40(const void* kv, void* out, int batch, int S, int64_t ld_batch, void* stream);
+/* ---- the three fused attention blocks above at ANY feature-map size (hw >= 1): partly filled last tiles ------------------------------------------
+ * Same arguments, tensors, weight formats and checks (NULL, alignment, 2 GiB, 1 <= n_keys <= 80, n_images % images_per_text == 0, F = 16, 8 heads,
+ * C = 320 | 640) as fmc_temporal_block_bf16 / fmc_xattn_block640_bf16 / fmc_xattn_block320_bf16; only the divisibility of hw is not asked for.
+ *   temporal: a clip is ceil(hw / 10) tiles of 10 pixels x 16 frames at C = 320, ceil(hw / 5) tiles of 5 pixels at C = 640; the last tile of a clip
+ *     holds hw % 10 (hw % 5) pixels.
+ *   text cross-attention: a segment = the images_per_text * hw consecutive rows that share a text; it is ceil(rows / 160) tiles at C = 320,
+ *     ceil(rows / 80) at C = 640; tile j of segment s starts at row s * rows + 160 j (80 j) and never holds rows of two texts.
+ * The pad rows of a last tile read that tile's last valid pixel / row again (every address stays inside the tensors), are computed, and are never
+ * stored: not to out, not to ln_stats.  Valid rows go through exactly the operations of the whole-tile kernels: padded to whole tiles and run through
+ * the entry points above, the same tokens give the same bits.  The whole-tile entry points keep refusing ragged sizes (FMC_E_SHAPE); callers opt in
+ * (`hip_ops.PARTIAL_TILES`, default off). */
+int fmc_temporal_block_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_tm,
+                                    const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out,
+                                    float* ln_stats, float ln_stats_eps, int n_clips, int frames, int hw, int channels, int heads, float scale,
+                                    void* stream);
+int fmc_xattn_block640_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                    const void* kvfrag, const void* w_out_frag, const void* b_out, int n_images, int hw, int n_keys, int images_per_text,
+                                    float scale, void* stream);
+int fmc_xattn_block320_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                    const void* kvfrag, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images, int hw,
+                                    int n_keys, int images_per_text, float scale, void* stream);
 /* ---- LayerNorm + GEGLU projection of a feed-forward at the 20x32 level, A operand resident (round 4) ----------------------------------------------
  * out[M][cff] = (n W_v^T + b_v) * gelu(n W_g^T + b_g), n = LayerNorm(h): `GEGLU.forward` of diffusers' FeedForward behind norm3 / ff_norm
  * (fmc/models/motion_module.py:295-299; BasicTransformerBlock).  A workgroup keeps its 80 normalised rows in LDS and walks the cff / 320 column chunks

@@ -170,6 +170,12 @@ SIGNATURES = {
     "fmc_xattn_pack_kv40": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "fmc_xattn_block320_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                         c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fmc_temporal_block_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fmc_xattn_block640_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                c_int, c_float, c_void_p]),
+    "fmc_xattn_block320_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                                c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fmc_conv3x3_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
 }

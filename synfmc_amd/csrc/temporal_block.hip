@@ -88,7 +88,11 @@ __device__ __forceinline__ void unpack4(const u32x2& w, float (&o)[4]) {
     } while (0)
 
 // HAS_MERGE: attention block 0 (Camera Adapter); STATS: also emit the (mean, rstd) of the output rows
-template <bool HAS_MERGE, bool STATS, bool XATT = false>
+// PARTIAL: the last tile of a clip (temporal: hw % 10 pixels) or of a text's segment of `images_per_text * hw` rows (XATT: rows % 160) is partly filled.
+// Its pad rows READ the tile's last valid pixel / row (the source address is clamped, so h, the pose term and the residual are only ever read inside the
+// tensors), are computed like any other row -- every row's result depends on its own pixel's 16 frames (temporal) or on itself and the text (XATT) only --
+// and are never stored: not to `out`, not to `ln_stats`.  P.tiles counts the partly filled tiles; nothing else in TBParams changes.
+template <bool HAS_MERGE, bool STATS, bool XATT = false, bool PARTIAL = false>
 __global__ __launch_bounds__(512, 2)
 void temporal_block_kernel(const TBParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -166,45 +170,69 @@ void temporal_block_kernel(const TBParams P) {
         __builtin_amdgcn_sched_barrier(0);                                                                               \
     } while (0)
 
-    const int n_tiles_per_clip = P.hw / TB_PIX;
+    const int n_tiles_per_clip = PARTIAL ? (P.hw + TB_PIX - 1) / TB_PIX : P.hw / TB_PIX;
+    // PARTIAL XATT: a segment = the rows of one text; its tiles start at segment * seg_rows + 160 j and never reach into the next text's rows
+    const int seg_rows = PARTIAL && XATT ? P.images_per_text * P.hw : 0, seg_tiles = PARTIAL && XATT ? (seg_rows + TB_ROWS - 1) / TB_ROWS : 1;
     // tile row r = 16 hi + lo lives at element row0 + lo * fstride + hi * pstride: temporal = (frame lo, pixel hi) of the clip; XATT = row 160 tile + r
     const unsigned fstride = XATT ? (unsigned)TB_C : (unsigned)(P.hw * TB_C), pstride = XATT ? (unsigned)(16 * TB_C) : (unsigned)TB_C;
     auto tile_row0 = [&](int t) {
+        if constexpr (XATT && PARTIAL) {
+            const int seg = t / seg_tiles;
+            return (unsigned)(((int64_t)seg * seg_rows + (int64_t)(t - seg * seg_tiles) * TB_ROWS) * TB_C);
+        }
         if (XATT) return (unsigned)((int64_t)t * TB_ROWS * TB_C);
         const int clip = t / n_tiles_per_clip, p0 = (t - clip * n_tiles_per_clip) * TB_PIX;
         return (unsigned)(((int64_t)clip * TB_F * P.hw + p0) * TB_C);
     };
 
+    // PARTIAL: what tile t holds: valid pixels (temporal, 1..10) or valid rows (XATT, 1..160); tile row r reads source row src_row(r, valid).  Both are
+    // wave-uniform and computed once per tile at the head of the persistent loop, for the tile and for the one the look-ahead requests (the division
+    // would otherwise run on the vector unit in the middle of the epilogue, where every register is taken), and handed to the request helpers.
+    auto tile_valid = [&](int t) {
+        if constexpr (XATT) {
+            const int left = seg_rows - (t % seg_tiles) * TB_ROWS;
+            return left < TB_ROWS ? left : TB_ROWS;
+        } else {
+            const int left = P.hw - (t % n_tiles_per_clip) * TB_PIX;
+            return left < TB_PIX ? left : TB_PIX;
+        }
+    };
+    auto src_row = [&](int r, int nv) {
+        if constexpr (!PARTIAL) return r;
+        else if constexpr (XATT) return r < nv ? r : nv - 1;
+        else return (min(r >> 4, nv - 1) << 4) | (r & 15);
+    };
     // rows [r0, r0 + nr) of a tile of `rs` (h or the pose term) -> LDS at `dst` by LDS-DMA, row-major with X's chunk swizzle (16-byte chunk c of tile
     // row r at chunk c ^ ((r >> 1) & 7): the source address carries it).  nr * 40 chunks = pieces of 64; piece q = wave + 8 j.
-    auto issue_rows = [&](const __amdgpu_buffer_rsrc_t& rs, int t, int r0, int nr, bf16_t* dst) {
+    auto issue_rows = [&](const __amdgpu_buffer_rsrc_t& rs, int t, int r0, int nr, bf16_t* dst, unsigned p_row0, int nv) {
         int ln = lane;
         asm volatile("" : "+v"(ln));                  // (per-tile address arithmetic must not be hoisted out of the persistent loop: 40 live registers)
-        const unsigned row0 = tile_row0(t);
+        const unsigned row0 = PARTIAL ? p_row0 : tile_row0(t);
         const int pieces = nr * 40 / 64;
 #pragma unroll
         for (int j = 0; j < 13; ++j) {
             const int q = wave + 8 * j;
             if (q < pieces) {
-                const int idx = 64 * q + ln, rl = idx / 40, pc = idx - rl * 40, r = r0 + rl, c = pc ^ ((r >> 1) & 7);
-                const unsigned src = (row0 + (unsigned)(r & 15) * fstride + (unsigned)(r >> 4) * pstride + (unsigned)c * 8) * 2;
+                const int idx = 64 * q + ln, rl = idx / 40, pc = idx - rl * 40, r = r0 + rl, c = pc ^ ((r >> 1) & 7), sr = src_row(r, nv);
+                const unsigned src = (row0 + (unsigned)(sr & 15) * fstride + (unsigned)(sr >> 4) * pstride + (unsigned)c * 8) * 2;
                 tb_dma(rs, src, 0, dst + 64 * q * 8);
             }
         }
     };
-    auto issue_h = [&](int t) { issue_rows(rsH, t, 0, TB_ROWS, X); };
+    auto issue_h = [&](int t, unsigned p_row0, int nv) { issue_rows(rsH, t, 0, TB_ROWS, X, p_row0, nv); };
     // epilogue side operand (pose term) of pass p = the rows of accumulator block mb = p of BOTH wave rows (tile rows 16 p .. and 80 + 16 p ..): 32 rows
     // = one 20-KiB ring buffer, rows 0-15 / 16-31, X's swizzle.  20 one-KiB pieces: 3 from waves 0-3, 2 from waves 4-7.
-    auto issue_pass = [&](const __amdgpu_buffer_rsrc_t& rs, int t, int pss, int buf) {
+    auto issue_pass = [&](const __amdgpu_buffer_rsrc_t& rs, int t, int pss, int buf, unsigned p_row0, int nv) {
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const unsigned row0 = tile_row0(t);
+        const unsigned row0 = PARTIAL ? p_row0 : tile_row0(t);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int q = wave + 8 * j;
             if (q < 20) {
                 const int idx = 64 * q + ln, rl = idx / 40, pc = idx - rl * 40, r = (rl < 16 ? 16 * pss + rl : 64 + 16 * pss + rl), c = pc ^ ((r >> 1) & 7);
-                const unsigned src = (row0 + (unsigned)(r & 15) * fstride + (unsigned)(r >> 4) * pstride + (unsigned)c * 8) * 2;
+                const int sr = src_row(r, nv);
+                const unsigned src = (row0 + (unsigned)(sr & 15) * fstride + (unsigned)(sr >> 4) * pstride + (unsigned)c * 8) * 2;
                 tb_dma(rs, src, 0, RING + buf * TB_SUB + 64 * q * 8);
             }
         }
@@ -213,7 +241,7 @@ void temporal_block_kernel(const TBParams P) {
     do {                                                                                                                 \
         if (wave < 4) TB_VMCNT(a); else TB_VMCNT(b);                                                                     \
     } while (0)
-    if ((int)blockIdx.x < P.tiles) issue_h(blockIdx.x);
+    if ((int)blockIdx.x < P.tiles) issue_h(blockIdx.x, PARTIAL ? tile_row0(blockIdx.x) : 0u, PARTIAL ? tile_valid(blockIdx.x) : 0);
     float* stats = reinterpret_cast<float*>(smem_raw + TB_X_ELEMS * 2 + 53248);      // (mean, rstd) x 160 rows: behind the epilogue's staging rows in the ring region
 
     int tslot = -1;
@@ -223,6 +251,15 @@ void temporal_block_kernel(const TBParams P) {
         const int clip = tile / n_tiles_per_clip, p0 = (tile - clip * n_tiles_per_clip) * TB_PIX;
         // global element offset of tile row (pixel p, frame f): ((clip * 16 + f) * hw + p0 + p) * 320
         const unsigned row0 = tile_row0(tile);                                          // (pixel 0, frame 0)
+        int n_valid = 0, next_valid = 0;                                                // PARTIAL: valid pixels (temporal) / rows (XATT) of this tile
+        unsigned next_row0 = 0;                                                         // ... and of the tile the look-ahead requests
+        if constexpr (PARTIAL) {
+            n_valid = __builtin_amdgcn_readfirstlane(tile_valid(tile));
+            if (tile + (int)gridDim.x < P.tiles) {
+                next_valid = __builtin_amdgcn_readfirstlane(tile_valid(tile + gridDim.x));
+                next_row0 = __builtin_amdgcn_readfirstlane(tile_row0(tile + gridDim.x));
+            }
+        }
         // ================= phase A: LayerNorm (+ pe) of the h rows in X, in place =================
         // (the rows were requested under the previous tile's epilogue; the merge's first two weight sub-tiles go out behind the norm's constants)
         __builtin_amdgcn_sched_barrier(0);
@@ -235,9 +272,13 @@ void temporal_block_kernel(const TBParams P) {
         TB_STAMP(1);
         {
             // statistics: 4 lanes per row, the row's 40 chunks in registers, centred variance
+            // (PARTIAL: from an opaque copy of the thread index -- hoisted out of the persistent loop, this loop's row address and counter are what the
+            //  register allocator spills in the merge + statistics instantiation; the whole-tile instantiations keep their code)
+            int tid_s = tid;
+            if constexpr (PARTIAL) asm volatile("" : "+v"(tid_s));
 #pragma unroll 1
-            for (int r = tid >> 2; r < TB_ROWS; r += 128) {
-                const int q = tid & 3;
+            for (int r = tid_s >> 2; r < TB_ROWS; r += 128) {
+                const int q = tid_s & 3;
                 const bf16_t* xr = X + r * TB_C;
                 u32x4 x4[10];
                 float s1 = 0.f;
@@ -324,15 +365,15 @@ void temporal_block_kernel(const TBParams P) {
                 read_frags(g, g % 3);
                 if (g + 2 < 10) issue_w(rsWM, g + 2, (g + 2) % 3);
                 // the ring buffers the weight stream no longer needs take the first pose-term passes (same rule as the stream: the buffer read at LOAD(g - 1))
-                if (g == 8) issue_pass(rsPT, tile, 0, 1);
-                if (g == 9) issue_pass(rsPT, tile, 1, 2);
+                if (g == 8) issue_pass(rsPT, tile, 0, 1, row0, n_valid);
+                if (g == 9) issue_pass(rsPT, tile, 1, 2, row0, n_valid);
                 if (g < 8) TB_VMCNT(4);                           // retires sub-tile g + 1, the one just requested stays in flight
                 else if (g == 8) TB_VMCNT2(3, 2);                 // sub-tile 9; my pieces of pass 0 stay in flight
                 TB_MMA();
             }
             if (wr == 0) __builtin_amdgcn_s_barrier();            // the wave rows meet again: every fragment read of x is done, the ring is free
             __builtin_amdgcn_sched_barrier(0);
-            issue_pass(rsPT, tile, 2, 0);
+            issue_pass(rsPT, tile, 2, 0, row0, n_valid);
             // m = s acc + pose term + x, in place, accumulator block row by block row (pass p = block mb = p of both wave rows).  The pose-term rows
             // arrive in the ring by LDS-DMA (whole 640-byte rows) three passes ahead and are picked up in accumulator layout: as 25 eight-byte
             // global loads per lane they cost the texture path 16 quarter-lines per instruction (3 us of the epilogue), requested under the main
@@ -344,7 +385,7 @@ void temporal_block_kernel(const TBParams P) {
                 else if (pss < 4) TB_VMCNT2(3, 2);
                 else TB_VMCNT(0);
                 __syncthreads();                                  // pass pss published; everybody is done with pass pss - 1
-                if (pss >= 1 && pss + 2 < 5) issue_pass(rsPT, tile, pss + 2, (pss + 3) % 3);      // into the buffer pass pss - 1 has just left
+                if (pss >= 1 && pss + 2 < 5) issue_pass(rsPT, tile, pss + 2, (pss + 3) % 3, row0, n_valid);      // into the buffer pass pss - 1 has just left
                 {
                     const bf16_t* Pt = RING + ((pss + 1) % 3) * TB_SUB + (wr * 16 + l15) * TB_C;
                     bf16_t* Xr = X + (wr * 80 + pss * 16 + l15) * TB_C;
@@ -449,7 +490,7 @@ void temporal_block_kernel(const TBParams P) {
             }
             if constexpr (XATT) {
                 // ---- scores against the text keys (5 blocks of 16, keys >= n_keys masked), softmax and o = P V block by block; K and V^T fragments from the packed copy ----
-                const int batch = (int)(((int64_t)tile * TB_ROWS / P.hw) / P.images_per_text);
+                const int batch = PARTIAL ? tile / seg_tiles : (int)(((int64_t)tile * TB_ROWS / P.hw) / P.images_per_text);
                 const bf16_t* KF = P.kvfrag + ((size_t)batch * 8 + wave) * 7680;
                 bf16x8 ka[5];
                 s16x4 kt[5], vf[3][5];
@@ -604,7 +645,7 @@ void temporal_block_kernel(const TBParams P) {
         if (wr == 0) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         TB_STAMP(6);
-        issue_h(tile);                                            // X (= o) is dead: this tile's h rows come back for the residual add (see phase B)
+        issue_h(tile, row0, n_valid);                             // X (= o) is dead: this tile's h rows come back for the residual add (see phase B)
         {
             // epilogue: wave row `pass` stages its 80 rows (bf16, pitch 328) in the ring region; whole-row stores
             constexpr int OP = 328, CPR = 40;
@@ -635,7 +676,7 @@ void temporal_block_kernel(const TBParams P) {
             __syncthreads();
             // the NEXT tile's h rows stream into X under the staging passes and stores below
             __builtin_amdgcn_sched_barrier(0);
-            if (tile + (int)gridDim.x < P.tiles) issue_h(tile + gridDim.x);
+            if (tile + (int)gridDim.x < P.tiles) issue_h(tile + gridDim.x, next_row0, next_valid);
 #pragma unroll 1
             for (int pass = 0; pass < 2; ++pass) {
                 if (wr == pass) {
@@ -650,6 +691,9 @@ void temporal_block_kernel(const TBParams P) {
                 // staged row rr (0..79) = tile row 80 pass + rr = (pixel 5 pass + rr / 16, frame rr % 16)
                 for (int c = tid; c < 80 * CPR; c += 512) {
                     const int rr = c / CPR, ch = c - rr * CPR;
+                    if constexpr (PARTIAL) {                      // pad rows are not stored
+                        if ((XATT ? 80 * pass + rr : 5 * pass + (rr >> 4)) >= n_valid) continue;
+                    }
                     const unsigned dst = row0 + (unsigned)(rr & 15) * fstride + (unsigned)(5 * pass + (rr >> 4)) * pstride + (unsigned)ch * 8;
                     *reinterpret_cast<u32x4*>(P.out + dst) = *reinterpret_cast<const u32x4*>(Os + rr * OP + ch * 8);
                 }
@@ -674,8 +718,8 @@ void temporal_block_kernel(const TBParams P) {
                             s2 += a * a + b * b;
                         }
                     s2 += __shfl_xor(s2, 1); s2 += __shfl_xor(s2, 2);
-                    if (q == 0) {
-                        const int64_t grow = XATT ? (int64_t)tile * TB_ROWS + 80 * pass + rr : ((int64_t)clip * TB_F + (rr & 15)) * P.hw + p0 + 5 * pass + (rr >> 4);
+                    if (q == 0 && (!PARTIAL || (XATT ? 80 * pass + rr : 5 * pass + (rr >> 4)) < n_valid)) {
+                        const int64_t grow = XATT ? (PARTIAL ? (int64_t)(row0 / TB_C) : (int64_t)tile * TB_ROWS) + 80 * pass + rr : ((int64_t)clip * TB_F + (rr & 15)) * P.hw + p0 + 5 * pass + (rr >> 4);
                         *reinterpret_cast<f32x2_t*>(P.ln_stats + grow * 2) = f32x2_t{mean, rsqrtf(s2 * (1.f / 320.f) + P.ln_stats_eps)};
                     }
                 }
@@ -729,11 +773,12 @@ extern "C" int fmc_xattn_pack_kv40(const void* kv, void* out, int batch, int S, 
 
 // The text cross-attention block of the spatial transformer at the 40x64 level in one launch (see fmc_xattn_block640_bf16): tokens h [images][hw][320],
 // hw % 160 == 0, 8 heads x 40; w_q_packed = hip_ops.pack_xattn_q40, w_out_tm = hip_ops._w_tilemajor, kvfrag = fmc_xattn_pack_kv40; optional row statistics.
-extern "C" int fmc_xattn_block320_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
-                                       const void* kvfrag, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images, int hw,
-                                       int n_keys, int images_per_text, float scale, void* stream) {
+// `partial`: fmc_xattn_block320_partial_bf16 -- any hw >= 1; a text's segment of images_per_text * hw rows ends in a partly filled tile
+static int xattn_block320_run(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed, const void* kvfrag,
+                              const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images, int hw, int n_keys, int images_per_text,
+                              float scale, void* stream, bool partial) {
     if (!h || !out || !ln_gamma || !ln_bpe || !w_q_packed || !kvfrag || !w_out_tm) FMC_FAIL(FMC_E_NULL, "xattn_block320_bf16: NULL tensor");
-    if (n_images <= 0 || hw <= 0 || hw % 160 || n_keys <= 0 || n_keys > 80 || images_per_text <= 0 || n_images % images_per_text)
+    if (n_images <= 0 || hw <= 0 || (!partial && hw % 160) || n_keys <= 0 || n_keys > 80 || images_per_text <= 0 || n_images % images_per_text)
         FMC_FAIL(FMC_E_SHAPE, "xattn_block320_bf16: hw %% 160 == 0, 1 <= keys <= 80, images %% images_per_text == 0 (got hw=%d keys=%d images=%d / %d)", hw, n_keys,
                  n_images, images_per_text);
     if ((int64_t)n_images * hw * 320 * 2 >= ((int64_t)1 << 31)) FMC_FAIL(FMC_E_SHAPE, "xattn_block320_bf16: tensor of 2 GiB or more");
@@ -747,15 +792,37 @@ extern "C" int fmc_xattn_block320_bf16(const void* h, void* out, const float* ln
     P.kvfrag = (const bf16_t*)kvfrag; P.n_keys = n_keys; P.images_per_text = images_per_text;
     P.n_clips = 1; P.hw = hw; P.total_rows = (int64_t)n_images * hw;
     P.tiles = (int)(P.total_rows / TB_ROWS);
+    if (partial) P.tiles = (n_images / images_per_text) * (int)(((int64_t)images_per_text * hw + TB_ROWS - 1) / TB_ROWS);
     P.scale_log2 = scale * 1.4426950408889634f;
     P.dbg_times = nullptr;
     const int cus = fmc_cu_count();
     const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
     // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
-    if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-    else fmc_launch<temporal_block_kernel<false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_xattn_block320_bf16");
+    if (!partial) {
+        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+        else fmc_launch<temporal_block_kernel<false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+    } else {
+        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+        else fmc_launch<temporal_block_kernel<false, true, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
+    }
+    FMC_CHECK_LAUNCH(partial ? "fmc_xattn_block320_partial_bf16" : "fmc_xattn_block320_bf16");
     return 0;
+}
+
+extern "C" int fmc_xattn_block320_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                       const void* kvfrag, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images, int hw,
+                                       int n_keys, int images_per_text, float scale, void* stream) {
+    return xattn_block320_run(h, out, ln_gamma, ln_bpe, ln_eps, w_q_packed, kvfrag, w_out_tm, b_out, ln_stats, ln_stats_eps, n_images, hw, n_keys, images_per_text,
+                              scale, stream, false);
+}
+
+// The same block for any hw >= 1 (see PARTIAL in temporal_block_kernel): the rows of one text (images_per_text * hw) are cut into tiles of 160 of which
+// the last may be partly filled; every other check is fmc_xattn_block320_bf16's.
+extern "C" int fmc_xattn_block320_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                               const void* kvfrag, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps, int n_images,
+                                               int hw, int n_keys, int images_per_text, float scale, void* stream) {
+    return xattn_block320_run(h, out, ln_gamma, ln_bpe, ln_eps, w_q_packed, kvfrag, w_out_tm, b_out, ln_stats, ln_stats_eps, n_images, hw, n_keys, images_per_text,
+                              scale, stream, true);
 }
 
 static long long* g_tb_dbg = nullptr;
@@ -767,12 +834,12 @@ extern "C" int fmc_temporal_block_set_debug(void* buf) {
 
 int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_frag,
                                  const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_frag, const void* b_out,
-                                 int n_clips, int hw, float scale, hipStream_t st);      // temporal_block640.hip
+                                 int n_clips, int hw, float scale, hipStream_t st, bool partial);      // temporal_block640.hip
 
-extern "C" int fmc_temporal_block_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_tm,
-                                       const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out,
-                                       float* ln_stats, float ln_stats_eps, int n_clips, int frames, int hw, int channels, int heads, float scale,
-                                       void* stream) {
+// `partial`: fmc_temporal_block_partial_bf16 -- any hw >= 1; the last tile of a clip holds hw % 10 (C = 640: hw % 5) pixels
+static int temporal_block_run(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_tm, const void* pose_term,
+                              float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps,
+                              int n_clips, int frames, int hw, int channels, int heads, float scale, void* stream, bool partial) {
     if (!h || !out || !ln_gamma || !ln_bpe || !w_qkv_packed || !w_out_tm) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: NULL tensor");
     if (channels == 640 && frames == 16 && heads == 8 && hw > 0 && n_clips > 0) {     // the 20x32 level: its own kernel and weight formats (see fmc_hip.h)
         if ((w_merge_tm != nullptr) != (pose_term != nullptr)) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: w_merge and pose_term come together");
@@ -782,9 +849,9 @@ extern "C" int fmc_temporal_block_bf16(const void* h, void* out, const float* ln
             (w_merge_tm && (!fmc_aligned16(w_merge_tm) || !fmc_aligned16(pose_term))) || (b_out && !fmc_aligned16(b_out)))
             FMC_FAIL(FMC_E_ALIGN, "temporal_block_bf16: tensors must be 16-byte aligned");
         return fmc_temporal_block640_launch(h, out, ln_gamma, ln_bpe, ln_eps, w_merge_tm, pose_term, merge_scale, w_qkv_packed, w_out_tm, b_out, n_clips, hw, scale,
-                                            (hipStream_t)stream);
+                                            (hipStream_t)stream, partial);
     }
-    if (frames != 16 || channels != 320 || heads != 8 || hw <= 0 || hw % 10 || n_clips <= 0)
+    if (frames != 16 || channels != 320 || heads != 8 || hw <= 0 || (!partial && hw % 10) || n_clips <= 0)
         FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: the fused block exists for F = 16, C = 320, 8 heads, pixels %% 10 == 0 (got F=%d C=%d H=%d hw=%d)", frames,
                  channels, heads, hw);
     if ((w_merge_tm != nullptr) != (pose_term != nullptr)) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: w_merge and pose_term come together");
@@ -797,20 +864,49 @@ extern "C" int fmc_temporal_block_bf16(const void* h, void* out, const float* ln
     P.w_merge = (const bf16_t*)w_merge_tm; P.pose_term = (const bf16_t*)pose_term; P.merge_scale = merge_scale;
     P.w_qkv = (const bf16_t*)w_qkv_packed; P.w_out = (const bf16_t*)w_out_tm; P.b_out = (const bf16_t*)b_out;
     P.ln_stats = ln_stats; P.ln_stats_eps = ln_stats_eps;
-    P.n_clips = n_clips; P.hw = hw; P.tiles = n_clips * (hw / 10);
+    P.n_clips = n_clips; P.hw = hw; P.tiles = n_clips * (partial ? (hw + 9) / 10 : hw / 10);
     P.total_rows = (int64_t)n_clips * frames * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
     P.dbg_times = g_tb_dbg;
     const int cus = fmc_cu_count();
     const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
     hipStream_t st = (hipStream_t)stream;
-    if (w_merge_tm) {                                  // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
-        if (!ln_stats) fmc_launch<temporal_block_kernel<true, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        else fmc_launch<temporal_block_kernel<true, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-    } else {
-        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        else fmc_launch<temporal_block_kernel<false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+    if (!partial) {
+        if (w_merge_tm) {                                  // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
+            if (!ln_stats) fmc_launch<temporal_block_kernel<true, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
+            else fmc_launch<temporal_block_kernel<true, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        } else {
+            if (!ln_stats) fmc_launch<temporal_block_kernel<false, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
+            else fmc_launch<temporal_block_kernel<false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        }
+        FMC_CHECK_LAUNCH("fmc_temporal_block_bf16");
+        return 0;
     }
-    FMC_CHECK_LAUNCH("fmc_temporal_block_bf16");
+    if (w_merge_tm) {
+        if (!ln_stats) fmc_launch<temporal_block_kernel<true, false, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        else fmc_launch<temporal_block_kernel<true, true, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+    } else {
+        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+        else fmc_launch<temporal_block_kernel<false, true, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
+    }
+    FMC_CHECK_LAUNCH("fmc_temporal_block_partial_bf16");
     return 0;
+}
+
+extern "C" int fmc_temporal_block_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_tm,
+                                       const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out,
+                                       float* ln_stats, float ln_stats_eps, int n_clips, int frames, int hw, int channels, int heads, float scale,
+                                       void* stream) {
+    return temporal_block_run(h, out, ln_gamma, ln_bpe, ln_eps, w_merge_tm, pose_term, merge_scale, w_qkv_packed, w_out_tm, b_out, ln_stats, ln_stats_eps, n_clips,
+                              frames, hw, channels, heads, scale, stream, false);
+}
+
+// The same block for any hw >= 1 (see PARTIAL in temporal_block_kernel / temporal_block640_kernel): ceil(hw / 10) tiles per clip at C = 320, ceil(hw / 5) at
+// C = 640, the last one partly filled; every other check is fmc_temporal_block_bf16's.
+extern "C" int fmc_temporal_block_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_tm,
+                                               const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out,
+                                               float* ln_stats, float ln_stats_eps, int n_clips, int frames, int hw, int channels, int heads, float scale,
+                                               void* stream) {
+    return temporal_block_run(h, out, ln_gamma, ln_bpe, ln_eps, w_merge_tm, pose_term, merge_scale, w_qkv_packed, w_out_tm, b_out, ln_stats, ln_stats_eps, n_clips,
+                              frames, hw, channels, heads, scale, stream, true);
 }

@@ -63,9 +63,15 @@ __device__ __forceinline__ void t6_unpack4(const u32x2& w, float (&o)[4]) {
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
     } while (0)
+__device__ __forceinline__ int t6_opaque(int v) {              // v, behind a barrier the optimiser does not see through (see issue_rows)
+    asm volatile("" : "+v"(v));
+    return v;
+}
 #define T6_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-template <bool HAS_MERGE, bool XATT>
+// PARTIAL (see temporal_block.hip): the last tile of a clip (temporal: hw % 5 pixels, P.tpc = ceil(hw / 5)) or of a text's segment of
+// frames_per_batch * hw rows (XATT: rows % 80) is partly filled; its pad rows read the tile's last valid pixel / row and are never stored.
+template <bool HAS_MERGE, bool XATT, bool PARTIAL = false>
 __global__ __launch_bounds__(512, 2)
 void temporal_block640_kernel(const T6Params P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -81,7 +87,13 @@ void temporal_block640_kernel(const T6Params P) {
     const int tile = blockIdx.x;
     const int clip = tile / P.tpc, p0 = (tile - clip * P.tpc) * T6_PIX;
     // tile row r = 16 hi + lo lives at element row0 + lo * fstride + hi * pstride: temporal = (frame lo, pixel hi) of the clip; XATT = row 80 tile + r
-    const unsigned row0 = XATT ? (unsigned)((int64_t)tile * T6_ROWS * T6_C) : (unsigned)(((int64_t)clip * T6_F * P.hw + p0) * T6_C);
+    // PARTIAL XATT: a segment = the rows of one text; its tiles start at segment * seg_rows + 80 j and never reach into the next text's rows
+    const int seg_rows = PARTIAL && XATT ? P.frames_per_batch * P.hw : 0, seg_tiles = PARTIAL && XATT ? (seg_rows + T6_ROWS - 1) / T6_ROWS : 1;
+    const int seg = PARTIAL && XATT ? tile / seg_tiles : 0, seg_r0 = PARTIAL && XATT ? (tile - seg * seg_tiles) * T6_ROWS : 0;
+    // PARTIAL: valid pixels (temporal, 1..5) / valid rows (XATT, 1..80) of this tile
+    const int n_valid = !PARTIAL ? 0 : XATT ? (seg_rows - seg_r0 < T6_ROWS ? seg_rows - seg_r0 : T6_ROWS) : (P.hw - p0 < T6_PIX ? P.hw - p0 : T6_PIX);
+    const unsigned row0 = XATT ? (PARTIAL ? (unsigned)(((int64_t)seg * seg_rows + seg_r0) * T6_C) : (unsigned)((int64_t)tile * T6_ROWS * T6_C))
+                               : (unsigned)(((int64_t)clip * T6_F * P.hw + p0) * T6_C);
     const unsigned fstride = XATT ? (unsigned)T6_C : (unsigned)(P.hw * T6_C);
     const unsigned pstride = XATT ? (unsigned)(16 * T6_C) : (unsigned)T6_C;
     const int64_t total_elems = P.total_rows * T6_C;
@@ -91,12 +103,20 @@ void temporal_block640_kernel(const T6Params P) {
     // rows [r0, r0 + nr) of the tile of `rs` -> LDS at `dst`, row-major with X's chunk swizzle; nr * 80 chunks = pieces of 64, piece q = wave + 8 j
     auto issue_rows = [&](const __amdgpu_buffer_rsrc_t& rs, int r0, int nr, bf16_t* dst) {
         const int pieces = nr * T6_CPR / 64;
+        // (PARTIAL: per-lane address arithmetic from an opaque copy of the lane, so that it is redone at each request instead of living through the
+        //  projections -- the registers the clamp below takes would otherwise add to what the merge instantiation spills.  Written as a constant
+        //  choice inside the expression: the whole-tile instantiations keep the parent's instruction stream, which a local copy of `lane` did not)
 #pragma unroll
         for (int j = 0; j < 13; ++j) {
             const int q = wave + 8 * j;
             if (q < pieces) {
-                const int idx = 64 * q + lane, rl = idx / T6_CPR, pc = idx - rl * T6_CPR, r = r0 + rl, c = pc ^ ((r >> 1) & 7);
-                const unsigned src = (row0 + (unsigned)(r & 15) * fstride + (unsigned)(r >> 4) * pstride + (unsigned)c * 8) * 2;
+                const int idx = 64 * q + (PARTIAL ? t6_opaque(lane) : lane), rl = idx / T6_CPR, pc = idx - rl * T6_CPR, r = r0 + rl, c = pc ^ ((r >> 1) & 7);
+                int sr = r;                                       // source row: a pad row reads the tile's last valid pixel / row
+                if constexpr (PARTIAL) {                          // (a 16-row pass of the temporal form is one pixel: its clamp is wave-uniform)
+                    if constexpr (XATT) sr = min(r, n_valid - 1);
+                    else sr = ((nr == 16 ? min(r0 >> 4, n_valid - 1) : min(r >> 4, n_valid - 1)) << 4) | (r & 15);
+                }
+                const unsigned src = (row0 + (unsigned)(sr & 15) * fstride + (unsigned)(sr >> 4) * pstride + (unsigned)c * 8) * 2;
                 t6_dma(rs, src, dst + 64 * q * 8);
             }
         }
@@ -323,7 +343,7 @@ void temporal_block640_kernel(const T6Params P) {
         }
         if constexpr (XATT) {
             // ---- scores against the text keys (5 blocks of 16, keys >= n_keys masked), softmax, o = P V: K and V^T fragments straight from the packed copy ----
-            const int batch = (int)(((int64_t)tile * T6_ROWS / P.hw) / P.frames_per_batch);
+            const int batch = PARTIAL ? seg : (int)(((int64_t)tile * T6_ROWS / P.hw) / P.frames_per_batch);
             const bf16_t* KF = P.kvfrag + ((size_t)batch * 8 + wave) * 12800;
             u32x2 pp[5][5];                                       // probabilities P^T: [query block m][key block]: keys 4 kq .. of query l15
             {
@@ -477,7 +497,8 @@ void temporal_block640_kernel(const T6Params P) {
             bf16_t* Hr = Hs + l15 * T6_C;
 #pragma unroll
             for (int nb = 0; nb < 5; ++nb) {
-                const int col = ecol + nb * 16, off = (((col >> 3) ^ xsw) << 3) + (col & 7);
+                // (PARTIAL: the five offsets are recomputed here; shared with phase B's epilogue they were kept through phase D in scratch)
+                const int col = (PARTIAL ? t6_opaque(ecol) : ecol) + nb * 16, off = (((col >> 3) ^ (PARTIAL ? t6_opaque(xsw) : xsw)) << 3) + (col & 7);
                 u32x2* ph = reinterpret_cast<u32x2*>(Hr + off);
                 float hv[4];
                 t6_unpack4(*ph, hv);
@@ -487,9 +508,12 @@ void temporal_block640_kernel(const T6Params P) {
         __syncthreads();                                          // the 16 finished rows (pixel pss, frames 0-15) are in the pass buffer
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const int c = tid + 512 * j;
+            const int c = (PARTIAL ? t6_opaque(tid) : tid) + 512 * j;      // (see issue_rows)
             if (j < 2 || tid < 256) {                             // 16 rows x 80 chunks = 2.5 x 512
                 const int rl = c / T6_CPR, pc = c - rl * T6_CPR, r = 16 * pss + rl, lc = pc ^ ((r >> 1) & 7);
+                if constexpr (PARTIAL) {                          // pad rows are not stored
+                    if ((XATT ? r : pss) >= n_valid) continue;
+                }
                 const unsigned dst = row0 + (unsigned)(r & 15) * fstride + (unsigned)(r >> 4) * pstride + (unsigned)lc * 8;
                 *reinterpret_cast<u32x4*>(P.out + dst) = *reinterpret_cast<const u32x4*>(Hs + c * 8);
             }
@@ -830,19 +854,24 @@ __global__ __launch_bounds__(256) void xattn_pack_kv_kernel(const bf16_t* __rest
 // called by fmc_temporal_block_bf16 (temporal_block.hip) for channels == 640; the arguments are already checked for NULL / alignment there
 int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_frag,
                                  const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_frag, const void* b_out,
-                                 int n_clips, int hw, float scale, hipStream_t st) {
-    if (hw % 5) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: C = 640 wants pixels %% 5 == 0 (got %d)", hw);
+                                 int n_clips, int hw, float scale, hipStream_t st, bool partial) {
+    if (!partial && hw % 5) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: C = 640 wants pixels %% 5 == 0 (got %d)", hw);
     T6Params P{};
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_bpe = ln_bpe; P.ln_eps = ln_eps;
     P.w_merge = (const bf16_t*)w_merge_frag; P.pose_term = (const bf16_t*)pose_term; P.merge_scale = merge_scale;
     P.w_qkv = (const bf16_t*)w_qkv_packed; P.w_out = (const bf16_t*)w_out_frag; P.b_out = (const bf16_t*)b_out;
-    P.n_clips = n_clips; P.hw = hw; P.tpc = hw / 5;
+    P.n_clips = n_clips; P.hw = hw; P.tpc = partial ? (hw + 4) / 5 : hw / 5;
     P.total_rows = (int64_t)n_clips * T6_F * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
     const unsigned grid = (unsigned)(n_clips * P.tpc);
-    if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
-    else fmc_launch<temporal_block640_kernel<false, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
-    FMC_CHECK_LAUNCH("fmc_temporal_block_bf16 (C = 640)");
+    if (!partial) {
+        if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
+        else fmc_launch<temporal_block640_kernel<false, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
+    } else {
+        if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false, true>>(dim3(grid), dim3(512), T6_LDS, st, P);
+        else fmc_launch<temporal_block640_kernel<false, false, true>>(dim3(grid), dim3(512), T6_LDS, st, P);
+    }
+    FMC_CHECK_LAUNCH(partial ? "fmc_temporal_block_partial_bf16 (C = 640)" : "fmc_temporal_block_bf16 (C = 640)");
     return 0;
 }
 
@@ -850,11 +879,12 @@ int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma
 // fmc/models/unet_blocks.py:323-333 / fmc/models/attention_processor.py:50-69,148-154):   out = to_out(softmax(to_q(LayerNorm(h)) k^T d^-1/2) v) + b + h
 // for tokens h [images][hw][640] (hw % 80 == 0), 8 heads x 80, text k | v packed by fmc_xattn_pack_kv.  Replaces LayerNorm + to_q GEMM + cross-attention
 // kernel + to_out GEMM.  ln_bpe: fp32 [16][640] rows all equal to the LayerNorm beta (the kernel shares phase A with the temporal block).
-extern "C" int fmc_xattn_block640_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
-                                       const void* kvfrag, const void* w_out_frag, const void* b_out, int n_images, int hw, int n_keys, int images_per_text,
-                                       float scale, void* stream) {
+// `partial`: fmc_xattn_block640_partial_bf16 -- any hw >= 1; a text's segment of images_per_text * hw rows ends in a partly filled tile
+static int xattn_block640_run(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed, const void* kvfrag,
+                              const void* w_out_frag, const void* b_out, int n_images, int hw, int n_keys, int images_per_text, float scale, void* stream,
+                              bool partial) {
     if (!h || !out || !ln_gamma || !ln_bpe || !w_q_packed || !kvfrag || !w_out_frag) FMC_FAIL(FMC_E_NULL, "xattn_block640_bf16: NULL tensor");
-    if (n_images <= 0 || hw <= 0 || hw % 80 || n_keys <= 0 || n_keys > 80 || images_per_text <= 0 || n_images % images_per_text)
+    if (n_images <= 0 || hw <= 0 || (!partial && hw % 80) || n_keys <= 0 || n_keys > 80 || images_per_text <= 0 || n_images % images_per_text)
         FMC_FAIL(FMC_E_SHAPE, "xattn_block640_bf16: hw %% 80 == 0, 1 <= keys <= 80, images %% images_per_text == 0 (got hw=%d keys=%d images=%d / %d)", hw, n_keys,
                  n_images, images_per_text);
     if ((int64_t)n_images * hw * 640 * 2 >= ((int64_t)1 << 31)) FMC_FAIL(FMC_E_SHAPE, "xattn_block640_bf16: tensor of 2 GiB or more");
@@ -868,10 +898,29 @@ extern "C" int fmc_xattn_block640_bf16(const void* h, void* out, const float* ln
     P.n_clips = 1; P.hw = hw; P.tpc = 1;
     P.total_rows = (int64_t)n_images * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
-    const unsigned grid = (unsigned)(P.total_rows / T6_ROWS);
-    fmc_launch<temporal_block640_kernel<false, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_xattn_block640_bf16");
+    if (!partial) {
+        const unsigned grid = (unsigned)(P.total_rows / T6_ROWS);
+        fmc_launch<temporal_block640_kernel<false, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
+    } else {
+        const unsigned grid = (unsigned)((n_images / images_per_text) * (((int64_t)images_per_text * hw + T6_ROWS - 1) / T6_ROWS));
+        fmc_launch<temporal_block640_kernel<false, true, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
+    }
+    FMC_CHECK_LAUNCH(partial ? "fmc_xattn_block640_partial_bf16" : "fmc_xattn_block640_bf16");
     return 0;
+}
+
+extern "C" int fmc_xattn_block640_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                       const void* kvfrag, const void* w_out_frag, const void* b_out, int n_images, int hw, int n_keys, int images_per_text,
+                                       float scale, void* stream) {
+    return xattn_block640_run(h, out, ln_gamma, ln_bpe, ln_eps, w_q_packed, kvfrag, w_out_frag, b_out, n_images, hw, n_keys, images_per_text, scale, stream, false);
+}
+
+// The same block for any hw >= 1 (see PARTIAL in temporal_block640_kernel): the rows of one text (images_per_text * hw) are cut into tiles of 80 of which the
+// last may be partly filled; every other check is fmc_xattn_block640_bf16's.
+extern "C" int fmc_xattn_block640_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_q_packed,
+                                               const void* kvfrag, const void* w_out_frag, const void* b_out, int n_images, int hw, int n_keys,
+                                               int images_per_text, float scale, void* stream) {
+    return xattn_block640_run(h, out, ln_gamma, ln_bpe, ln_eps, w_q_packed, kvfrag, w_out_frag, b_out, n_images, hw, n_keys, images_per_text, scale, stream, true);
 }
 
 // kv: bf16 [batch][S][1280] (k | v of the fused to_k / to_v projection, rows `ld_batch` elements apart per batch entry) -> out: bf16 [batch][8][12800]

@@ -1091,10 +1091,11 @@ TEMPORAL_FUSED_640 = os.environ.get("FMC_TEMPORAL_FUSED_640", "1") != "0"      #
 
 def temporal_block(h: torch.Tensor, ln_gamma: torch.Tensor, ln_bpe: torch.Tensor, ln_eps: float, w_qkv_packed: torch.Tensor,
                    w_out_tm: torch.Tensor, b_out: Optional[torch.Tensor], scale: float, w_merge_tm: Optional[torch.Tensor] = None,
-                   pose_term: Optional[torch.Tensor] = None, merge_scale: float = 1.0, stats_eps: Optional[float] = None):
+                   pose_term: Optional[torch.Tensor] = None, merge_scale: float = 1.0, stats_eps: Optional[float] = None, partial_tiles: bool = False):
     """One attention block of the temporal transformer in one launch (`fmc_temporal_block_bf16`): LayerNorm (+ pe) -> [Camera-Adapter merge] ->
     q | k | v -> attention over the frames -> out-projection + bias + h.  Returns `out` or `(out, ln_stats)` when `stats_eps` is given.
-    C = 320: `w_qkv_packed = pack_temporal_qkv(..)`, `w_out_tm` / `w_merge_tm` = `_w_tilemajor(..)`.  C = 640: `pack_temporal_qkv80`, `pack_w_frag80`, no statistics."""
+    C = 320: `w_qkv_packed = pack_temporal_qkv(..)`, `w_out_tm` / `w_merge_tm` = `_w_tilemajor(..)`.  C = 640: `pack_temporal_qkv80`, `pack_w_frag80`, no statistics.
+    `partial_tiles=True`: `fmc_temporal_block_partial_bf16` -- any hw >= 1, the last tile of a clip partly filled (`temporal_tile_count`)."""
     _dev(h, ln_gamma, ln_bpe, w_qkv_packed, w_out_tm, b_out, w_merge_tm, pose_term)
     B, F, hw, C = h.shape
     assert h.is_contiguous() and ln_gamma.dtype == torch.float32 and ln_bpe.dtype == torch.float32 and tuple(ln_bpe.shape) == (F, C) and ln_bpe.is_contiguous()
@@ -1102,12 +1103,13 @@ def temporal_block(h: torch.Tensor, ln_gamma: torch.Tensor, ln_bpe: torch.Tensor
     assert pose_term is None or (pose_term.shape == h.shape and pose_term.is_contiguous() and pose_term.dtype == h.dtype)
     out = torch.empty_like(h)
     stats = torch.empty(B * F * hw, 2, dtype=torch.float32, device=h.device) if stats_eps is not None else None
-    _log_call("fused_block", ("temporal", B * F * hw, C, w_merge_tm is not None),
+    _log_call("fused_block", ("temporal", B * F * hw, C, w_merge_tm is not None) + ((("partial", temporal_tile_count(B, hw, C)),) if partial_tiles else ()),
               2.0 * B * F * hw * C * C * (5 if w_merge_tm is not None else 4) + 4.0 * B * F * hw * F * C)
-    _lib.check(_lib.load().fmc_temporal_block_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_bpe.data_ptr(), float(ln_eps), _p(w_merge_tm),
-                                                   _p(pose_term), float(merge_scale), w_qkv_packed.data_ptr(), w_out_tm.data_ptr(), _p(b_out),
-                                                   _p(stats), float(stats_eps or 0.0), B, F, hw, C, 8, float(scale), _stream()),
-               "fmc_temporal_block_bf16")
+    fn = _lib.load().fmc_temporal_block_partial_bf16 if partial_tiles else _lib.load().fmc_temporal_block_bf16
+    _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_bpe.data_ptr(), float(ln_eps), _p(w_merge_tm),
+                  _p(pose_term), float(merge_scale), w_qkv_packed.data_ptr(), w_out_tm.data_ptr(), _p(b_out),
+                  _p(stats), float(stats_eps or 0.0), B, F, hw, C, 8, float(scale), _stream()),
+               "fmc_temporal_block_partial_bf16" if partial_tiles else "fmc_temporal_block_bf16")
     return out if stats is None else (out, stats)
 
 
@@ -1157,34 +1159,96 @@ def xattn_pack_kv(kv: torch.Tensor) -> torch.Tensor:
 
 def xattn_block(h: torch.Tensor, ln_gamma: torch.Tensor, ln_btab: torch.Tensor, ln_eps: float, w_q_packed: torch.Tensor, kv: torch.Tensor,
                 w_out_packed: torch.Tensor, b_out: Optional[torch.Tensor], scale: float, images_per_text: int, stats_eps: Optional[float] = None,
-                frag: Optional[torch.Tensor] = None):
+                frag: Optional[torch.Tensor] = None, partial_tiles: bool = False):
     """`to_out(softmax(to_q(LayerNorm(h)) k^T scale) v) + b + h` in one launch; `kv [B, S, 2 C]` = the text's fused k | v projection (packed into MFMA
     fragments by one tiny launch); `ln_btab [16, C]` fp32 rows = the LayerNorm beta.  C = 640: `fmc_xattn_block640_bf16`, weights `pack_w_frag80`;
-    C = 320: `fmc_xattn_block320_bf16`, `pack_xattn_q40` / `_w_tilemajor`, and `stats_eps` adds the (mean, rstd) of the output rows: `(out, stats)`."""
+    C = 320: `fmc_xattn_block320_bf16`, `pack_xattn_q40` / `_w_tilemajor`, and `stats_eps` adds the (mean, rstd) of the output rows: `(out, stats)`.
+    `partial_tiles=True`: the `_partial` entry points -- any hw >= 1, the last tile of a text's `images_per_text * hw` rows partly filled (`xattn_tile_count`)."""
     _dev(h, ln_gamma, ln_btab, w_q_packed, kv, w_out_packed, b_out)
     N, hw, C = h.shape
     B, S, C2 = kv.shape
     assert C in (320, 640) and C2 == 2 * C and kv.stride(2) == 1 and kv.stride(1) == C2 and N % images_per_text == 0 and N // images_per_text == B
     out = torch.empty_like(h)
     L = _lib.load()
-    _log_call("fused_block", ("xattn", N * hw, C, S), 2.0 * N * hw * C * C * 2 + 4.0 * N * hw * S * C)
+    _log_call("fused_block", ("xattn", N * hw, C, S) + ((("partial", xattn_tile_count(N, hw, images_per_text, C)),) if partial_tiles else ()),
+              2.0 * N * hw * C * C * 2 + 4.0 * N * hw * S * C)
     if frag is None:
         frag = xattn_pack_kv(kv)
     assert frag.numel() == B * 8 * (12800 if C == 640 else 7680) and frag.dtype == h.dtype
     if C == 640:
         assert stats_eps is None
-        _lib.check(L.fmc_xattn_block640_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
-                                             frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), N, hw, S, images_per_text, float(scale), _stream()),
-                   "fmc_xattn_block640_bf16")
+        fn = L.fmc_xattn_block640_partial_bf16 if partial_tiles else L.fmc_xattn_block640_bf16
+        _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
+                      frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), N, hw, S, images_per_text, float(scale), _stream()),
+                   "fmc_xattn_block640_partial_bf16" if partial_tiles else "fmc_xattn_block640_bf16")
         return out
     stats = torch.empty(N * hw, 2, dtype=torch.float32, device=h.device) if stats_eps is not None else None
-    _lib.check(L.fmc_xattn_block320_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
-                                         frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), _p(stats), float(stats_eps or 0.0), N, hw, S, images_per_text,
-                                         float(scale), _stream()), "fmc_xattn_block320_bf16")
+    fn = L.fmc_xattn_block320_partial_bf16 if partial_tiles else L.fmc_xattn_block320_bf16
+    _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
+                  frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), _p(stats), float(stats_eps or 0.0), N, hw, S, images_per_text,
+                  float(scale), _stream()), "fmc_xattn_block320_partial_bf16" if partial_tiles else "fmc_xattn_block320_bf16")
     return out if stats is None else (out, stats)
 
 
 xattn_block640 = xattn_block
+
+
+# ---- the fused attention blocks at any feature-map size: partly filled last tiles (csrc/temporal_block.hip: PARTIAL) -----------------------------------
+# One switch opts the models in (`TemporalTransformerBlock.forward`, `BasicTransformerBlock.forward`); read at call time.  Off by default: the whole-tile
+# predicates, wrappers and entry points behave as before, and ragged sizes keep the un-fused chain (profiles/partial_tiles.md has the numbers).
+PARTIAL_TILES = os.environ.get("FMC_PARTIAL_TILES", "0") not in ("", "0")
+
+
+def _tile_units(C: int, xattn: bool) -> int:
+    """What a tile of the fused blocks holds: pixels (x 16 frames) of the temporal form, rows of the text cross-attention form."""
+    assert C in (320, 640)
+    return (160 if C == 320 else 80) if xattn else (10 if C == 320 else 5)
+
+
+def temporal_tile_count(n_clips: int, hw: int, C: int) -> int:
+    """Tiles (= the grid before the persistent cap at C = 320) of `fmc_temporal_block_partial_bf16`: ceil(hw / 10 | 5) per clip."""
+    return n_clips * -(-hw // _tile_units(C, False))
+
+
+def temporal_tile(t: int, hw: int, C: int):
+    """Tile t of the temporal form -> (clip, first pixel, valid pixels): the kernel's `tile_row0` / `tile_valid`."""
+    px = _tile_units(C, False)
+    per_clip = -(-hw // px)
+    clip, p0 = t // per_clip, (t % per_clip) * px
+    return clip, p0, min(px, hw - p0)
+
+
+def xattn_tile_count(n_images: int, hw: int, images_per_text: int, C: int) -> int:
+    """Tiles of `fmc_xattn_block320 | 640_partial_bf16`: a segment = the `images_per_text * hw` rows of one text, ceil(rows / 160 | 80) tiles each."""
+    return (n_images // images_per_text) * -(-(images_per_text * hw) // _tile_units(C, True))
+
+
+def xattn_tile(t: int, seg_rows: int, C: int):
+    """Tile t of the text cross-attention form -> (segment = text, first global row, valid rows); a tile never holds rows of two texts."""
+    rows = _tile_units(C, True)
+    per_seg = -(-seg_rows // rows)
+    seg, r0 = t // per_seg, (t % per_seg) * rows
+    return seg, seg * seg_rows + r0, min(rows, seg_rows - r0)
+
+
+def _on_gpu(t: torch.Tensor) -> bool:
+    """(its own function so that the host tests can exercise every other condition of the two predicates below on CPU tensors)"""
+    return t.is_cuda
+
+
+def temporal_block_partial_supported(h: torch.Tensor, heads: int) -> bool:
+    """`temporal_block_supported` without the divisibility of hw: what `temporal_block(..., partial_tiles=True)` takes."""
+    return (_on_gpu(h) and h.dtype == torch.bfloat16 and h.ndim == 4 and h.is_contiguous() and h.shape[1] == 16 and heads == 8 and h.shape[2] >= 1
+            and (h.shape[3] == 320 or (h.shape[3] == 640 and TEMPORAL_FUSED_640))
+            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled())
+
+
+def xattn_block_partial_supported(h: torch.Tensor, kv_tokens: int, heads: int) -> bool:
+    """`xattn_block_supported` without the divisibility of hw: what `xattn_block(..., partial_tiles=True)` takes."""
+    if not (_on_gpu(h) and h.dtype == torch.bfloat16 and h.ndim == 3 and h.is_contiguous() and heads == 8 and 0 < kv_tokens <= 80 and h.shape[1] >= 1
+            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
+        return False
+    return (XATTN_FUSED_640 and h.shape[2] == 640) or (XATTN_FUSED_320 and h.shape[2] == 320)
 
 
 GEGLU_DIRECT_640 = os.environ.get("FMC_GEGLU_DIRECT_640", "1") != "0"      # A/B switch: LayerNorm + GEGLU projection of the 20x32 level with the A operand resident

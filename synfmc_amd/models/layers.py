@@ -916,8 +916,9 @@ class BasicTransformerBlock(nn.Module):
         self.attn2.text_kv(text, w_kv)
         return True
 
-    def _xattn_fused(self, hidden_states, encoder_hidden_states, kw):
-        """`attn2(norm2(h), text) + h` as one launch (the text's k | v projection and its fragment pack come from `Attention.text_kv`: once per clip)."""
+    def _xattn_fused(self, hidden_states, encoder_hidden_states, kw, partial=False):
+        """`attn2(norm2(h), text) + h` as one launch (the text's k | v projection and its fragment pack come from `Attention.text_kv`: once per clip).
+        `partial`: hw does not fill whole tiles -- the partial-tile entry points (`hip_ops.xattn_block(..., partial_tiles=True)`)."""
         attn = self.attn2
         w_q, w_kv, w_o = self._attn2_weights(kw)
         wq_p, wo_p = derived(attn, "_fused_xb", [w_q, w_o], lambda: (K.pack_w_frag80(w_q), K.pack_w_frag80(w_o)) if w_q.shape[0] == 640
@@ -928,12 +929,13 @@ class BasicTransformerBlock(nn.Module):
         kv, frag = attn.text_kv(encoder_hidden_states, w_kv)           # (once per clip, not per step)
         per_text = h.shape[0] // encoder_hidden_states.shape[0]
         if h.shape[2] == 640:
-            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag)
+            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
         # the 40x64 level: the feed-forward's norm3 is applied by its GEGLU projection from the row statistics this launch leaves
-        if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight):          # (the feed-forward normalises its input itself: no statistics to leave)
-            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag)
+        # (the feed-forward normalises its input itself: no statistics to leave; nor where a ragged row count keeps its GEMM from taking them, `hip_ops.lnc_ok`)
+        if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) or (partial and not K.lnc_ok(h, self.ff.net[0].proj.weight)):
+            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
         out, stats = K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps,
-                                   frag=frag)
+                                   frag=frag, partial_tiles=partial)
         K.ln_epilogue_calls["emitted"] += 1
         out._fmc_ln = (stats, self.norm3._ln_key(None, 1, 1), True)
         return out
@@ -955,8 +957,12 @@ class BasicTransformerBlock(nn.Module):
         # the text cross-attention block of the 40x64 / 20x32 levels as ONE launch (LayerNorm + to_q + attention over the text tokens + to_out + residual:
         # hip_ops.xattn_block): plain / frozen-LoRA processor, 8 heads, tokens [images, hw, 320 | 640] with hw % 160 | 80 == 0, no mask
         fuse2 = (d2 and not cfg_expand and encoder_hidden_states is not None and encoder_attention_mask is None and hidden_states.ndim == 3
-                 and encoder_hidden_states.ndim == 3 and hidden_states.shape[0] % encoder_hidden_states.shape[0] == 0
-                 and K.xattn_block_supported(hidden_states, encoder_hidden_states.shape[1], self.attn2.heads)
+                 and encoder_hidden_states.ndim == 3 and hidden_states.shape[0] % encoder_hidden_states.shape[0] == 0)
+        # (hw that does not fill whole tiles: the same launch with a partly filled last tile per text, behind `hip_ops.PARTIAL_TILES`, default off)
+        whole2 = fuse2 and K.xattn_block_supported(hidden_states, encoder_hidden_states.shape[1], self.attn2.heads)
+        partial2 = (fuse2 and not whole2 and K.PARTIAL_TILES
+                    and K.xattn_block_partial_supported(hidden_states, encoder_hidden_states.shape[1], self.attn2.heads))
+        fuse2 = ((whole2 or partial2)
                  and self.attn2.inner_dim == hidden_states.shape[2] and not self.attn2.residual_connection and self.attn2.rescale_output_factor == 1.0
                  and self.attn2.to_q.weight.dtype == torch.bfloat16 and encoder_hidden_states.dtype == torch.bfloat16)
         # (`_lazy_res`: the output projection's `+ residual` may be left to the next norm's pass when the projection runs on the vendor arm;
@@ -984,7 +990,7 @@ class BasicTransformerBlock(nn.Module):
         if cfg_expand:          # shared classifier-free-guidance prefix ends here: the text cross-attention is the first op that tells the halves apart
             hidden_states = torch.cat([hidden_states, hidden_states], dim=0)
         if fuse2:
-            hidden_states = self._xattn_fused(hidden_states, encoder_hidden_states, kw)
+            hidden_states = self._xattn_fused(hidden_states, encoder_hidden_states, kw, partial=partial2)
         elif self.attn2 is not None:
             hidden_states, n = self.norm2.skip(hidden_states, defer=d2)
             hidden_states = self.attn2(n, encoder_hidden_states=encoder_hidden_states, attention_mask=encoder_attention_mask,
