@@ -115,7 +115,7 @@ __device__ __forceinline__ void zero8(float (&v)[8]) {
 // below is compile-time false and Fr is the compile-time tile height: the whole-tile instantiations compile to the instruction streams they had.
 // fp32 storage: the PART forward kernels compute Q K^T and P V as four split products (lo * lo included), not three.  The x3 form's rel-inf error
 // against the fp32 oracle is 0.9 - 1.6e-5 on most inputs but reached 2.07e-5 on one (F = 25, d = 8), beyond the 2e-5 the parity mode is held to;
-// with lo * lo the worst of 110 draws over all lengths at that shape is 1.3e-5.  The whole-tile kernels keep x3: their results must not move.
+// with lo * lo the worst of 110 draws over all lengths at that shape is 1.3e-5.  The whole-tile kernels keep x3.
 // FT = ceil(F/16) frame tiles; NK32 = ceil(D/32) k-steps of the QK^T reduction
 template <typename T, int FT, int NK32, int NWV, bool PART>     // NWV waves per unit (they split its heads)
 __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams P) {
@@ -247,11 +247,14 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
                 for (int r = 0; r < 4; ++r) { s[kt][r] = TA_EXP2(s[kt][r] - mx); sum += s[kt][r]; }
             sum += __shfl_xor(sum, 16, 64);
             sum += __shfl_xor(sum, 32, 64);
+            // p goes into the PV product as it leaves the exp (p <= 1, the row maximum's p exactly 1) and 1 / l is applied to the fp32 accumulator:
+            // rounding p * (1 / l) instead put a bf16 rounding on every key's weight, the dominant one included, which the 1 .. 32 keys of a
+            // clip do not average out (profiles/attn_forward_bounds.md)
             const float inv = 1.f / sum;
             F4<T> pf[FT];
 #pragma unroll
             for (int kt = 0; kt < FT; ++kt) {
-                float p4[4] = {s[kt][0] * inv, s[kt][1] * inv, s[kt][2] * inv, s[kt][3] * inv};
+                float p4[4] = {s[kt][0], s[kt][1], s[kt][2], s[kt][3]};
                 make_f4(p4, pf[kt]);
             }
             // ---- O^T = V^T P^T, 16 output channels at a time; result replaces Q(qt, head) in LDS ---------
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(64 * NWV) void temporal_attn_kernel(const TAParams 
                 }
                 const int dO = dt * 16 + lg * 4;    // 4 consecutive output channels of query l15
                 if (dO < D) {
-                    float o4[4] = {o[0], o[1], o[2], o[3]};
+                    float o4[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};      // (inv is per query l15: the same in all four lane groups)
                     st4<T>(Qs + (qt * 16 + l15) * PITCH + hc + dO, o4);
                 }
             }
@@ -425,11 +428,11 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
                 for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(s[kt][r] - mx); sum += s[kt][r]; }
             sum += __shfl_xor(sum, 16, 64);
             sum += __shfl_xor(sum, 32, 64);
-            const float inv = 1.f / sum;
+            const float inv = sv / sum;             // un-normalised p into the PV product, 1 / l and V's scale onto the accumulator (see temporal_attn_kernel)
             F4<bf16_t> pf[FT];
 #pragma unroll
             for (int kt = 0; kt < FT; ++kt) {
-                float p4[4] = {s[kt][0] * inv, s[kt][1] * inv, s[kt][2] * inv, s[kt][3] * inv};
+                float p4[4] = {s[kt][0], s[kt][1], s[kt][2], s[kt][3]};
                 make_f4(p4, pf[kt]);
             }
             const int ndt = (D + 15) / 16;
@@ -448,7 +451,7 @@ __global__ __launch_bounds__(256) void temporal_attn_fp8_kernel(const TA8Params 
                 }
                 const int dO = dt * 16 + lg * 4;
                 if (dO < D) {
-                    float o4[4] = {o[0] * sv, o[1] * sv, o[2] * sv, o[3] * sv};
+                    float o4[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
                     st4<bf16_t>(Os + (qt * 16 + l15) * OPITCH + hc + dO, o4);
                 }
             }

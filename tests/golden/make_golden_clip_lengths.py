@@ -3,7 +3,8 @@
 fmc_temporal_attn_fp8_fwd / _bwd) at F = 16 and F = 32 on the fixed inputs of `tests/clip_lengths_common.py`, as raw bits.  Recorded on an
 MI355X with the library built from the commit BEFORE the kernels learnt partial frame tiles (`FMC_HIP_LIB` selects the build; the Python
 layer of the entry points did not change), so that tests/test_gpu_clip_lengths.py::test_full_tiles_bit_identical can assert that the
-16- and 32-frame paths did not move by one bit.  Needs the GPU; writes data only:
+16- and 32-frame paths did not move by one bit.  (The forward arrays of the committed files are from the library that
+normalises on the PV accumulator, profiles/attn_forward_bounds.md; the backward arrays from the earlier one.)  Needs the GPU; writes data only:
 
     FMC_HIP_LIB=/path/to/the/earlier/libfmc_hip.so python tests/golden/make_golden_clip_lengths.py [output directory]
 """

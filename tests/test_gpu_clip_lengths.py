@@ -240,8 +240,10 @@ def test_pad_rows_are_never_touched_fp8(K, Fr):
 # ---- 5. whole tiles did not move -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("Fr", [16, 32])
 def test_full_tiles_bit_identical(K, golden_dir, Fr):
-    """F = 16 and F = 32 on fixed inputs equal, bit for bit, what the library of the commit before the partial-tile work gave
-    (tests/golden/make_golden_clip_lengths.py, same machine type): the existing paths did not move."""
+    """F = 16 and F = 32 on fixed inputs equal the recorded bits (tests/golden/make_golden_clip_lengths.py, same machine type).  The three backward
+    arrays are those of the library before the partial-tile work: those paths did not move.  The three forward arrays were recorded again when the
+    forward kernels moved the normalisation from the rounded p onto the PV accumulator (profiles/attn_forward_bounds.md); the backward arrays were
+    bit-identical in that run."""
     gold = np.load(os.path.join(golden_dir, f"g8_temporal_attn_full_tiles_f{Fr}.npz"))
     got = CL.full_tile_outputs(K, Fr)
     for name in ("fwd_bf16", "fwd_f32", "bwd_bf16", "bwd_f32", "fp8_fwd", "fp8_bwd"):
