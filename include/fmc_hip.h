@@ -357,6 +357,15 @@ int fmc_linear_bf16_imgw(const void* x, const void* w_img, const float* bias_img
  * k_split % 64 == 0. */
 int fmc_linear_bf16_fftail(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M,
                            int N, int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor, void* stream);
+/* The two consumers of the tile-major intermediate at any row count (gemm160p_kernel<..., PARTIAL>): x_blocked = ceil(M / 160) WHOLE tiles
+ * [K' / 32][160][32] as fmc_geglu_pipe_ln_partial_bf16 leaves them (pad rows of the last tile: anything, NaN included -- they reach no valid row);
+ * out / residual / x2 are row-major with M rows.  fmc_linear_bf16_ffblk_partial: out = alpha (x W^T + bias) + residual (the x_blocked form of
+ * fmc_linear_bf16_ffblk, plain epilogue); fmc_linear_bf16_fftail_partial: fmc_linear_bf16_fftail, gn_partials must be NULL and gn_hw 0.  N % 320 == 0,
+ * ceil(M / 160) * (N / 320) >= CUs, K (and k_split) % 64 == 0.  Valid rows are bit-identical to the whole-tile entry points on padded tokens. */
+int fmc_linear_bf16_ffblk_partial(const void* x_blocked, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
+                                  int64_t ldres, float alpha, int w_tilemajor, void* stream);
+int fmc_linear_bf16_fftail_partial(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M,
+                                   int N, int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor, void* stream);
 int fmc_conv3x3_bf16_gn(const void* x, const void* w, const void* bias, const void* temb, const void* residual, void* out, int n_img,
                         int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x,
                         float* gn_partials, int w_tilemajor, void* stream);
@@ -432,6 +441,12 @@ int fmc_attention_fwd(const void* q, const void* k, const void* v, void* o, cons
 int fmc_geglu_pipe_supported(int64_t M, int cff, int C, int variant);
 int fmc_geglu_pipe_ln_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed, const void* bias,
                            int64_t M, int cff, int C, int out_blocked, int variant, void* stream);
+/* The same with a partly filled last tile: any M >= 1, ceil(M / 80 | 160) workgroups.  Pad rows read the tile's last valid row again and are not stored.
+ * out_blocked: out is ceil(M / 160) WHOLE tiles [cff / 32][160][32] -- the caller allocates the padded size, the pad rows of the last tile are left as they
+ * were.  Valid rows are bit-identical to fmc_geglu_pipe_ln_bf16 on the same tokens padded to whole tiles. */
+int fmc_geglu_pipe_partial_supported(int64_t M, int cff, int C, int variant);
+int fmc_geglu_pipe_ln_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed, const void* bias,
+                                   int64_t M, int cff, int C, int out_blocked, int variant, void* stream);
 
 /* The statistics pass of fmc_groupnorm_silu_fwd alone (x read once, nothing written but the sums): partials [N][splits][G][2] fp32 with
  * splits = fmc_groupnorm_partial_splits(HW, C); x2 / C1: two-source channel concat as for fmc_groupnorm_silu_fwd. */

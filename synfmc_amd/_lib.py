@@ -113,6 +113,12 @@ SIGNATURES = {
                                        c_int64, c_void_p]),
     "fmc_geglu_pipe_supported": (c_int, [c_int64, c_int, c_int, c_int]),
     "fmc_geglu_pipe_ln_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "fmc_geglu_pipe_partial_supported": (c_int, [c_int64, c_int, c_int, c_int]),
+    "fmc_geglu_pipe_ln_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                               c_void_p]),
+    "fmc_linear_bf16_ffblk_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_float, c_int, c_void_p]),
+    "fmc_linear_bf16_fftail_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int64,
+                                               c_void_p, c_int, c_int, c_void_p]),
     "fmc_attention_supported": (c_int, [c_int]),
     "fmc_attention_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,
                                   c_int64, c_int64, c_float, c_int, c_int, c_void_p]),

@@ -18,6 +18,10 @@
 // g 0-15 | g 16-31], `hip_ops.pack_geglu_frag64`) per chunk of 128: both accumulator sets (2 x 80) stay in architectural VGPRs next to the gate's temporaries,
 // the weight ring lives in AGPRs.  (The first build kept geglu_direct_kernel's 80-weight-row waves: 2 x 100 accumulators went to AGPRs and every chunk paid
 // 300 v_accvgpr_read / _write to hand them to the VALU.)
+// Any row count (PARTIAL_ = true, fmc_geglu_pipe_ln_partial_bf16): ceil(M / ROWS) workgroups, the last tile partly filled.  The source row of the `h` DMA
+// is CLAMPED to the tile's last valid row (as the fused attention blocks do) instead of relying on the buffer range: every read lies inside `h`, and a pad
+// row is a finite copy of a valid one.  Pad rows are computed and NOT stored: their store offset -- all of it in the per-lane operand, scalar offset 0 -- is
+// selected out of the buffer range, which for a tile-major `out` is built from the padded size.  The note above the entry point has the details.
 #include <type_traits>
 
 #include "common.h"
@@ -25,7 +29,7 @@
 namespace {
 
 struct GPParams {
-    const bf16_t* h; bf16_t* out;                          // h [M][C]; out [M][Cff] row-major or tile-major [M / 160][Cff / 32][160][32]
+    const bf16_t* h; bf16_t* out;                          // h [M][C]; out [M][Cff] row-major or tile-major [ceil(M / 160)][Cff / 32][160][32]
     const float* ln_gamma; const float* ln_beta; float ln_eps;
     const bf16_t* w;                                       // [Cff / G column groups][C / 32 k-steps][G / 8 blocks][lane][8], G = 32 | 16 gated columns per wave (hip_ops.pack_geglu_frag)
     const bf16_t* bias;                                    // [2 Cff] (value | gate) or NULL
@@ -78,7 +82,8 @@ __device__ __forceinline__ f32x2_t gp_gate2(f32x2_t v, f32x2_t g) {
 // values, half gates): <C, 4, 5, 4> = 80 rows, one wave per SIMD, 32 gated columns per wave; <320, 8, 10, 2> = 160 rows, two waves per SIMD, 16 gated columns
 // per wave -- every weight fragment a wave loads then serves 160 rows: the fragment stream is 25 B / clk / CU against the 64 B / clk of the CU's vector-memory
 // path (the 80-row forms of this and of geglu_direct_kernel need 50: what throttles their MFMA stream to half rate even with no gate at all).
-template <int GC_, int NW_, int MB_, int NBK_>
+// PARTIAL_: the grid is ceil(M / ROWS) tiles and the last one may hold fewer than ROWS rows (see the note above fmc_geglu_pipe_ln_partial_bf16).
+template <int GC_, int NW_, int MB_, int NBK_, bool PARTIAL_ = false>
 __global__ __launch_bounds__(64 * NW_, NW_ / 4)
 void geglu_pipe_kernel(const GPParams P) {
     constexpr int C = GC_, NW = NW_, MB = MB_, NBK = NBK_, NT = 64 * NW, ROWS = 16 * MB, CPR = C / 8, KS = C / 32, GW = 8 * NBK, GCOLS = GW * NW, LPR = CPR / 10,
@@ -95,6 +100,7 @@ void geglu_pipe_kernel(const GPParams P) {
     const int l15 = lane & 15, kq = lane >> 4;
     const int xsw = (l15 >> 1) & 7;
     const int64_t m0 = (int64_t)blockIdx.x * ROWS;
+    const int rlast = PARTIAL_ ? (int)(P.M - 1 - m0 < ROWS - 1 ? P.M - 1 - m0 : ROWS - 1) : ROWS - 1;   // last valid row of my tile (uniform)
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc((void*)P.h, 0, (int)(P.M * C * 2), 0x00020000);
     // ---- phase A: rows -> X, LayerNorm in place (geglu_direct_kernel's) ----
 #pragma unroll
@@ -102,7 +108,8 @@ void geglu_pipe_kernel(const GPParams P) {
         const int q = wave + NW * j;
         if (q < ROWS * CPR / 64) {
             const int idx = 64 * q + lane, r = idx / CPR, pc = idx - r * CPR, c = pc ^ ((r >> 1) & 7);
-            gp_dma(rsH, (unsigned)(((m0 + r) * C + c * 8) * 2), X + 64 * q * 8);
+            if constexpr (PARTIAL_) gp_dma(rsH, (unsigned)(((m0 + (r < rlast ? r : rlast)) * C + c * 8) * 2), X + 64 * q * 8);   // pad rows: the last valid row again
+            else gp_dma(rsH, (unsigned)(((m0 + r) * C + c * 8) * 2), X + 64 * q * 8);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -158,7 +165,9 @@ void geglu_pipe_kernel(const GPParams P) {
     // ---- the pipelined chunk loop ----
     const int nchunks = P.cff / GCOLS;
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)P.w, 0, (int)((int64_t)2 * P.cff * C * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc((void*)P.out, 0, (int)(P.M * P.cff * 2), 0x00020000);
+    // (PARTIAL_, tile-major: the range covers the whole last 160-row tile -- valid rows of it lie behind pad rows of earlier column blocks)
+    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)P.out, 0, (int)((PARTIAL_ && P.out_blocked ? (P.M + 159) / 160 * 160 : P.M) * P.cff * 2), 0x00020000);
     // (no bias: an empty range -- every load returns zero; chunks past the end read zeros the same way: the steady-state steps carry no branch, so that
     //  the whole k-step stays ONE scheduling region for the MFMA / gate interleave)
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(P.bias ? P.bias : P.w), 0, P.bias ? 2 * P.cff * 2 : 0, 0x00020000);
@@ -219,6 +228,12 @@ void geglu_pipe_kernel(const GPParams P) {
         const f32x2_t o23 = gp_gate2(v23, g23);
 #endif
         const u32x2 o = u32x2{pack_bf2(o01[0], o01[1]), pack_bf2(o23[0], o23[1])};
+        if constexpr (PARTIAL_) {
+            // a pad row's store is dropped by the range check: its WHOLE offset sits in the per-lane operand (the scalar offset stays 0), selected out of
+            // range -- two VALU instructions per unit in the MFMAs' shadow, no branch
+            const int vo = 16 * mb + l15 <= rlast ? ooff[p] + mb * rstep : (int)0x80000000u;
+            __builtin_amdgcn_raw_buffer_store_b64(o, rsO, vo, 0, 0);
+        } else
         __builtin_amdgcn_raw_buffer_store_b64(o, rsO, ooff[p], mb * rstep, 0);
     };
     // step S of a two-chunk round (chunks c0 = even, c0 + 1): MFMAs of (chunk c0 + S / KS, k-step S % KS) into accumulator set S / KS, the weight request of
@@ -368,5 +383,40 @@ extern "C" int fmc_geglu_pipe_ln_bf16(const void* h, void* out, const float* ln_
     else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4>>(dim3((unsigned)(M / 80)), dim3(256), lds640, st, P);
     else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2>>(dim3((unsigned)(M / 160)), dim3(512), lds320w, st, P);
     FMC_CHECK_LAUNCH("fmc_geglu_pipe_ln_bf16");
+    return 0;
+}
+
+// Partly filled last tile (geglu_pipe_kernel<..., PARTIAL_ = true>): any M >= 1, ceil(M / ROWS) workgroups.  Decision on the two ends of the tile:
+//   * reads: the source row of the `h` DMA is CLAMPED to the tile's last valid row, as the fused attention blocks do -- every address lies inside the
+//     tensor and nothing rests on what an out-of-range LDS-DMA leaves in LDS.  A pad row is the last valid row again: finite wherever that row is;
+//   * stores: a pad row's store carries its whole byte offset in the per-lane operand and that operand is selected out of range (0x80000000), so the
+//     descriptor's range check drops it whichever way the hardware treats the scalar offset; the scalar offset is 0.  Row-major the range ends at row
+//     M; tile-major it is built from the padded size ceil(M / 160) * 160 rows, `out` must own that much, and its pad rows are never written.
+// Valid rows go through the same instructions in the same order as in the whole-tile form: their bits are the same.
+extern "C" int fmc_geglu_pipe_partial_supported(int64_t M, int cff, int C, int variant) {
+    const int64_t Mp = (M + 159) / 160 * 160;
+    const bool common = M > 0 && cff > 0 && cff % 128 == 0 && Mp * (int64_t)cff * 2 < ((int64_t)1 << 31) && (int64_t)2 * cff * C * 2 < ((int64_t)1 << 31) &&
+                        Mp * (int64_t)C * 2 < ((int64_t)1 << 31);
+    if (variant == 1) return common && C == 320;
+    return variant == 0 && common && (C == 320 || C == 640);
+}
+
+extern "C" int fmc_geglu_pipe_ln_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed,
+                                              const void* bias, int64_t M, int cff, int C, int out_blocked, int variant, void* stream) {
+    if (!h || !out || !ln_gamma || !ln_beta || !w_packed) FMC_FAIL(FMC_E_NULL, "geglu_pipe_ln_partial_bf16: NULL tensor");
+    if (!fmc_geglu_pipe_partial_supported(M, cff, C, variant))
+        FMC_FAIL(FMC_E_SHAPE, "geglu_pipe_ln_partial_bf16: C in {320, 640} (variant 1: 320), M >= 1, cff %% 128 == 0, padded tensors below 2 GiB (got M=%lld "
+                              "cff=%d C=%d variant=%d)", (long long)M, cff, C, variant);
+    if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_packed) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_beta) || (bias && ((uintptr_t)bias & 7)))
+        FMC_FAIL(FMC_E_ALIGN, "geglu_pipe_ln_partial_bf16: tensors must be 16-byte aligned");
+    GPParams P;
+    P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
+    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
+    constexpr int lds320 = 80 * 320 * 2 + 640, lds640 = 80 * 640 * 2 + 640, lds320w = 160 * 320 * 2 + 1280;
+    hipStream_t st = (hipStream_t)stream;
+    if (variant == 0 && C == 320) fmc_launch<geglu_pipe_kernel<320, 4, 5, 4, true>>(dim3((unsigned)((M + 79) / 80)), dim3(256), lds320, st, P);
+    else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4, true>>(dim3((unsigned)((M + 79) / 80)), dim3(256), lds640, st, P);
+    else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2, true>>(dim3((unsigned)((M + 159) / 160)), dim3(512), lds320w, st, P);
+    FMC_CHECK_LAUNCH("fmc_geglu_pipe_ln_partial_bf16");
     return 0;
 }

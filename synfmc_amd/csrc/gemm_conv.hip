@@ -1863,7 +1863,21 @@ void gemm160_kernel(const GemmParams P) {
 // stream's A requests of a sub-tile past ksplit / 32 go to a2 with ONE per-lane offset (row in piece, 16-byte chunk) and the piece / k position in the
 // scalar offset, so the variant costs one register over the plain one.
 // IMG = 1 (plain epilogue): per-image weights and fp32 bias rows, see GemmParams::bias_img.
-template <int EPI, int MB, int LN = 0, int LNC = 0, int A2 = 0, int IMG = 0>
+// PARTIAL = 1 (plain epilogue, tile-major A, with or without A2; fmc_linear_bf16_ffblk_partial / _fftail_partial): tiles_m = ceil(M / 160) and the last
+// row tile holds M - 160 (tiles_m - 1) rows.  What that tile does differently, and why the vmcnt bookkeeping above still holds:
+//   * operands: the tile-major A blocks are whole (the allocation is padded to tiles_m * 160 rows, a_bytes says so); what the producer left in the pad
+//     rows, NaN included, reaches the pad rows' accumulators only (a row of the product depends on its own A row).  The a2 requests clamp their row --
+//     the scalar piece base AND the lane's row in the piece -- to M - 1, so every address lies inside a2 whatever the range check makes of the scalar
+//     offset; a pad row reads the last valid row again.  Requests per wave and sub-tile: NE, as before;
+//   * residual loads: row clamped to M - 1.  They are loads whose values are consumed before the stores, so they never stand between the stores and
+//     the next request;
+//   * stores: a chunk whose row lies past M is redirected exactly as a thread without a last chunk already is -- staging row AND destination row clamped
+//     to the tile's last valid row, the same bytes to the same address a second time.  A pass whose 80 rows are ALL past M (the last tile holds <= 80
+//     rows; only pass 1 can be such) skips its residual staging and does not overwrite the staging tile, which therefore still holds pass 0's rounded
+//     rows: its seven stores per thread repeat pass 0's last valid row from there.  So every thread still issues EXACTLY S_EPI = 14 stores per tile, in
+//     the same places of the instruction stream, and `vmcnt(S_EPI + NE)` in the first phase after the epilogue counts what it counted.  The skipped
+//     branches are workgroup-uniform (they depend on m0 and M only): every barrier is met by all threads.
+template <int EPI, int MB, int LN = 0, int LNC = 0, int A2 = 0, int IMG = 0, int PARTIAL = 0>
 __global__ __launch_bounds__(512, 2)
 void gemm160p_kernel(const GemmParams P) {
     constexpr int BM = 32 * MB, BN = 320, BK = 32, NT = 512, NBUF = 3;
@@ -1873,6 +1887,7 @@ void gemm160p_kernel(const GemmParams P) {
     constexpr int S_EPI = MB == 5 ? (EPI == 1 ? 7 : (LN == 1 ? 28 : (LN == 2 ? 16 : 14))) : 10;   // global stores per thread and tile (see the header)
     static_assert(!LN || (EPI == 0 && MB == 5), "LayerNorm rides in the plain epilogue of the 160-row tile");
     static_assert(MB == 5 || (MB == 8 && EPI == 1), "the 256-row tile has the GEGLU epilogue only");
+    static_assert(!PARTIAL || (EPI == 0 && MB == 5 && !LN && !LNC && !IMG), "partly filled last tile: plain epilogue of the 160-row tile, forms 0 and 6 only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16_t* smem = reinterpret_cast<bf16_t*>(smem_raw);
     auto lds0 = (__attribute__((address_space(3))) unsigned char*)smem_raw;
@@ -1943,8 +1958,16 @@ void gemm160p_kernel(const GemmParams P) {
                 const int i = NE * wave + e;
                 const bool real = s_m0 >= 0 && i < 20 + BM / 16;
                 const int dst = e_lds[e] == NBUF * SUB_ELEMS ? NBUF * SUB_ELEMS : it_buf * SUB_ELEMS + e_lds[e];
+                if constexpr (PARTIAL) {              // piece base and lane row clamped to row M - 1 (see the header)
+                    const int mlast = (int)P.M - 1;
+                    const int base = real ? min(s_m0 + 16 * (i - 20), mlast) : 0;
+                    const int so2 = real ? (int)(((int64_t)base * P.lda2 + (it_s - nksA) * BK) * 2) : 0;
+                    const unsigned vo2 = (unsigned)((min(prow, mlast - base) * P.lda2 + psrc * 8) * 2);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA2, (__attribute__((address_space(3))) void*)(lds0 + 2 * dst), 16, real ? (int)vo2 : (int)OOB, so2, 0, 0);
+                } else {
                 const int so2 = real ? (int)((((int64_t)s_m0 + 16 * (i - 20)) * P.lda2 + (it_s - nksA) * BK) * 2) : 0;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA2, (__attribute__((address_space(3))) void*)(lds0 + 2 * dst), 16, real ? (int)lane_a2 : (int)OOB, so2, 0, 0);
+                }
             }
         } else {
 #pragma unroll
@@ -2178,10 +2201,12 @@ void gemm160p_kernel(const GemmParams P) {
             float gs = 0.f, gss = 0.f;
 #pragma unroll 1
             for (int pass = 0; pass < 2; ++pass) {                       // rows [80 pass, 80 pass + 80): wave row `pass`
+                const int rl = PARTIAL ? (int)(P.M - 1 - m0 < BM - 1 ? P.M - 1 - m0 : BM - 1) : BM - 1;   // last valid row of the tile
+                const bool dead = PARTIAL && rl < pass * 80;             // (uniform) no row of this pass exists: see the header
 #pragma unroll 1
                 for (int rz = 0; rz < 2; ++rz) {
                     const bf16_t* rp = rz == 0 ? P.res : P.res2;
-                    if (rp == nullptr) continue;                       // (uniform)
+                    if (rp == nullptr || dead) continue;               // (uniform)
                     {   // the 80 residual rows in ONE burst of 7 loads per thread (80 x 40 chunks = 6.25 per thread: the 7th repeats the 6th): rolled, the loop
                         // was load -> s_waitcnt vmcnt(0) -> ds_write per iteration, seven dependent HBM round trips per wave row and residual
                         constexpr int RB = LN == 1 ? 2 : 7;              // (the LayerNorm-writing variant has 2 free registers: 7 in flight spilled 18, 4 spilled 5)
@@ -2193,6 +2218,8 @@ void gemm160p_kernel(const GemmParams P) {
                                 int c = tid + min(h * RB + it, 6) * NT;
                                 if (c >= 80 * CPR) c -= NT;
                                 const int r = c / CPR, ch = c - r * CPR;
+                                if constexpr (PARTIAL) rv[it] = *reinterpret_cast<const u32x4*>(rp + (m0 + min(pass * 80 + r, rl)) * P.ldres + n0 + ch * 8);
+                                else
                                 rv[it] = *reinterpret_cast<const u32x4*>(rp + (m0 + pass * 80 + r) * P.ldres + n0 + ch * 8);
                             }
 #pragma unroll
@@ -2217,7 +2244,7 @@ void gemm160p_kernel(const GemmParams P) {
                     }
                     __syncthreads();
                 }
-                if (wr == pass) {
+                if (wr == pass && !dead) {
 #pragma unroll
                     for (int mb = 0; mb < 5; ++mb)
 #pragma unroll
@@ -2232,6 +2259,10 @@ void gemm160p_kernel(const GemmParams P) {
                     int c = tid + it * NT;
                     if (c >= 80 * CPR) c -= NT;
                     const int r = c / CPR, ch = c - r * CPR;
+                    if constexpr (PARTIAL) {
+                        const int rt = min(pass * 80 + r, rl), rs = rt - (dead ? 0 : pass * 80);      // destination row in the tile, staging row
+                        *reinterpret_cast<u32x4*>(P.out + (m0 + rt) * P.ldo + n0 + ch * 8) = *reinterpret_cast<const u32x4*>(Os + rs * OP + ch * 8);
+                    } else
                     *reinterpret_cast<u32x4*>(P.out + (m0 + pass * 80 + r) * P.ldo + n0 + ch * 8) = *reinterpret_cast<const u32x4*>(Os + r * OP + ch * 8);
                 }
                 if (LN) {
@@ -3237,4 +3268,55 @@ extern "C" int fmc_linear_fp8_qkv(const void* x, const void* w, void* out_fp8, i
     launch_gemm8<0, 2, 4>(P, (hipStream_t)stream);
     FMC_CHECK_LAUNCH("fmc_linear_fp8_qkv");
     return 0;
+}
+
+// ---- the feed-forward's second GEMM at any row count: gemm160p_kernel<..., PARTIAL = 1> (see its header) ----------------------------------------------
+// x_blocked: ceil(M / 160) WHOLE tiles [K' / 32][160][32] (K' = K, or k_split with x2); the pad rows of the last tile may hold anything.  Everything else as
+// the whole-tile forms: N % 320 == 0, at least as many tiles as CUs, plain epilogue, bf16.
+static int ff_partial_impl(const char* who, const void* xb, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N,
+                           int K, int k_split, int64_t ldx2, int64_t ldres, float alpha, int w_tilemajor, void* stream) {
+    if (!xb || !w || !out) FMC_FAIL(FMC_E_NULL, "%s: NULL tensor", who);
+    const int cus = fmc_cu_count() & ~7;
+    const int64_t tiles_m = (M + 159) / 160, Mp = tiles_m * 160;
+    const int ka = x2 ? k_split : K;                          // columns of the tile-major segment
+    if (M <= 0 || N <= 0 || K <= 0 || N % 320 || K % BK_MAX || cus < 8 || tiles_m * (N / 320) < cus || g160_persist() == 0 || (residual && ldres % 8) ||
+        (x2 && (k_split <= 0 || k_split >= K || k_split % BK_MAX || ldx2 % 8 || ldx2 < K - k_split || ((M - 1) * ldx2 + (K - k_split)) * 2 >= ((int64_t)1 << 31))) ||
+        Mp * (int64_t)ka * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31))
+        FMC_FAIL(FMC_E_SHAPE, "%s: need N %% 320 == 0, K %% 64 == 0, ceil(M / 160) * (N / 320) >= CUs, operands below 2 GiB (M=%lld N=%d K=%d k_split=%d)", who,
+                 (long long)M, N, K, k_split);
+    if (!fmc_aligned16(xb) || !fmc_aligned16(w) || !fmc_aligned16(out) || (x2 && !fmc_aligned16(x2)) || (residual && !fmc_aligned16(residual)) ||
+        (bias && !fmc_aligned16(bias)))
+        FMC_FAIL(FMC_E_ALIGN, "%s: tensors must be 16-byte aligned", who);
+    GemmParams P{};
+    P.a = (const bf16_t*)xb; P.w = (const bf16_t*)w; P.bias = (const bf16_t*)bias; P.res = (const bf16_t*)residual; P.out = (bf16_t*)out;
+    P.M = M; P.N = N; P.K = K; P.lda = ka; P.ldres = ldres; P.ldo = N; P.hw = 1; P.alpha = alpha; P.temb_div = 1;
+    P.ln_pe_inner = 1; P.ln_pe_frames = 1;
+    P.a2 = (const bf16_t*)x2; P.lda2 = ldx2; P.ksplit = x2 ? k_split : 0;
+    P.a_blocked = 1; P.w_blocked = w_tilemajor != 0;
+    P.a_bytes = Mp * (int64_t)ka * 2;                         // the padded allocation: the last tile's blocks are read whole
+    if (int rc = set_split_k(P, 1, nullptr, 0, true, who)) return rc;
+    P.tiles_m = (int)tiles_m;
+    P.tiles_n = N / 320;
+    P.tap_outer = 0;
+    P.group_m = xcd_group_m(P, true, 32.0, 320, 160);
+    constexpr size_t ldsp = (size_t)3 * (160 + 320) * 32 * sizeof(bf16_t) + 1024 + (size_t)80 * 328 * 2 + 5120;     // launch_gemm160's, plain epilogue
+    const dim3 grid((unsigned)cus), block(512);
+    hipStream_t st = (hipStream_t)stream;
+    if (x2) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1, 0, 1>>(grid, block, ldsp, st, P);
+    else fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 0, 1>>(grid, block, ldsp, st, P);
+    FMC_CHECK_LAUNCH(who);
+    return 0;
+}
+
+extern "C" int fmc_linear_bf16_ffblk_partial(const void* x_blocked, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
+                                             int64_t ldres, float alpha, int w_tilemajor, void* stream) {
+    return ff_partial_impl("linear_bf16_ffblk_partial", x_blocked, nullptr, w, bias, residual, out, M, N, K, 0, 0, ldres, alpha, w_tilemajor, stream);
+}
+
+extern "C" int fmc_linear_bf16_fftail_partial(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M,
+                                              int N, int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor,
+                                              void* stream) {
+    if (!x2) FMC_FAIL(FMC_E_NULL, "linear_bf16_fftail_partial: NULL x2 (use fmc_linear_bf16_ffblk_partial)");
+    if (gn_partials || gn_hw) FMC_FAIL(FMC_E_SHAPE, "linear_bf16_fftail_partial: no GroupNorm partials with a partly filled last tile");
+    return ff_partial_impl("linear_bf16_fftail_partial", x_blocked, x2, w, bias, residual, out, M, N, K, k_split, ldx2, ldres, 1.f, w_tilemajor, stream);
 }

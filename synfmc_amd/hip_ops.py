@@ -1305,17 +1305,95 @@ def geglu_ln_pipe_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
 
 
 def geglu_ln_pipe(h: torch.Tensor, ln_gamma: torch.Tensor, ln_beta: torch.Tensor, ln_eps: float, w_packed: torch.Tensor, bias: Optional[torch.Tensor],
-                  cff: int, blocked: bool = False, variant: int = 0) -> torch.Tensor:
+                  cff: int, blocked: bool = False, variant: int = 0, partial_tiles: bool = False) -> torch.Tensor:
     """`GEGLU(LayerNorm(h))` on `fmc_geglu_pipe_ln_bf16` (the gate of chunk c - 1 in the shadow of chunk c's MFMAs): `[..., C] -> [..., cff]`, `w_packed` =
-    `pack_geglu_frag(weight, 32 if variant == 0 else 16)`.  `blocked`: tile-major `[M / 160][cff / 32][160][32]` for `linear_from_blocked`."""
+    `pack_geglu_frag(weight, 32 if variant == 0 else 16)`.  `blocked`: tile-major `[M / 160][cff / 32][160][32]` for `linear_from_blocked`.
+    `partial_tiles`: any row count on `fmc_geglu_pipe_ln_partial_bf16`; with `blocked` the result owns padded storage (see `linear_from_blocked`)."""
     _dev(h, ln_gamma, ln_beta, w_packed, bias)
     C = h.shape[-1]
     M = h.numel() // C
+    if partial_tiles:
+        if blocked:          # ceil(M / 160) whole tiles; the tensor handed on is the [..., cff]-shaped head of that storage
+            out = torch.empty(ff_blocked_numel(M, cff), dtype=h.dtype, device=h.device)[:M * cff].view(*h.shape[:-1], cff)
+        else:
+            out = torch.empty(*h.shape[:-1], cff, dtype=h.dtype, device=h.device)
+        _log_call("geglu_direct", (M, 2 * cff, C, "partial"), 2.0 * M * 2 * cff * C)
+        _lib.check(_lib.load().fmc_geglu_pipe_ln_partial_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), float(ln_eps),
+                                                              w_packed.data_ptr(), _p(bias), M, cff, C, int(blocked), int(variant), _stream()),
+                   "fmc_geglu_pipe_ln_partial_bf16")
+        return out
     out = torch.empty(*h.shape[:-1], cff, dtype=h.dtype, device=h.device)
     _log_call("geglu_direct", (M, 2 * cff, C), 2.0 * M * 2 * cff * C)
     _lib.check(_lib.load().fmc_geglu_pipe_ln_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), float(ln_eps), w_packed.data_ptr(),
                                                   _p(bias), M, cff, C, int(blocked), int(variant), _stream()), "fmc_geglu_pipe_ln_bf16")
     return out
+
+
+# ---- the feed-forward chain at any row count: partly filled last tile (csrc/geglu_pipe.hip, csrc/gemm_conv.hip: PARTIAL) --------------------------------
+# M is one flat row count: ceil(M / 160) tiles, only the last one ragged.  Taken by `FeedForward.forward_ln` with `PARTIAL_TILES` on.
+def ff_tile_count(M: int, rows: int = 160) -> int:
+    return -(-M // rows)
+
+
+def ff_blocked_numel(M: int, K: int) -> int:
+    """Elements of the tile-major intermediate: ceil(M / 160) WHOLE tiles of `[K / 32][160][32]`."""
+    return ff_tile_count(M) * 160 * K
+
+
+def _ff_on_gpu(t: torch.Tensor) -> bool:
+    """(as `_on_gpu`, for `geglu_ln_partial_ok`: the host tests exercise every other condition of it on CPU tensors)"""
+    return t.is_cuda
+
+
+def geglu_pipe_partial_supported(M: int, cff: int, C: int, variant: int) -> bool:
+    """`fmc_geglu_pipe_partial_supported` (host arithmetic only; tests compare the two)."""
+    Mp = ff_tile_count(M) * 160
+    common = M > 0 and cff > 0 and cff % 128 == 0 and Mp * cff * 2 < (1 << 31) and 2 * cff * C * 2 < (1 << 31) and Mp * C * 2 < (1 << 31)
+    return bool(common and ((variant == 1 and C == 320) or (variant == 0 and C in (320, 640))))
+
+
+def geglu_pipe_partial_variant(C: int) -> int:
+    """The 160-row form at C = 320 (every weight fragment serves twice the rows), the 80-row form at C = 640."""
+    return 1 if C == 320 else 0
+
+
+def geglu_ln_partial_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
+    """`geglu_ln_direct_ok` without the divisibility of M: what `geglu_ln_pipe(..., partial_tiles=True)` takes (both levels on the pipe kernel)."""
+    C = h.shape[-1]
+    M = h.numel() // max(C, 1)
+    if not (_ff_on_gpu(h) and h.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and h.is_contiguous() and weight.shape[1] == C
+            and M >= 1 and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled() and GEGLU_PIPE):
+        return False
+    if not ((GEGLU_DIRECT_640 and C == 640) or (GEGLU_DIRECT_320 and C == 320)):
+        return False
+    return geglu_pipe_partial_supported(M, weight.shape[0] // 2, C, geglu_pipe_partial_variant(C))
+
+
+def geglu_direct_blocked_partial_ok(h: torch.Tensor, w2: torch.Tensor, residual) -> bool:
+    """`geglu_direct_blocked_ok` without `M % 160 == 0`: ceil(M / 160) tiles, more of them than CUs, the padded intermediate below 2 GiB."""
+    C = h.shape[-1]
+    M = h.numel() // C
+    N2, Cff = w2.shape
+    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and M >= 1 and N2 % 320 == 0 and Cff % 64 == 0
+            and ff_tile_count(M) * (N2 // 320) > _cus(h.device) and ff_blocked_numel(M, Cff) * 2 < (1 << 31) and N2 * Cff * 2 < (1 << 31)
+            and w2.dtype == torch.bfloat16 and w2.is_contiguous()
+            and (residual is None or (residual.is_contiguous() and residual.dtype == h.dtype)) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+
+
+def ff_tail_partial_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor]) -> bool:
+    """`ff_tail_ok` without `M % 160 == 0`: at least as many tiles (ceil) as CUs, the padded intermediate below 2 GiB."""
+    C = h.shape[-1]
+    M = h.numel() // C
+    return (FF_TAIL and not torch.is_grad_enabled() and h.dtype == torch.bfloat16 and h.is_contiguous() and wp.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16
+            and wp.ndim == 2 and wp.shape[1] == w2.shape[0] == C and wp.shape[0] % 320 == 0 and C % 64 == 0 and w2.shape[1] % 64 == 0
+            and M >= 1 and ff_tile_count(M) * (wp.shape[0] // 320) >= _cus(h.device) and ff_tile_count(M) * 160 * max(w2.shape[1], C) * 2 < (1 << 31)
+            and wp.shape[0] * (w2.shape[1] + C) * 2 < (1 << 31)
+            and tail_residual is not None and tail_residual.dtype == h.dtype and tail_residual.is_contiguous()
+            and tail_residual.numel() == M * wp.shape[0] and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+
+
+def _blocked_storage_ok(xb: torch.Tensor, M: int, K: int) -> bool:
+    return (xb.untyped_storage().nbytes() - xb.storage_offset() * xb.element_size()) >= ff_blocked_numel(M, K) * xb.element_size()
 
 
 def geglu_ln_direct_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
@@ -1830,8 +1908,13 @@ def geglu_linear_blocked(x: torch.Tensor, weight_il160: torch.Tensor, bias_il160
     return out
 
 
-def linear_from_blocked(xb: torch.Tensor, weight: torch.Tensor, bias, residual, alpha: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`alpha * (x @ weight^T + bias) + residual` for an x in the tile-major layout of `geglu_linear_blocked`; `out`: a contiguous `[M, N]` destination."""
+def linear_from_blocked(xb: torch.Tensor, weight: torch.Tensor, bias, residual, alpha: float = 1.0, out: Optional[torch.Tensor] = None,
+                        partial_tiles: bool = False) -> torch.Tensor:
+    """`alpha * (x @ weight^T + bias) + residual` for an x in the tile-major layout of `geglu_linear_blocked`; `out`: a contiguous `[M, N]` destination.
+    `partial_tiles` (`fmc_linear_bf16_ffblk_partial`; also `ff_tail`): any M.  The shape contract of the tile-major intermediate then, stated once: the
+    tensor has the logical shape `[..., K]` with M rows, and is the HEAD of a storage of `ff_blocked_numel(M, K)` = ceil(M / 160) * 160 * K elements that
+    the data spans in tile order -- what `geglu_ln_pipe(..., blocked=True, partial_tiles=True)` returns.  It is passed on as it is: a copy (`clone`,
+    `contiguous`) keeps M * K elements and loses the last tile.  The pad rows of that tile are never written and may hold anything."""
     _dev(xb, weight, bias, residual, out)
     N, Kd = weight.shape
     M = xb.numel() // Kd
@@ -1839,6 +1922,13 @@ def linear_from_blocked(xb: torch.Tensor, weight: torch.Tensor, bias, residual, 
         out = torch.empty(*xb.shape[:-1], N, dtype=xb.dtype, device=xb.device)
     assert out.is_contiguous() and out.numel() == M * N and out.dtype == xb.dtype
     wt = _w_tilemajor(weight) if W_TILEMAJOR else weight
+    if partial_tiles:
+        assert _blocked_storage_ok(xb, M, Kd), "linear_from_blocked: the tile-major operand does not own its padded storage"
+        _log_call("own_linear", (M, N, Kd, "from-blocked-partial", int(residual is not None)), 2.0 * M * N * Kd)
+        _lib.check(_lib.load().fmc_linear_bf16_ffblk_partial(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd,
+                                                             0 if residual is None else N, float(alpha), int(W_TILEMAJOR), _stream()),
+                   "fmc_linear_bf16_ffblk_partial")
+        return out
     _log_call("own_linear", (M, N, Kd, "from-blocked", int(residual is not None)), 2.0 * M * N * Kd)
     _lib.check(_lib.load().fmc_linear_bf16_ffblk(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd,
                                                  0 if residual is None else N, float(alpha), 0, 1, 0, None, None, None, int(W_TILEMAJOR), _stream()),
@@ -1876,15 +1966,24 @@ def fold_ff_tail(w2: torch.Tensor, b2: Optional[torch.Tensor], wp: torch.Tensor,
 
 
 def ff_tail(mid_blocked: torch.Tensor, h: torch.Tensor, w_cat: torch.Tensor, b_cat: Optional[torch.Tensor], tail_residual: torch.Tensor,
-            gn_hw: int = 0) -> torch.Tensor:
+            gn_hw: int = 0, partial_tiles: bool = False) -> torch.Tensor:
     """`[g | h] @ w_cat^T + b_cat + tail_residual` (`fmc_linear_bf16_fftail`): g = `mid_blocked`, the tile-major gated intermediate; `h` row-major `[M, C]`.
-    With `gn_hw` the 160-row tiles also leave the consumer GroupNorm's partial sums (as `linear_gn`).  Returns `[..., N]` in `tail_residual`'s shape."""
+    With `gn_hw` the 160-row tiles also leave the consumer GroupNorm's partial sums (as `linear_gn`).  Returns `[..., N]` in `tail_residual`'s shape.
+    `partial_tiles`: any M on `fmc_linear_bf16_fftail_partial` (`mid_blocked` as `linear_from_blocked` describes; no GroupNorm partial sums)."""
     _dev(mid_blocked, h, w_cat, b_cat, tail_residual)
     N, Kd = w_cat.shape
     C = h.shape[-1]
     M = h.numel() // C
     assert mid_blocked.numel() == M * (Kd - C) and tail_residual.numel() == M * N
     out = torch.empty_like(tail_residual)
+    if partial_tiles:
+        assert _blocked_storage_ok(mid_blocked, M, Kd - C), "ff_tail: the tile-major operand does not own its padded storage"
+        wt = _w_tilemajor(w_cat) if W_TILEMAJOR else w_cat
+        _log_call("own_linear", (M, N, Kd, "ff-tail-partial", 1), 2.0 * M * N * Kd)
+        _lib.check(_lib.load().fmc_linear_bf16_fftail_partial(mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(),
+                                                              out.data_ptr(), M, N, Kd, Kd - C, C, N, None, 0, int(W_TILEMAJOR), _stream()),
+                   "fmc_linear_bf16_fftail_partial")
+        return out
     part = None
     if gn_hw and gn_emit_ok(M, N, Kd, gn_hw, h.dtype):
         part = torch.empty(M // gn_hw, gn_hw // 160, 32, 2, dtype=torch.float32, device=h.device)

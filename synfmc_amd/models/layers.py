@@ -835,13 +835,47 @@ class FeedForward(nn.Module):
         out = self.net[2]
         return derived(self, "_tail_fold", [out.weight, out.bias, wp, bp], lambda: K.fold_ff_tail(out.weight, out.bias, wp, bp))
 
+    def ln_partial_route(self, h) -> bool:
+        """A row count that does not fill whole tiles, `hip_ops.PARTIAL_TILES` on: `forward_ln` normalises `h` itself on the partial-tile entry points
+        (so the producer of `h` leaves no row statistics).  Never where the whole-tile route exists."""
+        w = self.net[0].proj.weight
+        # (C = 640: only with `hip_ops.GEGLU_PIPE_640`, as on whole tiles -- the 80-row form measured level with the un-fused pair there,
+        #  profiles/partial_tiles.md section 10)
+        return bool(K.PARTIAL_TILES and not torch.is_grad_enabled() and (h.shape[-1] == 320 or K.GEGLU_PIPE_640)
+                    and not K.geglu_ln_direct_ok(h, w) and K.geglu_ln_partial_ok(h, w))
+
+    def _forward_ln_partial(self, h, norm, residual, tail):
+        """`forward_ln` on a partly filled last tile: the pipe kernel, then `ff_tail` where the whole-tile route would use it, else the ordinary
+        output projection."""
+        proj, out = self.net[0], self.net[2]
+        w = proj.proj.weight
+        var = K.geglu_pipe_partial_variant(h.shape[-1])
+        frag = derived(self, "_geglu_frag_partial", [w], lambda: K.pack_geglu_frag(w, 16 if var == 1 else 32), extra=(var,))
+        # the tile-major intermediate only in front of `ff_tail`: `linear_from_blocked(..., partial_tiles=True)` measured slower than the ordinary output
+        # projection on the row-major intermediate at these row counts (profiles/partial_tiles.md section 10) and is not routed to
+        folded = (tail is not None and residual is h and K.geglu_direct_blocked_partial_ok(h, out.weight, residual)
+                  and K.ff_tail_partial_ok(h, out.weight, tail[0], tail[2]))
+        mid = K.geglu_ln_pipe(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=folded,
+                              variant=var, partial_tiles=True)
+        if folded:
+            wc, bc = self._tail_weights(tail[0], tail[1])
+            # (`tail[3]`, gn_hw, is not passed on: the partial tail leaves no GroupNorm partial sums, and the consumer without an `_fmc_gn` tag computes its
+            #  own statistics, as it does wherever `hip_ops.gn_emit_ok` fails)
+            y = K.ff_tail(mid, h, wc, bc, tail[2], partial_tiles=True)
+            y._fmc_tail = True
+            return y
+        return out(mid, residual=residual)
+
     def forward_ln(self, h, norm, residual, tail=None):
         """`ff(norm(h)) + residual` with LayerNorm + GEGLU projection as one launch where `hip_ops.geglu_ln_direct` exists (the 20x32 level), else None.
         `tail = (W_p, b_p, x, gn_hw)`: the caller's next op is `proj_out(.) + x` -- where `hip_ops.ff_tail_ok` holds the result is THAT (tagged `_fmc_tail`)."""
         proj, out = self.net[0], self.net[2]
         w = proj.proj.weight
-        if not K.geglu_ln_direct_ok(h, w) or getattr(h, "_fmc_pending_add", None) is not None or getattr(h, "_fmc_ln", None) is not None \
-                or getattr(h, "_fmc_pending_ln", None) is not None:
+        pending = getattr(h, "_fmc_pending_add", None) is not None or getattr(h, "_fmc_ln", None) is not None \
+            or getattr(h, "_fmc_pending_ln", None) is not None
+        if not pending and self.ln_partial_route(h):
+            return self._forward_ln_partial(h, norm, residual, tail)
+        if not K.geglu_ln_direct_ok(h, w) or pending:
             return None
         M = h.numel() // h.shape[-1]
         pipe = K.geglu_ln_pipe_ok(h, w) and (h.shape[-1] == 320 or K.GEGLU_PIPE_640)
@@ -932,7 +966,8 @@ class BasicTransformerBlock(nn.Module):
             return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
         # the 40x64 level: the feed-forward's norm3 is applied by its GEGLU projection from the row statistics this launch leaves
         # (the feed-forward normalises its input itself: no statistics to leave; nor where a ragged row count keeps its GEMM from taking them, `hip_ops.lnc_ok`)
-        if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) or (partial and not K.lnc_ok(h, self.ff.net[0].proj.weight)):
+        # (nor where the feed-forward takes the partial-tile route, which normalises too)
+        if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) or self.ff.ln_partial_route(h) or (partial and not K.lnc_ok(h, self.ff.net[0].proj.weight)):
             return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
         out, stats = K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps,
                                    frag=frag, partial_tiles=partial)

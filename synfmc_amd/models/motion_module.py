@@ -236,7 +236,7 @@ class TemporalTransformerBlock(nn.Module):
                 wm, bm = proc.merge_wb(h)               # (the bf16 shadows of marked fp32 masters)
                 kw = dict(w_merge_tm=self._merge_packed(proc, wm), pose_term=proc._pose_term(pose, wm, bm, s), merge_scale=s)
             # (row statistics for the feed-forward's LayerNorm-in-GEMM: the 40x64 level, and only while the feed-forward does not normalise its input itself)
-            last = i == n_blocks - 1 and h.shape[-1] == 320 and not K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight)
+            last = i == n_blocks - 1 and h.shape[-1] == 320 and not K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) and not self.ff.ln_partial_route(h)
             if partial and last:                        # (a ragged row count: only where the consuming GEMM takes the statistics, `hip_ops.lnc_ok`)
                 last = K.lnc_ok(h, self.ff.net[0].proj.weight)
             out = K.temporal_block(h, gamma, bpe, self.norms[i].eps, w_qkv, w_o, attn.to_out[0].bias, attn.scale,

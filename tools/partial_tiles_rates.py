@@ -1,7 +1,7 @@
-"""What the partial-tile forms of the fused attention blocks cost at 16x256x384 (profiles/partial_tiles.md).
+"""What the partial-tile forms of the fused attention blocks and of the feed-forward chain cost at 16x256x384 (profiles/partial_tiles.md).
 
-    python tools/partial_tiles_rates.py --kernel      the four new launches next to the un-fused chain each replaces
-    python tools/partial_tiles_rates.py --loop        the 25-step CameraObjCtrlPipeline loop, hip_ops.PARTIAL_TILES off and on
+    python tools/partial_tiles_rates.py --kernel      the new launches next to the un-fused chain each replaces (--legs attn | ff | all)
+    python tools/partial_tiles_rates.py --loop        the 25-step CameraObjCtrlPipeline loop, hip_ops.PARTIAL_TILES off and on (--switch off | on | both)
 
 One GPU process per command.  Nothing is compared with a figure set in advance: the reference of every number is the other leg of the same
 process.
@@ -12,6 +12,9 @@ process.
            to_q GEMM, attention, out-projection + residual; called through the same modules as the model calls them) are each captured in a HIP
            graph of one call and replayed: 4 warm-up replays, then device events around 40.  A graph replay leaves the launches back to back, so the
            chain's figure is the sum of its launches and not the host's enqueue time.  Outputs of the two are compared (rel-inf) before timing.
+           --legs ff: the feed-forward at the same clip, M = 49152 rows x 320 and 12288 x 640 (`FeedForward.forward_ln` with the switch on): LayerNorm +
+           GEGLU projection (`geglu_ln_pipe(..., partial_tiles=True)`) next to `norm.skip` + the GEGLU module; `linear_from_blocked` / `ff_tail`
+           (`partial_tiles=True`) next to the output projection (+ proj_out) on the row-major intermediate; and the whole feed-forward both ways.
 --loop     `bench.py`'s `obj` model (full-width U-Net + CMC + OMC, bf16) through `CameraObjCtrlPipeline`, 25 steps, CFG, captured graph, latents
            out, at 16x256x384.  Two pipelines over the same model, one called with the switch off and one with it on (a pipeline keeps one graph per
            switch setting); a warm-up call each, then `--repeats` timed calls per leg, legs alternated; every run is printed.  Then one eager
@@ -73,7 +76,7 @@ def _init(mod, norms, seed):
             n.weight.add_(1.0)
 
 
-def kernel_mode():
+def attn_legs():
     from synfmc_amd import hip_ops as K
     from synfmc_amd.models import layers as L
     from synfmc_amd.models import motion_module as MM
@@ -130,6 +133,71 @@ def kernel_mode():
                 return sb.attn2(n, encoder_hidden_states=text, attention_mask=None, _residual=hh)
             rows.append(_compare(f"xattn C={C} 32 x {hw} x {C}, 16 per text, S=77", fused_x, chain_x))
             del sb
+    return rows
+
+
+def ff_legs():
+    """The feed-forward legs of --kernel: what `FeedForward.forward_ln` launches on the partial route next to what the model runs at these row counts without it."""
+    from synfmc_amd import hip_ops as K
+    from synfmc_amd.models import layers as L
+    dev, bf = "cuda", torch.bfloat16
+    rows = []
+    with torch.no_grad():
+        for C, hw in ((320, (HEIGHT // 8) * (WIDTH // 8)), (640, (HEIGHT // 16) * (WIDTH // 16))):
+            M = 2 * FRAMES * hw
+            ff, norm, po = L.FeedForward(C), L.LayerNorm(C), L.Linear(C, C)
+            _init(ff, (), 7)
+            _init(norm, (norm,), 8)
+            _init(po, (), 9)
+            ff, norm, po = ff.to(dev, bf).eval(), norm.to(dev, bf).eval(), po.to(dev, bf).eval()
+            h = (torch.randn(2 * FRAMES, hw, C) * 1.2).to(dev, bf)
+            x = torch.randn(2 * FRAMES, hw, C).to(dev, bf)
+            w = ff.net[0].proj.weight
+            assert not K.geglu_ln_direct_ok(h, w) and K.geglu_ln_partial_ok(h, w)
+            var = K.geglu_pipe_partial_variant(C)
+            frag = K.pack_geglu_frag(w, 16 if var == 1 else 32)
+            g, b = L.f32_param(norm, "weight"), L.f32_param(norm, "bias")
+            blocked = K.geglu_direct_blocked_partial_ok(h, ff.net[2].weight, h)
+
+            def on(fn):
+                def run():
+                    K.PARTIAL_TILES = True
+                    try:
+                        return fn()
+                    finally:
+                        K.PARTIAL_TILES = False
+                return run
+
+            def chain_proj():
+                hh, n = norm.skip(h, defer=True)
+                return ff.net[0](n)
+
+            def chain_ff():
+                hh, n = norm.skip(h, defer=True)
+                return ff(n, residual=hh)
+            mid_rm = chain_proj()
+            rows.append(_compare(f"ff C={C} M={M}: LayerNorm + GEGLU projection (pipe, variant {var})",
+                                 lambda: K.geglu_ln_pipe(h, g, b, norm.eps, frag, ff.net[0].proj.bias, w.shape[0] // 2, variant=var, partial_tiles=True), chain_proj))
+            if blocked:
+                mid = K.geglu_ln_pipe(h, g, b, norm.eps, frag, ff.net[0].proj.bias, w.shape[0] // 2, blocked=True, variant=var, partial_tiles=True)
+                out = ff.net[2]
+                rows.append(_compare(f"ff C={C} M={M}: output projection + residual (linear_from_blocked)",
+                                     lambda: K.linear_from_blocked(mid, out.weight, out.bias, h, partial_tiles=True), lambda: out(mid_rm, residual=h)))
+                if K.ff_tail_partial_ok(h, out.weight, po.weight, x):
+                    wc, bc = ff._tail_weights(po.weight, po.bias)
+                    rows.append(_compare(f"ff C={C} M={M}: output projection + proj_out + residuals (ff_tail)",
+                                         lambda: K.ff_tail(mid, h, wc, bc, x, partial_tiles=True), lambda: po(out(mid_rm, residual=h), residual=x)))
+                    pipe = lambda blk: K.geglu_ln_pipe(h, g, b, norm.eps, frag, ff.net[0].proj.bias, w.shape[0] // 2, blocked=blk, variant=var, partial_tiles=True)
+                    rows.append(_compare(f"ff C={C} M={M}: pipe (tile-major) + ff_tail | pipe (row-major) + the two projections",
+                                         lambda: K.ff_tail(pipe(True), h, wc, bc, x, partial_tiles=True), lambda: po(out(pipe(False), residual=h), residual=x)))
+                    rows.append(_compare(f"ff C={C} M={M}: whole feed-forward + proj_out", on(lambda: ff.forward_ln(h, norm, h, tail=(po.weight, po.bias, x, 0))),
+                                         lambda: po(chain_ff(), residual=x)))
+            rows.append(_compare(f"ff C={C} M={M}: whole feed-forward", on(lambda: ff.forward_ln(h, norm, h)), chain_ff))
+    return rows
+
+
+def kernel_mode(legs):
+    rows = (attn_legs() if legs in ("attn", "all") else []) + (ff_legs() if legs in ("ff", "all") else [])
     for r in rows:
         log(f"{r['case']:58s} fused {r['fused_ms']:.4f} ms   chain {r['chain_ms']:.4f} ms   chain / fused {r['chain_ms'] / r['fused_ms']:.2f}   "
             f"rel-inf fused vs chain {r['rel_inf']:.2e}")
@@ -148,7 +216,7 @@ def _compare(case, fused, chain):
             "chain_runs_ms": [round(t[0], 4), round(t[2], 4)], "rel_inf": err}
 
 
-def loop_mode(repeats, steps):
+def loop_mode(repeats, steps, switch="both"):
     import bench
     from synfmc_amd import configs as CM
     from synfmc_amd import hip_ops as K
@@ -185,22 +253,23 @@ def loop_mode(repeats, steps):
                 return time.perf_counter() - t0, torch.as_tensor(out.videos)
             finally:
                 K.PARTIAL_TILES = False
+        legs = {"off": (False,), "on": (True,), "both": (False, True)}[switch]
         outs = {}
-        for on in (False, True):                          # warm-up: autotuning, per-clip packs, graph capture
+        for on in legs:                                   # warm-up: autotuning, per-clip packs, graph capture
             s, outs[on] = call(on)
             log(f"warm-up, switch {'on' if on else 'off'}: {s:.2f} s")
             assert torch.isfinite(outs[on]).all()
         runs = {False: [], True: []}
         for r in range(repeats):
-            for on in (False, True):
+            for on in legs:
                 s, o = call(on)
                 runs[on].append(round(s, 4))
                 assert torch.equal(o, outs[on]), "a leg is not reproducible"
                 log(f"repeat {r}, switch {'on' if on else 'off'}: {s:.4f} s  ({s / steps * 1e3:.2f} ms per step)")
-        diff = rel_inf(outs[True], outs[False])
+        diff = rel_inf(outs[True], outs[False]) if len(legs) == 2 else None
         # ---- one eager step per leg: the launches of the GEMM-shaped front-ends by family ----
         tables = {}
-        for on in (False, True):
+        for on in legs:
             K.call_log = []
             try:
                 call(on, num_inference_steps=1, use_graph=False)
@@ -213,6 +282,13 @@ def loop_mode(repeats, steps):
             tables["on" if on else "off"] = dict(sorted(fam.items()))
             log(f"one eager step, switch {'on' if on else 'off'}: {tables['on' if on else 'off']}")
     off, on_ = runs[False], runs[True]
+    if len(legs) == 1:                                     # one leg (compared across processes: this commit against its parent, both with the switch on)
+        import hashlib
+        digest = hashlib.sha256(outs[legs[0]].float().cpu().numpy().tobytes()).hexdigest()[:16]
+        log(f"switch {switch}: {runs[legs[0]]} s   latents sha256 {digest}")
+        print(json.dumps({"mode": "loop", "clip": f"{FRAMES}x{HEIGHT}x{WIDTH}", "steps": steps, f"{switch}_s": runs[legs[0]], "latents_sha256_16": digest,
+                          "launches_one_eager_step": tables}), flush=True)
+        return
     spread = max(off) - min(off)
     log(f"off: {off} s (spread {spread:.4f} s)   on: {on_} s   slowest on - fastest off: {max(on_) - min(off):+.4f} s   latents on vs off rel-inf {diff:.3e}")
     print(json.dumps({"mode": "loop", "clip": f"{FRAMES}x{HEIGHT}x{WIDTH}", "steps": steps, "off_s": off, "on_s": on_, "off_spread_s": round(spread, 4),
@@ -226,12 +302,14 @@ def main():
     ap.add_argument("--loop", action="store_true")
     ap.add_argument("--repeats", type=int, default=3, help="--loop: timed calls per leg")
     ap.add_argument("--steps", type=int, default=25, help="--loop: denoising steps per call")
+    ap.add_argument("--legs", choices=("attn", "ff", "all"), default="all", help="--kernel: the fused attention blocks, the feed-forward, or both")
+    ap.add_argument("--switch", choices=("off", "on", "both"), default="both", help="--loop: which setting of hip_ops.PARTIAL_TILES to run")
     args = ap.parse_args()
     if args.kernel == args.loop:
         raise SystemExit("one of --kernel / --loop")
     if not torch.cuda.is_available():
         raise SystemExit("tools/partial_tiles_rates.py measures on the MI355X: there is nothing to time without one")
-    kernel_mode() if args.kernel else loop_mode(args.repeats, args.steps)
+    kernel_mode(args.legs) if args.kernel else loop_mode(args.repeats, args.steps, args.switch)
 
 
 if __name__ == "__main__":
