@@ -853,6 +853,33 @@ int fmc_relu_fwd(const void* x, void* y, int64_t n, void* stream);
 int fmc_relu_bwd(const void* dy, const void* y, void* dx, int64_t n, void* stream);
 int fmc_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * MXFP8 feed-forward GEMMs (csrc/gemm_mxfp8.hip; opt-in through hip_ops.FP8_FF, inference only).  OCP MXFP8: e4m3fn elements, one E8M0
+ * scale byte per 32 consecutive elements of the reduction axis: byte = clamp(floor(log2 amax) - 8 + 127, 0, 254) (0 for an all-zero block),
+ * elements x * 2^(127 - byte) clamped to +-448 and rounded to nearest even.  Inputs are finite.  No allocation, no host synchronisation.
+ *
+ * fmc_mxfp8_pack_weight: w [N, K] bf16 -> wq [N, K] e4m3, ws [N, K / 32] E8M0.  geglu_inner == 0: rows in order; geglu_inner = inner
+ *   (N == 2 inner, inner % 64 == 0): packed row 64 t + 32 g + c is source row g * inner + 32 t + c (value and gate rows of a column
+ *   in one wave's tile).  N % 64 == 0, K % 64 == 0.
+ * fmc_layernorm_mxfp8_fwd: xq [M, C], xs [M, C / 32] of LayerNorm(h) (h bf16, rows ldh apart; gamma / beta fp32; fp32 statistics); h is
+ *   read once.  gamma == beta == NULL: the rows of h are quantised with no normalisation, bit for bit the format above.  C % 64 == 0
+ *   (C <= 2048 with gamma), ldh % 8 == 0.
+ * fmc_linear_mxfp8: geglu == 0: out[m, n] = bf16(sum_k dq(x)[m, k] dq(w)[n, k] + bias[n] + residual[m, n]) (out rows ldo, residual rows
+ *   ldres apart, out_scales unused); geglu == 1 (N = inner, weights packed with geglu_inner = N, bias [2 N] value | gate, no residual):
+ *   (value + b_v) * gelu(gate + b_g) written as MXFP8, out = [M, N] e4m3 bytes and out_scales = [M, N / 32] E8M0 (blocks along n).
+ *   fp32 accumulation on v_mfma_scale_f32_32x32x64_f8f6f4; any M >= 1 (a partly filled last row tile reads clamped rows and stores
+ *   nothing past M); K % 64 == 0, N % 64 == 0, operands below 2 GiB, pointers 16-byte aligned (bias 8): fmc_linear_mxfp8_supported.
+ *   Anything else is FMC_E_SHAPE / FMC_E_ALIGN and nothing is written.
+ * fmc_mxfp8_tile_rows / _cols: the output tile of a workgroup (tests reach the ragged tile through them). */
+int fmc_mxfp8_tile_rows(void);
+int fmc_mxfp8_tile_cols(void);
+int fmc_linear_mxfp8_supported(int64_t M, int N, int K, int geglu);
+int fmc_mxfp8_pack_weight(const void* w, void* wq, void* ws, int N, int K, int geglu_inner, void* stream);
+int fmc_layernorm_mxfp8_fwd(const void* h, const void* gamma, const void* beta, void* xq, void* xs, int64_t M, int C, int64_t ldh, float eps,
+                            void* stream);
+int fmc_linear_mxfp8(const void* xq, const void* xs, const void* wq, const void* ws, const void* bias, const void* residual, void* out,
+                     void* out_scales, int64_t M, int N, int K, int64_t ldres, int64_t ldo, int geglu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

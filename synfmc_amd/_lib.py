@@ -182,7 +182,14 @@ SIGNATURES = {
                                                 c_int, c_float, c_void_p]),
     "fmc_xattn_block320_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                                 c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "fmc_conv3x3_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+    "fmc_mxfp8_tile_rows": (c_int, []),
+    "fmc_mxfp8_tile_cols": (c_int, []),
+    "fmc_linear_mxfp8_supported": (c_int, [c_int64, c_int, c_int, c_int]),
+    "fmc_mxfp8_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fmc_layernorm_mxfp8_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_void_p]),
+    "fmc_linear_mxfp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,
+                                 c_int, c_void_p]),
+    "fmc_conv3x3_bf16": (c_int,[c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
 }
 

@@ -1199,6 +1199,96 @@ xattn_block640 = xattn_block
 PARTIAL_TILES = os.environ.get("FMC_PARTIAL_TILES", "0") not in ("", "0")
 
 
+# ---- MXFP8 feed-forward (csrc/gemm_mxfp8.hip): block-scaled e4m3 operands on v_mfma_scale_f32_32x32x64_f8f6f4 ---------------------------------------------
+# One switch opts `FeedForward.forward_ln` in (inference, bf16, no pending tag); read at call time.  Off by default: a step launches what it launched before.
+# The chain is LayerNorm + quantise -> GEGLU GEMM (MXFP8 out) -> output GEMM (bias + residual, bf16 out); profiles/mxfp8_ff.md has the numbers.
+FP8_FF = os.environ.get("FMC_FP8_FF", "0") not in ("", "0")
+# the widths `ff_mxfp8_ok` does NOT route: a level is listed where the slowest run of the new chain did not beat the fastest run of the bf16 chain
+# (tools/mxfp8_ff_rates.py; profiles/mxfp8_ff.md: all three widths of the full-size U-Net at the bench clip, 0.35 / 0.27 / 0.24 ms against 0.24 / 0.22 / 0.22 ms --
+#  the first version of the kernel reaches 0.6 - 1.0 PFLOP/s and its epilogues are not hidden; other widths, which nobody has measured, are routed)
+MXFP8_FF_SLOWER = (320, 640, 1280)
+
+
+def mxfp8_supported(M: int, N: int, K: int, geglu: bool) -> bool:
+    """The domain of `linear_mxfp8` (`fmc_linear_mxfp8_supported`): N output columns (GEGLU: inner), K % 64 == 0, N % 64 == 0, operands below 2 GiB."""
+    return M >= 1 and N >= 64 and K >= 64 and K % 64 == 0 and N % 64 == 0 and M * K < (1 << 31) and (2 if geglu else 1) * N * K < (1 << 31) \
+        and M * N * (1 if geglu else 2) < (1 << 31)
+
+
+def mxfp8_pack_weight(w: torch.Tensor, geglu: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w `[N, K]` bf16 -> (e4m3 bytes `[N, K]` uint8, E8M0 scales `[N, K / 32]` uint8) in the row order `linear_mxfp8` wants; `geglu`: value and gate
+    rows interleaved in 32-row blocks.  Once per weight version (`derived`)."""
+    _dev(w)
+    assert w.ndim == 2 and w.dtype == torch.bfloat16
+    w = w.detach().contiguous()
+    N, Kd = w.shape
+    wq = torch.empty(N, Kd, dtype=torch.uint8, device=w.device)
+    ws = torch.empty(N, Kd // 32, dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.load().fmc_mxfp8_pack_weight(w.data_ptr(), wq.data_ptr(), ws.data_ptr(), N, Kd, N // 2 if geglu else 0, _stream()), "fmc_mxfp8_pack_weight")
+    return wq, ws
+
+
+def layernorm_mxfp8(h: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP8 of LayerNorm(h) over the last dim in one pass: (bytes `[M, C]`, scales `[M, C / 32]`), M = the rows of `h`.  `gamma is None`: the rows of
+    `h` quantised as they are.  `h` bf16 with a dense last dim and one row stride."""
+    _dev(h, gamma, beta)
+    assert h.dtype == torch.bfloat16 and h.stride(-1) == 1
+    C = h.shape[-1]
+    if h.ndim != 2:
+        assert h.is_contiguous()
+        h = h.view(-1, C)
+    M = h.shape[0]
+    xq = torch.empty(M, C, dtype=torch.uint8, device=h.device)
+    xs = torch.empty(M, C // 32, dtype=torch.uint8, device=h.device)
+    _lib.check(_lib.load().fmc_layernorm_mxfp8_fwd(h.data_ptr(), _p(gamma), _p(beta), xq.data_ptr(), xs.data_ptr(), M, C, h.stride(0) if M > 1 else C,
+                                                   float(eps), _stream()), "fmc_layernorm_mxfp8_fwd")
+    _log_call("mxfp8", ("ln", M, C), 0.0)
+    return xq, xs
+
+
+def linear_mxfp8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None, geglu: bool = False):
+    """`dq(xq, xs) @ dq(wq, ws)^T + bias (+ residual)` -> bf16 `[M, N]`, or with `geglu` (weights packed with `geglu=True`, bias `[2 inner]`) the GEGLU
+    product as MXFP8: (bytes `[M, inner]`, scales `[M, inner / 32]`), ready to be the next call's `xq, xs`."""
+    _dev(xq, xs, wq, ws, bias, residual)
+    M, Kd = xq.shape
+    N = wq.shape[0] // 2 if geglu else wq.shape[0]
+    assert xq.is_contiguous() and xs.is_contiguous() and wq.is_contiguous() and ws.is_contiguous() and wq.shape[1] == Kd
+    assert bias is None or (bias.dtype == torch.bfloat16 and bias.is_contiguous() and bias.numel() == wq.shape[0])
+    lib = _lib.load()
+    if geglu:
+        assert residual is None
+        oq = torch.empty(M, N, dtype=torch.uint8, device=xq.device)
+        osc = torch.empty(M, N // 32, dtype=torch.uint8, device=xq.device)
+        _lib.check(lib.fmc_linear_mxfp8(xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), ws.data_ptr(), _p(bias), None, oq.data_ptr(), osc.data_ptr(), M, N, Kd,
+                                        0, 0, 1, _stream()), "fmc_linear_mxfp8")
+        _log_call("mxfp8", ("geglu", M, N, Kd), 4.0 * M * N * Kd)
+        return oq, osc
+    if residual is not None:
+        assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.numel() == M * N
+    out = torch.empty(M, N, dtype=torch.bfloat16, device=xq.device)
+    _lib.check(lib.fmc_linear_mxfp8(xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), ws.data_ptr(), _p(bias), _p(residual), out.data_ptr(), None, M, N, Kd,
+                                    N, N, 0, _stream()), "fmc_linear_mxfp8")
+    _log_call("mxfp8", ("linear", M, N, Kd), 2.0 * M * N * Kd)
+    return out
+
+
+def ff_mxfp8_ok(h: torch.Tensor, w_proj: torch.Tensor, w_out: torch.Tensor, residual: Optional[torch.Tensor]) -> bool:
+    """What the MXFP8 feed-forward chain takes: bf16 tokens `h [..., C]` (contiguous) on the GPU, no gradient, GEGLU weight `[2 inner, C]`, output weight
+    `[C_out, inner]`, both bf16 and inside `mxfp8_supported`, a width outside `MXFP8_FF_SLOWER`, and a residual (or None) that is a plain bf16 tensor of the output's size."""
+    C = h.shape[-1]
+    M = h.numel() // max(C, 1)
+    if not (_on_gpu(h) and h.dtype == torch.bfloat16 and h.is_contiguous() and not torch.is_grad_enabled() and w_proj.dtype == torch.bfloat16
+            and w_out.dtype == torch.bfloat16 and w_proj.ndim == 2 and w_out.ndim == 2 and w_proj.shape[1] == C and w_proj.shape[0] % 2 == 0
+            and w_out.shape[1] == w_proj.shape[0] // 2 and C not in MXFP8_FF_SLOWER and C <= 2048):
+        return False
+    inner, n_out = w_out.shape[1], w_out.shape[0]
+    if residual is not None and not (residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.numel() == M * n_out
+                                     and getattr(residual, "_fmc_pending_add", None) is None and getattr(residual, "_fmc_pending_ln", None) is None):
+        return False
+    return mxfp8_supported(M, inner, C, True) and mxfp8_supported(M, n_out, inner, False)
+
+
 def _tile_units(C: int, xattn: bool) -> int:
     """What a tile of the fused blocks holds: pixels (x 16 frames) of the temporal form, rows of the text cross-attention form."""
     assert C in (320, 640)
@@ -2653,7 +2743,8 @@ call_log = None                     # a list while bench.py records one eager st
 def _log_call(family: str, shape: tuple, flops: float) -> None:
     """One launch of a GEMM-shaped front-end into `call_log` (bench.py: flops per kernel family of the step, and -- by launch order within a
     family -- the in-step duration of one SHAPE of a kernel that serves several).  Families: "own_linear" (one gemm* launch of this library),
-    "vendor" (one hipBLASLt launch), "geglu_direct", "fused_block" (temporal / text cross-attention block), "conv_halo", "conv_halo4"."""
+    "vendor" (one hipBLASLt launch), "geglu_direct", "fused_block" (temporal / text cross-attention block), "conv_halo", "conv_halo4", "mxfp8" (one launch
+    of the MXFP8 feed-forward chain: ("ln" | "geglu" | "linear", M, ...))."""
     if call_log is not None:
         call_log.append((family, tuple(shape), float(flops)))
 

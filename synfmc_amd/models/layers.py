@@ -866,6 +866,25 @@ class FeedForward(nn.Module):
             return y
         return out(mid, residual=residual)
 
+    def mxfp8_route(self, h, residual) -> bool:
+        """`hip_ops.FP8_FF` on: the feed-forward runs on the block-scaled e4m3 GEMMs (csrc/gemm_mxfp8.hip).  Inference on bf16 storage only: marked-trainable
+        modules, fp32 storage and anything under a gradient keep the bf16 routes."""
+        proj, out = self.net[0].proj, self.net[2]
+        return bool(not torch.is_grad_enabled() and not out.__dict__.get(OWN_MARK, False) and not proj.__dict__.get(OWN_MARK, False)
+                    and all(b is None or b.dtype == torch.bfloat16 for b in (proj.bias, out.bias))
+                    and K.ff_mxfp8_ok(h, proj.weight, out.weight, residual))
+
+    def _forward_ln_mxfp8(self, h, norm, residual):
+        """LayerNorm + quantise -> GEGLU GEMM (MXFP8 out) -> output GEMM (+ bias + residual, bf16): three launches, the intermediate never leaves 8 bits.
+        The result carries no tag: the caller's proj_out runs as without the switch (the `ff_tail` fold stays a bf16-only route)."""
+        proj, out = self.net[0].proj, self.net[2]
+        w1q, w1s = derived(self, "_mxfp8_geglu", [proj.weight], lambda: K.mxfp8_pack_weight(proj.weight, geglu=True))
+        w2q, w2s = derived(self, "_mxfp8_out", [out.weight], lambda: K.mxfp8_pack_weight(out.weight))
+        xq, xs = K.layernorm_mxfp8(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps)
+        mq, ms = K.linear_mxfp8(xq, xs, w1q, w1s, proj.bias, geglu=True)
+        y = K.linear_mxfp8(mq, ms, w2q, w2s, out.bias, None if residual is None else residual.reshape(-1, out.weight.shape[0]))
+        return y.view(*h.shape[:-1], out.weight.shape[0])
+
     def forward_ln(self, h, norm, residual, tail=None):
         """`ff(norm(h)) + residual` with LayerNorm + GEGLU projection as one launch where `hip_ops.geglu_ln_direct` exists (the 20x32 level), else None.
         `tail = (W_p, b_p, x, gn_hw)`: the caller's next op is `proj_out(.) + x` -- where `hip_ops.ff_tail_ok` holds the result is THAT (tagged `_fmc_tail`)."""
@@ -873,6 +892,8 @@ class FeedForward(nn.Module):
         w = proj.proj.weight
         pending = getattr(h, "_fmc_pending_add", None) is not None or getattr(h, "_fmc_ln", None) is not None \
             or getattr(h, "_fmc_pending_ln", None) is not None
+        if K.FP8_FF and not pending and not torch.is_grad_enabled() and self.mxfp8_route(h, residual):
+            return self._forward_ln_mxfp8(h, norm, residual)
         if not pending and self.ln_partial_route(h):
             return self._forward_ln_partial(h, norm, residual, tail)
         if not K.geglu_ln_direct_ok(h, w) or pending:

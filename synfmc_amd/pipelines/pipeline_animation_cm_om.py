@@ -271,9 +271,9 @@ class AnimationPipeline:
                 return unet(x, tt, encoder_hidden_states=text, **skw, **kw).sample
             return eager
         from .. import hip_ops as K
-        # (`hip_ops.PARTIAL_TILES` decides launches that a captured graph replays: a graph captured under the other setting is not this step's)
+        # (`hip_ops.PARTIAL_TILES` and `hip_ops.FP8_FF` decide launches that a captured graph replays: a graph captured under another setting is not this step's)
         key = (tuple(x_shape), tuple(text.shape), unet.dtype, pose_feats is not None, traj is not None,
-               shared, bool(t_float), bool(K.PARTIAL_TILES), _weights_version(unet))
+               shared, bool(t_float), bool(K.PARTIAL_TILES), bool(K.FP8_FF), _weights_version(unet))
         r = self._runners.get(key)
         if r is None:
             for k in [k for k in self._runners if k[:-1] == key[:-1]]:      # same shapes, stale weights: drop the graph
