@@ -693,6 +693,28 @@ int64_t fmc_linear_wgrad_workspace_bytes(const fmc_wgrad_problem* problems, int 
 int fmc_linear_wgrad_bf16(const fmc_wgrad_problem* problems, int n_problems, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Weight gradient of a trainable 3x3 / pad 1 convolution, straight into fp32 (csrc/conv_wgrad.hip): the same row-reduction product as
+ * fmc_linear_wgrad_bf16 with an implicit-GEMM loader for the input,
+ *     dw[co][ky][kx][ci] = alpha * sum_{n, yo, xo} dy[n, yo, xo, co] * x[n, s yo + ky - 1, s xo + kx - 1, ci]   (+ dw when accumulate != 0)
+ *   x  [n_img, H, W, Cin]  bf16 NHWC, dy [n_img, Ho, Wo, Cout] bf16 NHWC, Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1, stride s = 1 or 2;
+ *   taps outside the image contribute zero and no address outside x or dy is formed.
+ *   dw fp32, dense: dw_layout = FMC_DW_OIHW is [Cout][Cin][3][3] (a contiguous nn.Conv2d weight), FMC_DW_OHWI is [Cout][3][3][Cin]
+ *   (channels-last).  With accumulate the old value is added unscaled: dw = fma(alpha, sum, dw).
+ *   Domain (ask fmc_conv3x3_wgrad_supported; FMC_E_SHAPE otherwise): n_img, H, W >= 1, Cin % 16 == Cout % 16 == 0, fewer than 2^31 output
+ *   pixels and filter elements.  x and dy 16-byte aligned (FMC_E_ALIGN).
+ *   Long reductions are split over several workgroups by a rule that depends on the shape alone; their fp32 partials go to `workspace`
+ *   (caller-owned, at least fmc_conv3x3_wgrad_workspace_bytes of the same shape; NULL when that is 0) and a second kernel adds them in
+ *   split order: no atomics, no allocation, bit-reproducible.  (`hip_ops.conv3x3_wgrad`)
+ * fmc_conv3x3_wgrad_workspace_bytes: the workspace the shape needs, or -1 (with the error message set) outside the domain.
+ * ------------------------------------------------------------------------------------------- */
+#define FMC_DW_OIHW 0
+#define FMC_DW_OHWI 1
+int fmc_conv3x3_wgrad_supported(int n_img, int H, int W, int Cin, int Cout, int stride);
+int64_t fmc_conv3x3_wgrad_workspace_bytes(int n_img, int H, int W, int Cin, int Cout, int stride);
+int fmc_conv3x3_wgrad_bf16(const void* x, const void* dy, float* dw, int n_img, int H, int W, int Cin, int Cout, int stride, int dw_layout,
+                           float alpha, int accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The fused temporal attention block of the motion modules at the 40x64 level (round 4; csrc/temporal_block.hip).
  * Replaces, for one attention block of `TemporalTransformerBlock.forward` (fmc/models/motion_module.py:287-300) as driven by
  * `TemporalSelfAttention.forward` (:349-389) and `PoseAdaptorAttnProcessor.forward` / `AttnProcessor.__call__`

@@ -155,6 +155,10 @@ SIGNATURES = {
     "fmc_nhwc_to_cmajor_padded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p]),
     "fmc_linear_wgrad_workspace_bytes": (c_int64, [c_void_p, c_int]),
     "fmc_linear_wgrad_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "fmc_conv3x3_wgrad_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_wgrad_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                               c_int64, c_void_p]),
     "fmc_optim_chunk_elems": (c_int, []),
     "fmc_optim_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "fmc_optim_check_tables": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int]),

@@ -13,18 +13,11 @@
 // EXEC all ones: pad, don't mask).  Long reductions are split over `splits` workgroups per tile (a function of the problem's shape
 // only): each writes an fp32 partial into the caller's workspace, and a second kernel sums them in split order -- the result is
 // bit-reproducible, and a problem gives the same bits alone or in a group.
-#include "common.h"
+#include "wgrad_common.h"
 
 namespace {
 
-constexpr int WG_BT = 128;               // tokens per staged slab
-constexpr int WG_BN = 64;                // output rows (columns of A) per workgroup
-constexpr int WG_BK = 64;                // output columns (columns of B) per workgroup
-constexpr int WG_PITCH = 96;             // LDS row pitch in bf16: 192 B, so the 4 rows of a transposed read hit disjoint banks
 constexpr int WG_MAXP = 8;               // problems per launch
-constexpr int WG_MIN_SLABS = 4;          // a split reduces at least 512 tokens
-constexpr int WG_TARGET = 512;           // workgroups a problem is split towards (two per CU)
-constexpr size_t WG_LDS = 4 * 4 * 16 * 64 * sizeof(float);    // 64 KiB: the cross-wave reduction (the two staged slabs, 48 KiB, alias it)
 
 struct WgProblem {
     const bf16_t* a; const bf16_t* b; float* out; float* ws;  // ws: this problem's [splits][N][K] partials (splits > 1)
@@ -37,11 +30,6 @@ struct WgParams {
     int n;
 };
 
-typedef short __attribute__((ext_vector_type(4))) wg_s4;
-__device__ __forceinline__ wg_s4 lds_tr16(const bf16_t* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wg_s4*)(p));
-}
-
 __device__ __forceinline__ void load_slab(const bf16_t* __restrict__ src, int64_t ld, int64_t m0, int64_t m_end, int c0, int ncols,
                                           u32x4 (&r)[4]) {
 #pragma unroll
@@ -50,24 +38,6 @@ __device__ __forceinline__ void load_slab(const bf16_t* __restrict__ src, int64_
         const int64_t m = m0 + row;
         r[i] = (m < m_end && c < ncols) ? *reinterpret_cast<const u32x4*>(src + m * ld + c) : u32x4{0u, 0u, 0u, 0u};
     }
-}
-
-__device__ __forceinline__ void store_slab(bf16_t* __restrict__ dst, const u32x4 (&r)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = threadIdx.x + 256 * i;
-        *reinterpret_cast<u32x4*>(dst + (e >> 3) * WG_PITCH + 8 * (e & 7)) = r[i];
-    }
-}
-
-// operand fragment of the 32 columns [col0, col0 + 32) over tokens 8h .. 8h+7 of the wave's 16-token k-step at row t0
-__device__ __forceinline__ bf16x8 frag(const bf16_t* __restrict__ s, int t0, int col0, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const bf16_t* p = s + (t0 + 8 * (g >> 1) + (i >> 2)) * WG_PITCH + col0 + 16 * (g & 1) + 4 * (i & 3);
-    union { bf16x8 v; wg_s4 h[2]; } r;
-    r.h[0] = lds_tr16(p);                    // tokens +0..3
-    r.h[1] = lds_tr16(p + 4 * WG_PITCH);     // tokens +4..7
-    return r.v;
 }
 
 __global__ void __launch_bounds__(256) wgrad_kernel(const WgParams P) {
@@ -108,26 +78,11 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgParams P) {
             load_slab(pr.a + n0, pr.lda, m1, m_end, 0, pr.N - n0, ra);
             load_slab(pr.b + k0, pr.ldb, m1, m_end, 0, pr.K - k0, rb);
         }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int t0 = 32 * wave + 16 * ks;
-            const bf16x8 fa0 = frag(sa, t0, 0, lane), fa1 = frag(sa, t0, 32, lane);
-            const bf16x8 fb0 = frag(sb, t0, 0, lane), fb1 = frag(sb, t0, 32, lane);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb1, acc[1][1], 0, 0, 0);
-        }
+        slab_mfma(sa, sb, wave, lane, acc);
         __syncthreads();
     }
 
-    // the four waves' partial tiles -> LDS [wave][i * 2 + j][reg][lane], summed in wave order
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((wave * 4 + i * 2 + j) * 16 + r) * 64 + lane] = acc[i][j][r];
+    spill_tiles(red, wave, lane, acc);      // [wave][i * 2 + j][reg][lane], summed in wave order below
     __syncthreads();
     const bool direct = pr.splits == 1;
     float* dst = direct ? pr.out : pr.ws + (int64_t)split * pr.N * pr.K;
@@ -176,12 +131,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const WgParams P) {
 void plan(int64_t M, int N, int K, int& tiles_n, int& tiles_k, int& splits, int& chunk_slabs) {
     tiles_n = (N + WG_BN - 1) / WG_BN;
     tiles_k = (K + WG_BK - 1) / WG_BK;
-    const int64_t slabs = (M + WG_BT - 1) / WG_BT;
-    int64_t s = (WG_TARGET + tiles_n * tiles_k - 1) / (tiles_n * tiles_k);
-    if (s > slabs / WG_MIN_SLABS) s = slabs / WG_MIN_SLABS;
-    if (s < 1) s = 1;
-    chunk_slabs = (int)((slabs + s - 1) / s);
-    splits = (int)((slabs + chunk_slabs - 1) / chunk_slabs);
+    wg_split_plan(M, (int64_t)tiles_n * tiles_k, splits, chunk_slabs);
 }
 
 int check(const fmc_wgrad_problem* problems, int n) {

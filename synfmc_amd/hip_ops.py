@@ -3325,15 +3325,88 @@ def conv3x3_weight_grad(x_nhwc: torch.Tensor, dy_nhwc: torch.Tensor) -> torch.Te
     return dwt.view(3, 3, cin, cout).permute(3, 2, 0, 1)                  # logical [Cout, Cin, ky, kx]
 
 
+CONV_WGRAD = os.environ.get("FMC_CONV_WGRAD", "1") != "0"        # A/B switch: 0 = the fp32 masters' 3x3 dW through `conv3x3_weight_grad` (bf16), as before
+_conv_wgrad_ws = {}
+
+
+def conv3x3_wgrad_ok(n: int, h: int, w: int, cin: int, cout: int, stride: int = 1) -> bool:
+    """The domain of `fmc_conv3x3_wgrad_bf16`: any n, H, W >= 1, stride 1 or 2, Cin % 16 == Cout % 16 == 0 (and 32-bit pixel / filter counts)."""
+    return (min(n, h, w) >= 1 and stride in (1, 2) and cin >= 16 and cout >= 16 and cin % 16 == 0 and cout % 16 == 0
+            and n * ((h - 1) // stride + 1) * ((w - 1) // stride + 1) < 2 ** 31 and 9 * cin * cout < 2 ** 31)
+
+
+CONV_WGRAD_MAX_FLOPS = 80e9      # stride 1: above this the old chain's 128 x 128-tile GEMMs win (profiles/conv_wgrad.md: 832 -> 320 at 16 x 32 x 48, 118 GFLOP)
+
+
+def conv3x3_wgrad_routed(n: int, h: int, w: int, cin: int, cout: int, stride: int = 1) -> bool:
+    """Whether `_Conv3x3Trainable` sends an fp32 master's dW to `conv3x3_wgrad`: inside the kernel's domain and, where the old chain exists
+    (stride 1), not in the shape class in which that chain measured faster by more than its own spread."""
+    return conv3x3_wgrad_ok(n, h, w, cin, cout, stride) and (stride == 2 or 2.0 * n * h * w * 9 * cin * cout <= CONV_WGRAD_MAX_FLOPS)
+
+
+def conv3x3_wgrad(x_nhwc: torch.Tensor, dy_nhwc: torch.Tensor, stride: int = 1, alpha: float = 1.0, out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False) -> torch.Tensor:
+    """`alpha * dW` (+ out) of a 3x3 / pad 1 / stride 1 or 2 convolution, fp32 `[Cout, Cin, 3, 3]`, from its contiguous bf16 NHWC input
+    `[N, H, W, Cin]` and output gradient `[N, Ho, Wo, Cout]`: one `fmc_conv3x3_wgrad_bf16` launch (csrc/conv_wgrad.hip), plus its combine
+    when the pixel reduction is split.  `out` may be contiguous or channels-last; `out=None` allocates a contiguous one."""
+    _dev(x_nhwc, dy_nhwc, out)
+    n, H, W, cin = x_nhwc.shape
+    cout = dy_nhwc.shape[-1]
+    ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    assert x_nhwc.dtype == torch.bfloat16 and dy_nhwc.dtype == torch.bfloat16 and x_nhwc.is_contiguous() and dy_nhwc.is_contiguous()
+    assert tuple(dy_nhwc.shape) == (n, ho, wo, cout), "conv3x3_wgrad: dy must be [N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout]"
+    if not conv3x3_wgrad_ok(n, H, W, cin, cout, stride):
+        raise RuntimeError(f"conv3x3_wgrad: no kernel for n={n} H={H} W={W} Cin={cin} Cout={cout} stride={stride}")
+    if out is None:
+        out = torch.empty(cout, cin, 3, 3, dtype=torch.float32, device=x_nhwc.device)
+        accumulate = False
+    assert out.dtype == torch.float32 and tuple(out.shape) == (cout, cin, 3, 3)
+    layout = 0 if out.is_contiguous() else 1
+    assert layout == 0 or out.is_contiguous(memory_format=torch.channels_last), "conv3x3_wgrad: out must be contiguous or channels-last"
+    lib = _lib.load()
+    need = lib.fmc_conv3x3_wgrad_workspace_bytes(n, H, W, cin, cout, stride)
+    if need < 0:
+        _lib.check(-1, "fmc_conv3x3_wgrad_bf16")
+    ws, ws_bytes = None, 0
+    if need > 0:
+        dev = out.device
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+        buf = _conv_wgrad_ws.get(key)
+        if buf is None or buf.numel() * 4 < need:
+            if buf is not None:
+                _ws_retired.append(buf)        # a captured HIP graph may have baked its address
+            buf = torch.empty(need // 4 + 1024, dtype=torch.float32, device=dev)
+            _conv_wgrad_ws[key] = buf
+        ws, ws_bytes = buf.data_ptr(), buf.numel() * 4
+    _log_call("conv_wgrad", (n, H, W, cin, cout, stride), 2.0 * n * ho * wo * 9 * cin * cout)
+    _lib.check(lib.fmc_conv3x3_wgrad_bf16(x_nhwc.data_ptr(), dy_nhwc.data_ptr(), out.data_ptr(), n, H, W, cin, cout, stride, layout, float(alpha),
+                                          int(bool(accumulate)), ws, ws_bytes, _stream()), "fmc_conv3x3_wgrad_bf16")
+    return out
+
+
+def conv3x3_trainable_ok(n: int, h: int, w: int, cin: int, cout: int, stride: int = 1) -> bool:
+    """Whether `conv3x3_trainable` has all three kernels for a bf16 `[n, cin, h, w]` input.  Stride 1: the forward needs Cin % 64 == 0 and the
+    flipped-filter dX, whose input channels are Cout, needs Cout % 64 == 0 (`conv3x3_supported` on either filter); dW would take any multiple
+    of 16.  Stride 2: even h, w, the same forward rule and `conv3x3_down_bwd_supported` for dX."""
+    if cin % 64 or cout % 64 or not conv3x3_wgrad_ok(n, h, w, cin, cout, stride):
+        return False
+    return stride == 1 or (h % 2 == 0 and w % 2 == 0 and conv3x3_down_bwd_supported(n, h, w, cin, cout))
+
+
 class _Conv3x3Trainable(torch.autograd.Function):
-    """3x3 / stride 1 / pad 1 conv whose FILTER trains (OMC Adapter, camera encoder): forward, backward-data AND the weight
-    gradient on the gfx950 kernels -- forward / dX on the implicit-GEMM kernel (the filter is re-laid-out / flipped per step:
-    it changes every step and is small next to the activations), dW as pixel-reduction GEMMs (`conv3x3_weight_grad`)."""
+    """3x3 / pad 1 conv whose FILTER trains (OMC Adapter, camera encoder): forward, backward-data AND the weight gradient on the gfx950
+    kernels.  Stride 1: forward / dX on the implicit-GEMM kernel (the filter is re-laid-out / flipped per step: it changes every step and
+    is small next to the activations).  Stride 2 (even H, W; shadows only): the stride-2 forward, dX on `conv3x3_down_bwd`.  dW of an fp32
+    master: one `conv3x3_wgrad` launch straight into fp32; of a bf16 parameter (autocast) or with FMC_CONV_WGRAD=0: pixel-reduction GEMMs
+    rounded to bf16 (`conv3x3_weight_grad`, stride 1 only)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, w_run=None, b_run=None):
+    def forward(ctx, x, weight, bias, w_run=None, b_run=None, stride=1):
         ctx.has_bias = bias is not None
         ctx.shadow = w_run is not None
+        ctx.stride = stride
+        assert stride == 1 or (stride == 2 and ctx.shadow and CONV_WGRAD and weight.dtype == torch.float32), \
+            "conv3x3_trainable: stride 2 needs the bf16 shadows of an fp32 master and the direct weight gradient"
         with torch.no_grad():
             if w_run is None:
                 w_run = weight.detach().to(x.dtype)
@@ -3343,6 +3416,9 @@ class _Conv3x3Trainable(torch.autograd.Function):
                 w_cl = derived_on_owner(w_run, "_fmc_w_cl", None, lambda: w_run.contiguous(memory_format=torch.channels_last))
             ctx.save_for_backward(x, weight if not ctx.shadow else w_run)
             ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+            if stride == 2:
+                ctx.w_cl = w_cl
+                return conv3x3(x, w_cl, b_run, None, None, (2, 2), (1, 1))
             return conv3x3(x, w_cl, b_run)
 
     @staticmethod
@@ -3351,24 +3427,33 @@ class _Conv3x3Trainable(torch.autograd.Function):
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = dw = db = None
         with torch.no_grad():
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[0] and ctx.stride == 2:
+                dx = conv3x3_down_bwd(_nhwc(dy), _w_resample_bwd_packed(ctx.w_cl, False), x.shape[1]).permute(0, 3, 1, 2)
+            elif ctx.needs_input_grad[0]:
                 flip = lambda: weight.detach().to(dy.dtype).flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last)
                 dx = conv3x3(dy, derived_on_owner(weight, "_fmc_w_flip", None, flip) if ctx.shadow else flip(), None)
             if ctx.needs_input_grad[1]:
-                dw = conv3x3_weight_grad(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)).to(ctx.dtypes[0])
+                n, cin, h, w = x.shape
+                if (CONV_WGRAD and ctx.dtypes[0] == torch.float32 and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
+                        and conv3x3_wgrad_routed(n, h, w, cin, dy.shape[1], ctx.stride)):
+                    dw = conv3x3_wgrad(_nhwc(x), _nhwc(dy), ctx.stride)       # (views: both are channels-last)
+                else:
+                    assert ctx.stride == 1
+                    dw = conv3x3_weight_grad(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)).to(ctx.dtypes[0])
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 if ctx.shadow and dy.dtype == torch.bfloat16:
                     db = column_sum(dy.permute(0, 2, 3, 1).reshape(-1, dy.shape[1])).to(ctx.dtypes[1])
                 else:
                     db = dy.sum(dim=(0, 2, 3), dtype=torch.float32).to(ctx.dtypes[1])
-        return dx, dw, (db if ctx.has_bias else None), None, None
+        return dx, dw, (db if ctx.has_bias else None), None, None, None
 
 
-def conv3x3_trainable(x, weight, bias=None, w_run=None, b_run=None):
-    """3x3 / stride 1 / pad 1 convolution whose filter trains (see `_Conv3x3Trainable`).  `w_run` / `b_run`: the filter / bias in x's dtype
-    (cached bf16 shadows of fp32 masters, `layers.bf16_param`): their channels-last and flipped forms are then derived once per version
-    and the bias gradient is `column_sum`; default: a cast per call."""
-    return _Conv3x3Trainable.apply(x, weight, bias, w_run, b_run)
+def conv3x3_trainable(x, weight, bias=None, w_run=None, b_run=None, stride: int = 1):
+    """3x3 / pad 1 convolution whose filter trains (see `_Conv3x3Trainable`).  `w_run` / `b_run`: the filter / bias in x's dtype
+    (cached bf16 shadows of fp32 masters, `layers.bf16_param`): their channels-last, flipped and packed forms are then derived once per
+    version and the bias gradient is `column_sum`; default: a cast per call.  `stride=2` (even H, W) needs the shadows of an fp32 master;
+    ask `conv3x3_trainable_ok`."""
+    return _Conv3x3Trainable.apply(x, weight, bias, w_run, b_run, stride)
 
 
 # --------------------------------------------------------------------------------------------

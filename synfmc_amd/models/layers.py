@@ -350,9 +350,11 @@ class Conv2d(nn.Conv2d):
 
     def _forward_own(self, x, temb, residual, temb_div, upsample, x2, emit_gn):
         """A marked convolution with fp32 masters on bf16 activations (`own_trainable`).  Without a gradient: the forward of the bf16
-        shadows (`shadow_twin`).  Under a gradient: a 1x1 as a token GEMM on `linear_trainable`, a 3x3 / stride 1 / pad 1 with channel
-        counts that are multiples of 64 on `conv3x3_trainable`, both reading the cached shadows; any other form (a stride-2 3x3, thin
-        channels, a time embedding) and FMC_TRAINABLE_OWN=0 take torch ops on differentiably cast weights."""
+        shadows (`shadow_twin`).  Under a gradient: a 1x1 as a token GEMM on `linear_trainable`, a 3x3 / pad 1 of stride 1, or of stride 2
+        on an even-sized input, on `conv3x3_trainable` where `hip_ops.conv3x3_trainable_ok` finds a forward, a backward-data and a
+        weight-gradient kernel (channel counts that are multiples of 64: the forward and dX set that, dW alone would take multiples of 16),
+        both reading the cached shadows; any other form (thin channels, an odd-sized stride-2 input, a time embedding) and
+        FMC_TRAINABLE_OWN=0 take torch ops on differentiably cast weights."""
         if not torch.is_grad_enabled():
             return shadow_twin(self)(x, temb=temb, residual=residual, temb_div=temb_div, upsample=upsample, x2=x2, emit_gn=emit_gn)
         if self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and temb is None and not upsample:
@@ -364,10 +366,11 @@ class Conv2d(nn.Conv2d):
         assert x2 is None, "two-source input: 1x1 convs only"
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
-        if (TRAINABLE_OWN and not upsample and temb is None and residual is None and self.kernel_size == (3, 3) and self.stride == (1, 1)
-                and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and self.in_channels % 64 == 0
-                and self.out_channels % 64 == 0):
-            return K.conv3x3_trainable(x, self.weight, self.bias, bf16_param(self, "weight"), bf16_param(self, "bias"))
+        if (TRAINABLE_OWN and not upsample and temb is None and residual is None and self.kernel_size == (3, 3) and self.padding == (1, 1)
+                and self.dilation == (1, 1) and self.groups == 1 and self.stride in ((1, 1), (2, 2))
+                and (self.stride == (1, 1) or (K.CONV_WGRAD and K.RESAMPLE_BWD))
+                and K.conv3x3_trainable_ok(x.shape[0], x.shape[2], x.shape[3], self.in_channels, self.out_channels, self.stride[0])):
+            return K.conv3x3_trainable(x, self.weight, self.bias, bf16_param(self, "weight"), bf16_param(self, "bias"), self.stride[0])
         if upsample:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
         y = F.conv2d(x, self.weight.to(x.dtype), None if self.bias is None else self.bias.to(x.dtype), self.stride, self.padding,

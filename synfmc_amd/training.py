@@ -723,7 +723,7 @@ def camera_trainable_parameters(unet, pose_encoder) -> List[torch.nn.Parameter]:
     training route: run the step with bf16 activations and NO autocast.  The encoder then casts its input to bf16; forward, dX, dW and db of
     every projection, 1x1 and 3x3 convolution, the GEGLU feed-forwards, the average pools, ReLUs and the merges run on this library's
     kernels, reading cached bf16 shadows (`layers.bf16_param`) that `FusedAdamW.attach(unet, pose_encoder)` refreshes in its update.
-    Buffers keep their dtype.  Not covered: `Downsample(use_conv=True)` (torch ops on cast weights), fp32 activations (the torch route as before); a U-Net with `q_merge` / `kv_merge`
+    Buffers keep their dtype.  Not covered: a `Downsample(use_conv=True)` on an odd-sized input and 3x3 convolutions whose channel counts are no multiples of 64 (torch ops on cast weights), fp32 activations (the torch route as before); a U-Net with `q_merge` / `kv_merge`
     processors is refused."""
     partial = [n for n, m in unet.named_modules() if hasattr(m, "q_merge") or hasattr(m, "kv_merge")]
     if partial:

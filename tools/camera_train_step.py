@@ -9,6 +9,12 @@ encoder's gradients vanish.
   parent route: the Camera Encoder (stage 2) / OMC Adapter (stage 3) as fp32 modules under bf16 autocast, the merges bf16 parameters --
                 torch autograd on MIOpen / hipBLASLt / at::native kernels for the trained layers;
   new route:    `camera_trainable_parameters` / `omc_trainable_parameters` -- fp32 masters, bf16 activations, no autocast, `FusedAdamW`.
+    python tools/camera_train_step.py --conv-wgrad [--steps 20 --warmup 3]   # the new route with the direct 3x3 weight gradient off and on
+
+--conv-wgrad: one model per stage on the new route; `hip_ops.CONV_WGRAD` (FMC_CONV_WGRAD) is toggled between legs of `--steps` timed steps,
+off, on, off, on (every leg is printed: the two legs of a setting show its spread), then one step per setting with `hip_ops.call_log` on
+and `conv3x3_weight_grad` counted: the `conv_wgrad` entries and the calls of the old chain (each is two `fmc_nhwc_to_cmajor_padded`
+launches, three GEMMs, a stack and a cast).
 Prints one JSON line."""
 import argparse
 import json
@@ -154,8 +160,55 @@ def step_time(stage: str, route: str, steps: int, warmup: int) -> float:
     return ms
 
 
+def timed_steps(step, steps: int) -> float:
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def conv_wgrad_ab(stage: str, steps: int, warmup: int) -> dict:
+    """The new route of one stage with `hip_ops.CONV_WGRAD` off and on, alternated in one process on one model."""
+    from synfmc_amd import hip_ops as K
+    step, _ = stage2_step_fn(*build_stage2(), "new") if stage == "stage2" else stage3_step_fn(*build_stage3(), "new")
+    saved = K.CONV_WGRAD
+    legs = {"off_ms": [], "on_ms": []}
+    counts = {}
+    try:
+        for on in (False, True):                       # both settings warm: autotuning, packs, workspaces
+            K.CONV_WGRAD = on
+            for _ in range(warmup):
+                step()
+        for _ in range(2):
+            for on in (False, True):
+                K.CONV_WGRAD = on
+                legs["on_ms" if on else "off_ms"].append(round(timed_steps(step, steps), 3))
+        real, old_calls = K.conv3x3_weight_grad, []
+        K.conv3x3_weight_grad = lambda *a, **k: (old_calls.append(1), real(*a, **k))[1]
+        try:
+            for on in (False, True):
+                K.CONV_WGRAD, K.call_log = on, []
+                del old_calls[:]
+                step()
+                counts["on" if on else "off"] = {"conv_wgrad_entries": sum(1 for e in K.call_log if e[0] == "conv_wgrad"),
+                                                 "old_chain_calls": len(old_calls), "logged_launches": len(K.call_log)}
+        finally:
+            K.conv3x3_weight_grad, K.call_log = real, None
+    finally:
+        K.CONV_WGRAD = saved
+    del step
+    torch.cuda.empty_cache()
+    spread = max(legs["off_ms"]) - min(legs["off_ms"])
+    return dict(legs, off_spread_ms=round(spread, 3), on_minus_off_ms=round(min(legs["on_ms"]) - min(legs["off_ms"]), 3), one_step=counts)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--conv-wgrad", action="store_true", help="the new route with FMC_CONV_WGRAD off and on, legs alternated")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", choices=["stage2", "stage3"], help="one stage alone (for a kernel trace of it)")
@@ -163,6 +216,13 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("camera_train_step needs the MI355X")
+    if args.conv_wgrad:
+        out = {"tool": "camera_train_step", "mode": "conv_wgrad", "frames": FRAMES, "pixels": [H, W], "steps": args.steps, "warmup": args.warmup}
+        for stage in ("stage2", "stage3"):
+            out[stage] = conv_wgrad_ab(stage, args.steps, args.warmup)
+            print(stage, out[stage], file=sys.stderr, flush=True)
+        print(json.dumps(out))
+        return
     if args.only:
         ms = step_time(args.only, args.route, args.steps, args.warmup)
         print(json.dumps({"tool": "camera_train_step", "stage": args.only, "route": args.route, "ms_per_step": round(ms, 3), "steps": args.steps}))
