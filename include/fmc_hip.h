@@ -508,6 +508,42 @@ int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* 
 int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide);
 int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
                                 float* gn_partials, int wide, void* stream);
+/* The halo convolutions at ANY image width: partly filled column tiles.  Each *_partial_* entry is the entry of the same name above with its width
+ * rule dropped (W >= 1; every other condition, every operand and the packed filters -- there are no new pack routines -- are the same).  The column
+ * tile count is a ceiling, ceil(W / 32) for conv_halo and ceil(W / tw) for conv_halo4; the last tile of an image row holds the W - x0 columns that
+ * exist: a pad column is multiplied on zeros-padded input like any other and never fetched from (shortcut sources, residual), stored to, summed
+ * into the statistics or written to the split-K workspace.  A whole-tile shape gives the bits, output and statistics, of the whole-tile entry (for
+ * conv_halo4 at the geometry that entry picks: tw = 16 where W % 16 == 0, else 8).
+ *   conv_halo: gn_partials is [n_img, ceil(H / 10) * ceil(W / 32), 32, 2] (fold: 4 x as many splits, [source tile][phase]);
+ *     fmc_conv3x3_halo_partial_tiles_per_image returns the middle extent.
+ *   conv_halo4: the caller names the row-block geometry `tw`, 16 (10 x 16 pixels; the only one of the wide form) or 8 (5 x 8);
+ *     fmc_conv3x3_halo4_partial_tw returns the default -- the whole-tile entry's where W % 8 == 0, else the one with fewer pad pixels over the image,
+ *     ceil(H / TH) TH ceil(W / tw) tw, ties to 16.  gn_partials is [n_img, ceil(H / TH) * ceil(W / tw), 32, 2] with TH = 10 (tw 16) or 5 (tw 8):
+ *     fmc_conv3x3_halo4_partial_row_blocks_per_image; fmc_conv3x3_halo4_partial_tiles counts the workgroups of one split.
+ * The whole-tile entries keep refusing ragged widths. */
+int fmc_conv3x3_halo_partial_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x);
+int fmc_conv3x3_halo_partial_tiles_per_image(int H, int W);
+int fmc_conv3x3_halo_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                  const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                  int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream);
+int fmc_conv3x3_halo_sc_partial_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1);
+int fmc_conv3x3_halo_sc_partial_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
+                                     const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                     int temb_img_div, float* gn_partials, void* stream);
+int fmc_conv3x3_halo_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout);
+int fmc_conv3x3_halo_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                       int Cout, float* gn_partials, void* stream);
+int fmc_conv3x3_halo4_partial_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide);
+int fmc_conv3x3_halo4_partial_tw(int H, int W, int wide);
+int fmc_conv3x3_halo4_partial_row_blocks_per_image(int H, int W, int tw);
+int fmc_conv3x3_halo4_partial_tiles(int n_img, int H, int W, int Cout, int wide, int tw);
+int fmc_conv3x3_halo4_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                   const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                   int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes,
+                                   int wide, int tw, void* stream);
+int fmc_conv3x3_halo4_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide);
+int fmc_conv3x3_halo4_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                        int Cout, float* gn_partials, int wide, int tw, void* stream);
 /* Backward-data of the two resampling convolutions (training, frozen filter; csrc/conv_resample_bwd.hip).  The filter is the forward's
  * [Cout][3][3][Cin] (channels-last), Cin % 64 == 0 and Cout % 64 == 0, any n_img >= 1, every tensor below 2^31 bytes; dY and dX are channels-last bf16,
  * fp32 accumulation on v_mfma_f32_16x16x32_bf16, bias-free (a bias has no data gradient).  No W % 8 / W % 32 rule: the tiles run over a flat pixel list.

@@ -97,6 +97,24 @@ SIGNATURES = {
     "fmc_conv3x3_halo_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fmc_conv3x3_halo4_fold_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fmc_conv3x3_halo4_fold_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "fmc_conv3x3_halo_partial_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_partial_tiles_per_image": (c_int, [c_int, c_int]),
+    "fmc_conv3x3_halo_partial_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                              c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "fmc_conv3x3_halo_sc_partial_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_sc_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "fmc_conv3x3_halo_fold_partial_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo_fold_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fmc_conv3x3_halo4_partial_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_partial_tw": (c_int, [c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_partial_row_blocks_per_image": (c_int, [c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_partial_tiles": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_partial_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                               c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "fmc_conv3x3_halo4_fold_partial_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fmc_conv3x3_halo4_fold_partial_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                                    c_void_p]),
     "fmc_conv3x3_down_bwd_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "fmc_conv3x3_down_bwd_packed_bytes": (c_int64, [c_int, c_int]),
     "fmc_conv3x3_down_bwd_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

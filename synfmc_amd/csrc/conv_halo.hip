@@ -19,6 +19,10 @@
 //
 // Roofline: MFMA bound.  Algorithmic flops per launch = 2 * n_img*H*W * Cout * 9*Cin; algorithmic bytes = x + w + out (+ residual).
 //
+// Image width: fmc_conv3x3_halo_bf16 / _sc_bf16 / _fold_bf16 take W % 32 == 0 (tiles_x = W / 32); the *_partial_* entry points (`PARTIAL`, see conv_halo_kernel) take
+// any W >= 1 with tiles_x = ceil(W / 32) and a partly filled last column tile, on the same packed filters.  The whole-tile instantiations are the
+// instruction streams they were (profiles/partial_tiles.md section 15); what the partial launches cost per shape is in section 17.
+//
 // What this kernel shares with its small-feature-map geometry (conv_halo4.hip) -- the common parameters, halo piece addressing, the W stream, the
 // filter pack kernels (compiled here), the host-side checks -- is in conv_halo_common.h.
 #include "conv_halo_common.h"
@@ -79,7 +83,12 @@ template <bool SC> constexpr int nreq(int i) { return nh(i) + (SC && i == 16 ? N
 // the epilogue's bias + temb sum.  Staging: shortcut chunk 0 takes the place of "the next chunk" of the last 3x3 chunk; chunk k + 1's interior
 // pieces are requested in the second sub-tile of chunk k - 1 and written in the second sub-tile of chunk k into the buffer chunk k - 1 released
 // -- one sub-tile ahead of their first read, so that sub-tile drains its LDS operations in front of its first barrier.
-template <int GN, bool PH = false, bool SC = false>
+//
+// PARTIAL: images of ANY width.  tiles_x = ceil(W / TW), and the last column tile of a row holds min(TW, W - x0) real columns.  The main loop needs
+// nothing: a halo pixel with x >= W is outside the image and staged as zeros already (h_pix = -1, in `ups` and GroupNorm mode alike), so a pad column
+// is multiplied like any other and what it accumulates is dropped.  The shortcut interior pieces, the residual burst, the output stores and the
+// statistics sums ask whether their column exists; every thread runs the same barriers and counted waits as in the whole-tile form.
+template <int GN, bool PH = false, bool SC = false, bool PARTIAL = false>
 __global__ __launch_bounds__(512, 2)
 void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
     static_assert(!SC || (GN == 0 && !PH), "the shortcut mode is a plain 9-tap convolution");
@@ -158,7 +167,8 @@ void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
     const int sc_lds = pg * PLANE + ((sc_row + 1) * HWID + 8 * (wave & 3) + pp + 1) * 16;      // + j * 2 * HWID * 16 (+ buffer)
     u32x4 hsc[NSCP];
     auto sc_load = [&](int j, int k, u32x4& dst) {
-        const int hp = (k >= 0 && y0 + sc_row + 2 * j < P.H) ? sc_pix0 + 2 * j * P.W : -1;
+        int hp = (k >= 0 && y0 + sc_row + 2 * j < P.H) ? sc_pix0 + 2 * j * P.W : -1;
+        if constexpr (PARTIAL) hp = x0 + 8 * (wave & 3) + pp < P.W ? hp : -1;      // a pad column fetches nothing (the word there is the next row's)
         dst = halo::piece_load(rsS, rsS2, cs1, cs2, hp, pg, k * 64, k, nsc);
     };
     auto sc_store = [&](int j, int buf, const u32x4& v) { *reinterpret_cast<u32x4*>(smem_raw + buf * HALO + sc_lds + j * (2 * HWID * 16)) = v; };
@@ -422,6 +432,11 @@ void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
     bf16_t* Os = reinterpret_cast<bf16_t*>(smem_raw);        // [320][OP] = 107,520 B
     constexpr int CPR = BN / 8;                              // 20 sixteen-byte chunks per row
     const int vrows = min(TH, P.H - y0) * TW;                // (rows of a tile that hangs over the image's last row are not stored)
+    const int vcols = PARTIAL ? min(TW, P.W - x0) : TW;      // (PARTIAL: nor are the columns of a tile that hangs over its right border)
+    auto row_valid = [&](int r) -> bool {
+        if constexpr (PARTIAL) return r < vrows && (r & 31) < vcols;
+        return r < vrows;
+    };
     auto row_pixel = [&](int r) -> int64_t {
         if constexpr (PH) return ((int64_t)img * (2 * P.H) + 2 * (y0 + (r >> 5)) + py) * (2 * P.W) + 2 * (x0 + (r & 31)) + px_;      // pixel shuffle
         return ((int64_t)img * P.H + y0 + (r >> 5)) * P.W + x0 + (r & 31);
@@ -464,7 +479,7 @@ void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
 #pragma unroll
             for (int it = 0; it < 7; ++it) {
                 const int cidx = min(tid + (7 * h + it) * 512, BM * CPR - 1), r = cidx / CPR, ch = cidx - r * CPR;
-                rv[it] = *reinterpret_cast<const u32x4*>(P.res + row_pixel(r < vrows ? r : 0) * P.cout + n0 + ch * 8);
+                rv[it] = *reinterpret_cast<const u32x4*>(P.res + row_pixel(row_valid(r) ? r : 0) * P.cout + n0 + ch * 8);
             }
 #pragma unroll
             for (int it = 0; it < 7; ++it) {
@@ -497,6 +512,7 @@ void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
     if (P.gn_part) {
         const int gl = tid % GT;
         for (int r = tid / GT; r < vrows; r += RP) {
+            if constexpr (PARTIAL) { if ((r & 31) >= vcols) continue; }
             const unsigned* wsrc = reinterpret_cast<const unsigned*>(Os + r * OP + gl * cpg);
             for (int k = 0; k < cpg / 2; ++k) {
                 const unsigned u = wsrc[k];
@@ -508,7 +524,7 @@ void conv_halo_kernel(const std::conditional_t<SC, CHParamsSC, CHParams> P) {
     }
     for (int cidx = tid; cidx < BM * CPR; cidx += 512) {
         const int r = cidx / CPR, ch = cidx - r * CPR;
-        if (r < vrows)
+        if (row_valid(r))
             *reinterpret_cast<u32x4*>(P.out + row_pixel(r) * P.cout + n0 + ch * 8) = *reinterpret_cast<const u32x4*>(Os + r * OP + ch * 8);
     }
     if (P.gn_part) {
@@ -640,14 +656,23 @@ extern "C" int fmc_conv3x3_halo_pack_weight(const void* w, void* dst, int Cin, i
     return 0;
 }
 
-extern "C" int fmc_conv3x3_halo_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x) {
-    if (n_img < 1 || H < 1 || W < 1 || W % TW || Cin % 64 || Cout % BN) return 0;
+// (the conditions of the whole-tile and the PARTIAL entry points: the latter drop the width rule alone)
+static int halo_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, bool any_width) {
+    if (n_img < 1 || H < 1 || W < 1 || (!any_width && W % TW) || Cin % 64 || Cout % BN) return 0;
     if (Cin1 <= 0 || Cin1 > Cin || Cin1 % 64) return 0;
     if (upsample2x && ((H | W) & 1)) return 0;
     const int64_t hs = upsample2x ? H / 2 : H, ws = upsample2x ? W / 2 : W;
     if ((int64_t)n_img * hs * ws * Cin1 * 2 >= (1ll << 31) || (int64_t)n_img * hs * ws * (Cin - Cin1) * 2 >= (1ll << 31)) return 0;
     if ((int64_t)Cout * 9 * Cin * 2 >= (1ll << 31)) return 0;
     return 1;
+}
+
+extern "C" int fmc_conv3x3_halo_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x) {
+    return halo_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, false);
+}
+
+extern "C" int fmc_conv3x3_halo_partial_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x) {
+    return halo_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, true);
 }
 
 extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
@@ -764,6 +789,81 @@ extern "C" int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, c
 }
 
 extern "C" int fmc_conv3x3_halo_tiles_per_image(int H, int W) { return ((H + TH - 1) / TH) * (W / TW); }
+
+// ---- images of any width (PARTIAL, see conv_halo_kernel): the entry points above without the width rule, tiles_x = ceil(W / 32).  Same packed
+// filters; a whole-tile shape gives the bits of the entry point above ----------------------------------------------------------------------------------
+extern "C" int fmc_conv3x3_halo_partial_tiles_per_image(int H, int W) { return ((H + TH - 1) / TH) * ((W + TW - 1) / TW); }
+
+extern "C" int fmc_conv3x3_halo_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                             const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                             int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
+    if (!x2) Cin1 = Cin;
+    if (int e = halo::check_args("conv3x3_halo_partial", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_partial_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x),
+                                 "%s: needs Cin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
+        return e;
+    CHParams P;
+    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
+    P.gn_coef = gn_coef; P.gn_act = gn_act;
+    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = (W + TW - 1) / TW; P.tiles_n = Cout / BN;
+    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
+    if (!gn_coef) fmc_launch<conv_halo_kernel<0, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    else if (gn_act) fmc_launch<conv_halo_kernel<1, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    else fmc_launch<conv_halo_kernel<2, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_partial_bf16");
+    return 0;
+}
+
+extern "C" int fmc_conv3x3_halo_sc_partial_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
+    if (!fmc_conv3x3_halo_partial_supported(n_img, H, W, Cin, Cin, Cout, 0)) return 0;
+    return halo::sc_sources_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1);
+}
+
+extern "C" int fmc_conv3x3_halo_sc_partial_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
+                                                const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout,
+                                                int64_t temb_row_stride, int temb_img_div, float* gn_partials, void* stream) {
+    if (!xs2) Cin_sc1 = Cin_sc;
+    if (int e = halo::check_args("conv3x3_halo_sc_partial", true, x, nullptr, w_packed, bias, temb, nullptr, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_sc_partial_supported(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1),
+                                 "%s: needs Cin %% 64 == 0, shortcut channels %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d Cout=%d shortcut=%d+%d)", n_img, H, W, Cin, Cout, Cin_sc1, Cin_sc - Cin_sc1))
+        return e;
+    if (int e = halo::check_sc_args("conv3x3_halo_sc_partial", xs, xs2)) return e;
+    CHParamsSC P;
+    halo::fill_params(P, x, nullptr, Cin, w_packed, bias, temb, nullptr, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, 0, gn_partials, 9);
+    halo::fill_params_sc(P, xs, xs2, Cin_sc1, Cin_sc);
+    P.gn_coef = nullptr; P.gn_act = 0;
+    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = (W + TW - 1) / TW; P.tiles_n = Cout / BN;
+    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
+    fmc_launch<conv_halo_kernel<0, false, true, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_sc_partial_bf16");
+    return 0;
+}
+
+extern "C" int fmc_conv3x3_halo_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout) {
+    if (!fmc_conv3x3_halo_partial_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0)) return 0;
+    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
+    return 1;
+}
+
+extern "C" int fmc_conv3x3_halo_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                                  int Cout, float* gn_partials, void* stream) {
+    if (int e = halo::check_args("conv3x3_halo_fold_partial", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo_fold_partial_supported(n_img, Hs, Ws, Cin, Cout),
+                                 "%s: needs Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
+                                 n_img, Hs, Ws, Cin, Cout))
+        return e;
+    CHParams P;
+    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
+    P.gn_coef = nullptr; P.gn_act = 0;
+    P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = (Ws + TW - 1) / TW; P.tiles_n = 4 * (Cout / BN);
+    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
+    fmc_launch<conv_halo_kernel<0, true, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_partial_bf16");
+    return 0;
+}
 
 extern "C" int fmc_groupnorm_coef(const float* partials, int part_splits, const float* gamma, const float* beta, float* coef, float* stats,
                                   int N, int HW, int C, int G, float eps, void* stream) {

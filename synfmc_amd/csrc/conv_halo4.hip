@@ -16,6 +16,11 @@
 // LDS: halo double buffer 2 x 8 x NP x 16 B + W ring 5 x 5 KiB (TW = 16: 135,168 B; TW = 8: 163,840 - the ring shrinks to 4).
 // Roofline: MFMA bound.  Algorithmic flops per launch = 2 * n_img*H*W * Cout * 9*Cin.
 //
+// Image width: fmc_conv3x3_halo4_bf16 / _fold_bf16 take W % 8 == 0 and pick TW themselves; the *_partial_* entry points (`PARTIAL`, see
+// conv_halo4_kernel) take any W >= 1 at the TW the caller names (fmc_conv3x3_halo4_partial_tw: the default), tiles_x = ceil(W / TW), the last row block
+// of an image row partly filled -- 4 x 6 and 8 x 12 pixels per image at the 1280-channel levels of a 256x384 clip.  The whole-tile instantiations are the
+// instruction streams they were (profiles/partial_tiles.md section 15); what the partial launches cost per shape is in section 17.
+//
 // What this kernel shares with conv_halo_kernel -- the common parameters, halo piece addressing, the W stream, the filter pack kernels (compiled in
 // conv_halo.hip), the host-side checks -- is in conv_halo_common.h.
 #include "conv_halo_common.h"
@@ -67,7 +72,11 @@ template <int NPIECE, bool PH> constexpr int nh(int i) {
 // PH: the PHASE MODE of the nearest-2x upsample convolutions, as in conv_halo_kernel (conv_halo.hip): the tile is 320 SOURCE pixels, the channel-tile
 // index is (phase (py, px), channel tile), a chunk is 4 taps x 2 k-halves = 8 sub-tiles of the folded filter (fmc_conv3x3_upfold_pack_weight), and the
 // epilogue stores out[2 i + py, 2 j + px].  No split-K, temb or residual there.
-template <int TW, int NWV, bool PH = false>
+//
+// PARTIAL: images of ANY width.  tiles_x = ceil(W / TW): the last row block of an image row holds W - xb TW real columns.  As in conv_halo_kernel the
+// main loop needs nothing (a halo pixel with x >= W is staged as zeros already); the split-K partial store, the residual burst, the output stores and
+// the statistics sums ask whether their column exists, and every thread runs the same barriers and counted waits as in the whole-tile form.
+template <int TW, int NWV, bool PH = false, bool PARTIAL = false>
 __global__ __launch_bounds__(64 * NWV, NWV / 4)
 void conv_halo4_kernel(const C4Params P) {
     using G = Geo<TW, NWV>;
@@ -274,7 +283,9 @@ void conv_halo4_kernel(const C4Params P) {
             const int r = wp * 80 + mb * 16 + l15;
             const int blk = r / RB, q = r - blk * RB, ty = q / TW, tx = q - ty * TW;
             const int rb = rb0 + blk, img = rb / tpi, rin = rb - img * tpi, yb = rin / P.tiles_x, xb = rin - yb * P.tiles_x, y = yb * TH + ty;
-            if (rb < rb_total && y < P.H) {
+            bool ok = rb < rb_total && y < P.H;
+            if constexpr (PARTIAL) ok = ok && xb * TW + tx < P.W;
+            if (ok) {
                 float* dst = P.ws + ((int64_t)split * mtot + ((int64_t)img * P.H + y) * P.W + xb * TW + tx) * P.cout + n0 + wn * 80 + 4 * kq;
 #pragma unroll
                 for (int nb = 0; nb < 5; ++nb) *reinterpret_cast<f32x4*>(dst + nb * 16) = acc[mb][nb];
@@ -289,6 +300,7 @@ void conv_halo4_kernel(const C4Params P) {
         const int blk = r / RB, q = r - blk * RB, ty = q / TW, tx = q - ty * TW;
         const int rb = rb0 + blk, img = rb / tpi, rin = rb - img * tpi, yb = rin / P.tiles_x, xb = rin - yb * P.tiles_x, y = yb * TH + ty;
         ok = rb < rb_total && y < P.H;
+        if constexpr (PARTIAL) ok = ok && xb * TW + tx < P.W;
         if constexpr (PH) return ((int64_t)img * (2 * P.H) + 2 * y + py) * (2 * P.W) + 2 * (xb * TW + tx) + px_;      // pixel shuffle
         return ((int64_t)img * P.H + y) * P.W + xb * TW + tx;
     };
@@ -383,6 +395,7 @@ void conv_halo4_kernel(const C4Params P) {
             const int vr = min(TH, P.H - (sp / P.tiles_x) * TH) * TW;       // rows of this block inside the image
             float gs = 0.f, gss = 0.f;
             for (int r = tid / GT; r < vr; r += RP) {
+                if constexpr (PARTIAL) { if ((sp % P.tiles_x) * TW + r % TW >= P.W) continue; }
                 const unsigned* wsrc = reinterpret_cast<const unsigned*>(Os + (blk * RB + r) * OP + gl * cpg);
                 for (int k = 0; k < cpg / 2; ++k) {
                     const unsigned u = wsrc[k];
@@ -447,10 +460,10 @@ __global__ __launch_bounds__(256) void conv_halo4_finish_kernel(const C4Params P
     }
 }
 
-template <int TW, int NWV, bool PH = false> int launch_c4(C4Params& P, hipStream_t st) {
+template <int TW, int NWV, bool PH = false, bool PARTIAL = false> int launch_c4(C4Params& P, hipStream_t st) {
     using G = Geo<TW, NWV>;
     P.tiles_y = (P.H + G::TH - 1) / G::TH;
-    P.tiles_x = P.W / TW;
+    P.tiles_x = PARTIAL ? (P.W + TW - 1) / TW : P.W / TW;
     P.tiles_p = (P.n_img * P.tiles_y * P.tiles_x + G::NB - 1) / G::NB;
     {   // XCD grid (see the kernel): FMC_C4_XCD = 0 contiguous ranges (rounds 5's order), 1 / 2 / 4 / 8 forced where it divides, unset = least fabric traffic
         static const int forced = fmc_env_int("FMC_C4_XCD", -1);
@@ -465,7 +478,7 @@ template <int TW, int NWV, bool PH = false> int launch_c4(C4Params& P, hipStream
             }
         }
     }
-    fmc_launch<conv_halo4_kernel<TW, NWV, PH>>(dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
+    fmc_launch<conv_halo4_kernel<TW, NWV, PH, PARTIAL>>(dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
     if (P.splits > 1) {
         const int64_t chunks = (int64_t)P.n_img * P.H * P.W * (P.cout / 8);
         const unsigned grid = (unsigned)((chunks + 255) / 256 < 2048 ? (chunks + 255) / 256 : 2048);
@@ -489,14 +502,20 @@ extern "C" int fmc_conv3x3_halo4_pack_weight(const void* w, void* dst, int Cin, 
 
 // row blocks are 10 x 16 pixels where W % 16 == 0, else 5 x 8 (W % 8 == 0); any H
 static int c4_tw(int W) { return W % 16 == 0 ? 16 : 8; }
-extern "C" int fmc_conv3x3_halo4_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
-    if (n_img < 1 || H < 1 || W < 8 || W % 8 || Cin % 64 || Cout % (wide ? 160 : 80) || (wide && W % 16)) return 0;
+// (the conditions of the whole-tile and the PARTIAL entry points: the latter drop the width rule alone)
+static int c4_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide, bool any_width) {
+    if (n_img < 1 || H < 1 || W < 1 || Cin % 64 || Cout % (wide ? 160 : 80)) return 0;
+    if (!any_width && (W < 8 || W % 8 || (wide && W % 16))) return 0;
     if (Cin1 <= 0 || Cin1 > Cin || Cin1 % 64) return 0;
     if (upsample2x && ((H | W) & 1)) return 0;
     const int64_t hs = upsample2x ? H / 2 : H, ws = upsample2x ? W / 2 : W;
     if ((int64_t)n_img * hs * ws * Cin1 * 2 >= (1ll << 31) || (int64_t)n_img * hs * ws * (Cin - Cin1) * 2 >= (1ll << 31)) return 0;
     if ((int64_t)Cout * 9 * Cin * 2 >= (1ll << 31)) return 0;
     return 1;
+}
+
+extern "C" int fmc_conv3x3_halo4_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
+    return c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, false);
 }
 
 extern "C" int fmc_conv3x3_halo4_row_blocks_per_image(int H, int W) {
@@ -569,5 +588,92 @@ extern "C" int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, 
     else if (wide) launch_c4<16, 8, true>(P, st);
     else launch_c4<16, 4, true>(P, st);
     FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_fold_bf16");
+    return 0;
+}
+
+// ---- images of any width (PARTIAL, see conv_halo4_kernel): the entry points above without the width rule.  The caller names the row-block geometry:
+// tw = 16 (10 x 16-pixel row blocks; the only one of the wide form) or 8 (5 x 8); tiles_x = ceil(W / tw).  Same packed filters; a whole-tile shape at
+// the geometry the entry points above pick gives their bits -------------------------------------------------------------------------------------------
+extern "C" int fmc_conv3x3_halo4_partial_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
+    return c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, true);
+}
+
+static int64_t c4_padded_pixels(int H, int W, int tw) {
+    const int th = tw == 8 ? 5 : 10;
+    return (int64_t)((H + th - 1) / th) * th * ((W + tw - 1) / tw) * tw;
+}
+
+// the default geometry: that of the whole-tile entry points where W % 8 == 0, else the one with fewer pad pixels over the image (ties: 16)
+extern "C" int fmc_conv3x3_halo4_partial_tw(int H, int W, int wide) {
+    if (wide) return 16;
+    if (W % 8 == 0) return c4_tw(W);
+    return c4_padded_pixels(H, W, 8) < c4_padded_pixels(H, W, 16) ? 8 : 16;
+}
+
+extern "C" int fmc_conv3x3_halo4_partial_row_blocks_per_image(int H, int W, int tw) {
+    return (tw == 8 ? (H + 4) / 5 : (H + 9) / 10) * ((W + tw - 1) / tw);
+}
+
+extern "C" int fmc_conv3x3_halo4_partial_tiles(int n_img, int H, int W, int Cout, int wide, int tw) {
+    const int nb = tw == 8 ? 8 : 2;
+    return (n_img * fmc_conv3x3_halo4_partial_row_blocks_per_image(H, W, tw) + nb - 1) / nb * (Cout / (wide ? 160 : 80));
+}
+
+/* As fmc_conv3x3_halo4_bf16 for any W >= 1; gn_partials [n_img, fmc_conv3x3_halo4_partial_row_blocks_per_image(H, W, tw), 32, 2]. */
+extern "C" int fmc_conv3x3_halo4_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                              const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                              int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace,
+                                              int64_t workspace_bytes, int wide, int tw, void* stream) {
+    const int BN = wide ? 160 : 80;
+    if (!x2) Cin1 = Cin;
+    if (int e = halo::check_args("conv3x3_halo4_partial", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo4_partial_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide) && (tw == 16 || (tw == 8 && !wide)),
+                                 "%s: needs tw 16 or 8 (wide: 16), Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d tw=%d)", BN, n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x, tw))
+        return e;
+    if (split_k < 1) split_k = 1;
+    if (split_k > Cin / 64) split_k = Cin / 64;
+    if (split_k > 1) {
+        if (gn_partials) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_partial: the statistics epilogue is not available with split_k > 1");
+        if (!workspace || workspace_bytes < (int64_t)split_k * n_img * H * W * Cout * 4 || !fmc_aligned16(workspace))
+            FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_partial: split_k %d needs a 16-byte aligned workspace of %lld bytes", split_k,
+                     (long long)split_k * n_img * H * W * Cout * 4);
+    }
+    C4Params P;
+    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
+    P.tiles_n = Cout / BN;
+    P.splits = split_k; P.ws = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    if (tw == 8) launch_c4<8, 4, false, true>(P, st);
+    else if (wide) launch_c4<16, 8, false, true>(P, st);
+    else launch_c4<16, 4, false, true>(P, st);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_partial_bf16");
+    return 0;
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
+    if (!fmc_conv3x3_halo4_partial_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0, wide)) return 0;
+    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
+    return 1;
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                                   int Cout, float* gn_partials, int wide, int tw, void* stream) {
+    const int BN = wide ? 160 : 80;
+    if (int e = halo::check_args("conv3x3_halo4_fold_partial", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
+                                 fmc_conv3x3_halo4_fold_partial_supported(n_img, Hs, Ws, Cin, Cout, wide) && (tw == 16 || (tw == 8 && !wide)),
+                                 "%s: needs tw 16 or 8 (wide: 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
+                                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d tw=%d)", BN, n_img, Hs, Ws, Cin, Cout, tw))
+        return e;
+    C4Params P;
+    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
+    P.tiles_n = 4 * (Cout / BN);
+    P.splits = 1; P.ws = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (tw == 8) launch_c4<8, 4, true, true>(P, st);
+    else if (wide) launch_c4<16, 8, true, true>(P, st);
+    else launch_c4<16, 4, true, true>(P, st);
+    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_fold_partial_bf16");
     return 0;
 }

@@ -2139,6 +2139,42 @@ def conv3x3_halo_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: in
     return bool(_lib.load().fmc_conv3x3_halo_supported(n, h, w, cin, cin1, cout, int(upsample)))
 
 
+# ---- the halo convolutions at any image width: partly filled column tiles (include/fmc_hip.h: fmc_conv3x3_halo*_partial_*).  The wrappers take
+# `partial_tiles=True`; `conv3x3`, `conv3x3_upfold_arm` and `shortcut_fold_ok` ask for it only with `PARTIAL_TILES` on, and only where
+# `partial_conv_routed` says that the launch measured faster than the route the shape takes without (profiles/partial_tiles.md section 17;
+# tools/partial_conv_rates.py).  The kinds -- "halo4": a width that is no multiple of 8 (ring kernel / vendor arm today) on conv_halo4's row blocks;
+# "halo": a width that is no multiple of 32 on the 10 x 32 tiles (conv_halo4's whole row blocks today where W % 8 == 0);  "halo_sc": the shortcut fold
+# on them;  "upfold_halo" / "upfold_halo4": the phase mode of the upsample sites.  FMC_PARTIAL_CONV names the kinds that may be routed at all (A/B).
+PARTIAL_CONV_ROUTED = frozenset(k for k in os.environ.get("FMC_PARTIAL_CONV", "halo,halo_sc,halo4,upfold_halo4").split(",") if k)
+PARTIAL_CONV_RULES = True           # False: every shape of a routed kind goes to the partial launch (the measurement itself, tests)
+
+
+def partial_conv_routed(kind: str, n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    """The routing decisions of profiles/partial_tiles.md section 17 in closed form (h x w: the launch's own image -- the SOURCE of a fold).  Every
+    measured (shape, kind) pair that cleared "median below the parent route's by more than the legs' spread" at 16x256x384 is routed, none that did not is;
+    where one bound had to separate the two, marginal wins (3 - 8 %, 16x512x768) fall on the unrouted side."""
+    if kind not in PARTIAL_CONV_ROUTED:
+        return False
+    if not PARTIAL_CONV_RULES:
+        return True
+    macs = n * h * w * cin * cout                          # per filter tap
+    if kind in ("halo", "halo_sc"):
+        # 10 x 32 tiles: at least three quarters of the last column tile filled (W = 24, 48; W = 12 and 6 measured 0.26 - 0.92 of the parent route) ...
+        if 4 * w < 3 * 32 * ((w + 31) // 32):
+            return False
+        # ... and a launch small enough that the tile shape still matters: against conv_halo4's 10 x 16 row blocks (W % 16 == 0) and with the shortcut
+        # the gain is gone from 10e9 multiply-adds per tap on (1.00 - 1.03), against its 5 x 8 row blocks (W = 24) from 30e9 on
+        return macs <= (7e9 if kind == "halo_sc" or w % 16 == 0 else 21e9)
+    if kind == "halo4":
+        # against the ring kernel's arms: ahead (1.06 - 1.20) up to 1280 input channels and 2^21 input elements, level or behind (0.94 - 1.05) beyond
+        return cin <= 1280 and n * h * w * cin <= (1 << 21)
+    return True                                            # the folds: 1.42 - 1.71 on conv_halo4's row blocks at every source measured
+
+
+def conv3x3_halo_partial_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: int, upsample: bool) -> bool:
+    return bool(_lib.load().fmc_conv3x3_halo_partial_supported(n, h, w, cin, cin1, cout, int(upsample)))
+
+
 def _w_packed(weight_cl: torch.Tensor, key: str, factor: int, fn: str, *args) -> torch.Tensor:
     """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> a halo kernel's sub-tile order, cached on the weight per version under `key`:
     `factor` = 9 taps, or 16 for the folded filter of the phase mode; `fn(filter, packed, Cin, Cout, *args, stream)` is the C pack routine."""
@@ -2167,6 +2203,17 @@ def conv3x3_halo_sc_supported(n: int, h: int, w: int, cin: int, cout: int, cin_s
     return bool(_lib.load().fmc_conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cin_sc1))
 
 
+def conv3x3_halo_sc_partial_supported(n: int, h: int, w: int, cin: int, cout: int, cin_sc: int, cin_sc1: int) -> bool:
+    return bool(_lib.load().fmc_conv3x3_halo_sc_partial_supported(n, h, w, cin, cout, cin_sc, cin_sc1))
+
+
+def _shortcut_fold_partial(n: int, h: int, w: int, cin: int, cout: int, cin_sc: int, cs1: int) -> bool:
+    """The shortcut fold of a width the whole-tile kernel refuses goes to the partial launch (`PARTIAL_TILES` on, the kind routed, the tiles fill the chip)."""
+    return bool(PARTIAL_TILES and partial_conv_routed("halo_sc", n, h, w, cin, cout) and not conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
+                and conv3x3_halo_sc_partial_supported(n, h, w, cin, cout, cin_sc, cs1)
+                and n * _lib.load().fmc_conv3x3_halo_partial_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES)
+
+
 def _w_halo_sc_packed(weight_cl: torch.Tensor, w_sc: torch.Tensor, bn: int = 160) -> torch.Tensor:
     """The 3x3 filter and the 1x1 shortcut filter `[Cout, Cin_sc]` in one sub-tile order (`fmc_conv3x3_halo_sc_pack_weight`), cached on the 3x3
     weight per version of both.  The entry holds the shortcut weight, so an equal pointer is the same live storage."""
@@ -2193,8 +2240,10 @@ def shortcut_fold_ok(x_nchw: torch.Tensor, weight_cl: torch.Tensor, xs: torch.Te
         return False
     cs1 = xs.shape[1]
     cin_sc = cs1 + (xs2.shape[1] if xs2 is not None else 0)
-    return (conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
-            and n * _lib.load().fmc_conv3x3_halo_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES)
+    if (conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
+            and n * _lib.load().fmc_conv3x3_halo_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES):
+        return True
+    return _shortcut_fold_partial(n, h, w, cin, cout, cin_sc, cs1)
 
 
 def _gn_tagged(y, want: bool, cout: int):
@@ -2245,9 +2294,15 @@ def _w_halo4_packed(weight_cl: torch.Tensor, wide: bool = False) -> torch.Tensor
     return _w_packed(weight_cl, "halo4w" if wide else "halo4", 9, "fmc_conv3x3_halo4_pack_weight", int(wide))
 
 
-def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 256, wide: bool = False) -> int:
-    """Workgroups per tile: 1 where the tiles fill the chip, else the divisor of the chunk count that brings the launch closest to one round."""
-    tiles = _lib.load().fmc_conv3x3_halo4_tiles(n, h, w, cout, int(wide))
+def conv3x3_halo4_partial_supported(n: int, h: int, w: int, cin: int, cin1: int, cout: int, upsample: bool, wide: bool = False) -> bool:
+    return bool(_lib.load().fmc_conv3x3_halo4_partial_supported(n, h, w, cin, cin1, cout, int(upsample), int(wide)))
+
+
+def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 256, wide: bool = False, tw: Optional[int] = None) -> int:
+    """Workgroups per tile: 1 where the tiles fill the chip, else the divisor of the chunk count that brings the launch closest to one round.
+    `tw`: the row-block geometry of a partial-tile launch (the tile count is then that launch's)."""
+    L = _lib.load()
+    tiles = L.fmc_conv3x3_halo4_tiles(n, h, w, cout, int(wide)) if tw is None else L.fmc_conv3x3_halo4_partial_tiles(n, h, w, cout, int(wide), int(tw))
     if tiles >= (3 * cus) // 4:
         return 1
     nchunk = cin // 64
@@ -2259,14 +2314,33 @@ def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 
 
 
 def conv3x3_halo4(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=None, residual_nhwc=None, temb_div: int = 1, upsample: bool = False,
-                  x2_nhwc: Optional[torch.Tensor] = None, emit_gn: bool = False, split_k: Optional[int] = None, wide: bool = False):
+                  x2_nhwc: Optional[torch.Tensor] = None, emit_gn: bool = False, split_k: Optional[int] = None, wide: bool = False,
+                  partial_tiles: bool = False, tw: Optional[int] = None):
     """`conv3x3` on the small feature maps (images 8 / 16 / 32 pixels wide; csrc/conv_halo4.hip): arguments and results as `conv3x3_halo` without the
-    GroupNorm operand path; the statistics partials are per (image, row block of 5 / 10 rows)."""
+    GroupNorm operand path; the statistics partials are per (image, row block of 5 / 10 rows).
+    `partial_tiles`: any width >= 1, on row blocks `tw` = 16 or 8 pixels wide (None: `fmc_conv3x3_halo4_partial_tw`) with a partly filled last block
+    per image row; the partials are per (image, row block) of that geometry."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc)
     n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     L = _lib.load()
     wp = _w_halo4_packed(weight_cl, wide)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
+    if partial_tiles:
+        tw = int(L.fmc_conv3x3_halo4_partial_tw(h, w, int(wide))) if tw is None else int(tw)
+        if split_k is None:
+            split_k = 1 if emit_gn else conv3x3_halo4_split(n, h, w, cin, cout, wide=wide, tw=tw)
+        ws, ws_bytes = (None, 0) if split_k <= 1 else _splitk_workspace(x_nhwc.device, split_k, n * h * w, cout)
+        part = (torch.empty(n, L.fmc_conv3x3_halo4_partial_row_blocks_per_image(h, w, tw), 32, 2, dtype=torch.float32, device=x_nhwc.device)
+                if emit_gn else None)
+        conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
+        if call_log is not None:
+            call_log.append(("conv_halo4", (n, h, w, cin, cout, bool(upsample), ("partial", tw)), 2.0 * n * h * w * cout * 9 * cin))
+        _lib.check(L.fmc_conv3x3_halo4_partial_bf16(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc),
+                                                    out.data_ptr(), n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div),
+                                                    int(upsample), _p(part), int(split_k), ws, ws_bytes, int(wide), tw, _stream()),
+                   "fmc_conv3x3_halo4_partial_bf16")
+        return (out, part) if emit_gn else out
+    assert tw is None, "conv3x3_halo4: the whole-tile launch picks its own row blocks"
     if split_k is None:
         split_k = 1 if emit_gn else conv3x3_halo4_split(n, h, w, cin, cout, wide=wide)
     ws, ws_bytes = (None, 0) if split_k <= 1 else _splitk_workspace(x_nhwc.device, split_k, n * h * w, cout)
@@ -2297,17 +2371,20 @@ def groupnorm_partials(x: torch.Tensor, groups: int, x2: Optional[torch.Tensor] 
 
 def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=None, residual_nhwc=None, temb_div: int = 1, upsample: bool = False,
                  x2_nhwc: Optional[torch.Tensor] = None, gn_coef: Optional[torch.Tensor] = None, gn_act: bool = True, emit_gn: bool = False,
-                 shortcut=None):
+                 shortcut=None, partial_tiles: bool = False):
     """`conv3x3(act(x * scale + shift))` on channels-last bf16 images: x `[N, Hs, Ws, C1]` (+ `x2 [N, Hs, Ws, C2]`: channel concat read in place),
     filter `[Cout, C1 + C2, 3, 3]` channels-last, `gn_coef [N, C1 + C2, 2]` fp32 or None (plain convolution).  Returns out `[N, H, W, Cout]`, or
     `(out, partials [N, tiles, 32, 2])` with `emit_gn` (statistics of the output for the GroupNorm that consumes it).
     `shortcut = (xs [N, H, W, Cs1], xs2 [N, H, W, Cs2] | None, w_sc [Cout, Cs1 + Cs2], b_sc [Cout] | None)`: `+ w_sc . [xs | xs2] + b_sc` in the same
-    reduction (plain convolution of one source without temb / residual / upsample only)."""
+    reduction (plain convolution of one source without temb / residual / upsample only).
+    `partial_tiles`: any width >= 1, ceil(W / 32) column tiles per image row with a partly filled last one (the `*_partial_*` entry points)."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc, gn_coef)
     n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     assert gn_coef is None or (gn_coef.shape == (n, cin, 2) and gn_coef.dtype == torch.float32 and gn_coef.is_contiguous())
     L = _lib.load()
-    part = torch.empty(n, L.fmc_conv3x3_halo_tiles_per_image(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+    tiles_fn = L.fmc_conv3x3_halo_partial_tiles_per_image if partial_tiles else L.fmc_conv3x3_halo_tiles_per_image
+    mark = ("partial",) if partial_tiles else ()
+    part = torch.empty(n, tiles_fn(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
     if shortcut is not None:
         xs, xs2, w_sc, b_sc = shortcut
         _dev(xs, xs2, w_sc, b_sc)
@@ -2321,20 +2398,22 @@ def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=
         conv_halo_calls["conv"] += 1
         shortcut_fold_calls["folded"] += 1
         if call_log is not None:      # (a shape of its own: the longer launches do not enter the plain shapes' per-shape averages)
-            call_log.append(("conv_halo", (n, h, w, cin, cout, False, cin_sc), 2.0 * n * h * w * cout * (9 * cin + cin_sc)))
+            call_log.append(("conv_halo", (n, h, w, cin, cout, False, cin_sc) + mark, 2.0 * n * h * w * cout * (9 * cin + cin_sc)))
         # the shortcut bias rides as a one-row "temb" shared by all images: bias + temb are summed in fp32
-        _lib.check(L.fmc_conv3x3_halo_sc_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), _p(b_sc), out.data_ptr(), xs.data_ptr(), _p(xs2), cs1, cin_sc,
-                                              n, h, w, cin, cout, cout, n, _p(part), _stream()), "fmc_conv3x3_halo_sc_bf16")
+        fn = "fmc_conv3x3_halo_sc_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_sc_bf16"
+        _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), _p(b_sc), out.data_ptr(), xs.data_ptr(), _p(xs2), cs1, cin_sc,
+                                  n, h, w, cin, cout, cout, n, _p(part), _stream()), fn)
         return (out, part) if emit_gn else out
     wp = _w_halo_packed(weight_cl)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
     conv_halo_calls["conv"] += 1
     conv_halo_calls["gn_fused"] += gn_coef is not None
     if call_log is not None:
-        call_log.append(("conv_halo", (n, h, w, cin, cout, bool(upsample)), 2.0 * n * h * w * cout * 9 * cin))
-    _lib.check(L.fmc_conv3x3_halo_bf16(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(),
-                                       n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(gn_coef),
-                                       int(gn_act), _p(part), _stream()), "fmc_conv3x3_halo_bf16")
+        call_log.append(("conv_halo", (n, h, w, cin, cout, bool(upsample)) + mark, 2.0 * n * h * w * cout * 9 * cin))
+    fn = "fmc_conv3x3_halo_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_bf16"
+    _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(),
+                              n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(gn_coef),
+                              int(gn_act), _p(part), _stream()), fn)
     return (out, part) if emit_gn else out
 
 
@@ -2380,7 +2459,23 @@ def conv3x3_upfold_reference(x_nchw: torch.Tensor, wf: torch.Tensor, bias: Optio
 
 def conv3x3_upfold_arm(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[str]:
     """Which phase-mode launch takes the upsample convolution of `n` source images `hs x ws`: "halo" (10 x 32 source tiles, csrc/conv_halo.hip),
-    "halo4" / "halo4w" (320 source pixels of whole row blocks, csrc/conv_halo4.hip), or None (the 9-tap path keeps the shape)."""
+    "halo4" / "halo4w" (320 source pixels of whole row blocks, csrc/conv_halo4.hip), or None (the 9-tap path keeps the shape).  With `PARTIAL_TILES`
+    on, a source width none of them takes can go to "halo_partial" / "halo4_partial", the same launches with a partly filled last column tile, where
+    `partial_conv_routed` says so."""
+    arm = _upfold_arm_whole(n, hs, ws, cin, cout)
+    if arm is not None or not (PARTIAL_TILES and UPS_FOLD and CONV_HALO):
+        return arm
+    L = _lib.load()
+    if (partial_conv_routed("upfold_halo", n, hs, ws, cin, cout) and ws % 32 and L.fmc_conv3x3_halo_fold_partial_supported(n, hs, ws, cin, cout)
+            and n * L.fmc_conv3x3_halo_partial_tiles_per_image(hs, ws) * 4 * (cout // 160) >= CONV_HALO_MIN_TILES):
+        return "halo_partial"
+    if (CONV_HALO4 and partial_conv_routed("upfold_halo4", n, hs, ws, cin, cout) and ws % 8 and L.fmc_conv3x3_halo4_fold_partial_supported(n, hs, ws, cin, cout, 0)
+            and 4 * L.fmc_conv3x3_halo4_partial_tiles(n, hs, ws, cout, 0, L.fmc_conv3x3_halo4_partial_tw(hs, ws, 0)) >= CONV_HALO_MIN_TILES):
+        return "halo4_partial"
+    return None
+
+
+def _upfold_arm_whole(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[str]:
     if not (UPS_FOLD and CONV_HALO) or ws < UPS_FOLD_MIN_WS:
         return None
     L = _lib.load()
@@ -2402,10 +2497,12 @@ def _w_upfold_packed(weight_cl: torch.Tensor, tile_channels: int) -> torch.Tenso
     return _w_packed(weight_cl, "upfold%d" % tile_channels, 16, "fmc_conv3x3_upfold_pack_weight", tile_channels)
 
 
-def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emit_gn: bool = False, arm: Optional[str] = None):
+def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emit_gn: bool = False, arm: Optional[str] = None,
+                   partial_tiles: bool = False, tw: Optional[int] = None):
     """`conv3x3(nearest2x(x)) + bias` in phase mode: x `[N, Hs, Ws, Cin]` channels-last bf16, the RAW filter `[Cout, Cin, 3, 3]` channels-last (folded
     and packed once per weight version) -> out `[N, 2 Hs, 2 Ws, Cout]`, or `(out, partials [N, splits, 32, 2])` with `emit_gn`.  Inference only:
-    the fold is not the filter the weight gradient belongs to.  A shape no phase-mode launch takes is an error (ask `conv3x3_upfold_arm`)."""
+    the fold is not the filter the weight gradient belongs to.  A shape no phase-mode launch takes is an error (ask `conv3x3_upfold_arm`).
+    `partial_tiles` (or an arm "halo_partial" / "halo4_partial"): any source width, partly filled last column tile; `tw`: conv_halo4's row blocks."""
     _dev(x_nhwc, weight_cl, bias)
     n, hs, ws, cin = x_nhwc.shape
     cout = weight_cl.shape[0]
@@ -2413,23 +2510,37 @@ def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emi
     assert not (torch.is_grad_enabled() and (x_nhwc.requires_grad or weight_cl.requires_grad)), "conv3x3_upfold: inference only"
     if arm is None:
         arm = conv3x3_upfold_arm(n, hs, ws, cin, cout)
+    if arm in ("halo_partial", "halo4_partial", "halo4w_partial"):
+        arm, partial_tiles = arm[:-len("_partial")], True
     if arm not in ("halo", "halo4", "halo4w"):
         raise ValueError(f"conv3x3_upfold: no phase-mode launch for n={n} {hs}x{ws} {cin}->{cout} (arm {arm})")
     L = _lib.load()
+    mark = ("partial",) if partial_tiles else ()
     out = torch.empty(n, 2 * hs, 2 * ws, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
     shape, flops = (n, 2 * hs, 2 * ws, cin, cout, True), 2.0 * n * 4 * hs * ws * cout * 9 * cin      # (the algorithmic, 9-tap flops: useful-work rates)
     conv_halo_calls["upfold"] = conv_halo_calls.get("upfold", 0) + 1
     if arm == "halo":
         wp = _w_upfold_packed(weight_cl, 160)
-        part = torch.empty(n, 4 * L.fmc_conv3x3_halo_tiles_per_image(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+        tiles_fn = L.fmc_conv3x3_halo_partial_tiles_per_image if partial_tiles else L.fmc_conv3x3_halo_tiles_per_image
+        part = torch.empty(n, 4 * tiles_fn(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
         conv_halo_calls["conv"] += 1
         if call_log is not None:
-            call_log.append(("conv_halo", shape, flops))
-        _lib.check(L.fmc_conv3x3_halo_fold_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), _stream()),
-                   "fmc_conv3x3_halo_fold_bf16")
+            call_log.append(("conv_halo", shape + mark, flops))
+        fn = "fmc_conv3x3_halo_fold_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_fold_bf16"
+        _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), _stream()), fn)
     else:
         wide = arm == "halo4w"
         wp = _w_upfold_packed(weight_cl, 160 if wide else 80)
+        if partial_tiles:
+            tw = int(L.fmc_conv3x3_halo4_partial_tw(hs, ws, int(wide))) if tw is None else int(tw)
+            part = (torch.empty(n, 4 * L.fmc_conv3x3_halo4_partial_row_blocks_per_image(hs, ws, tw), 32, 2, dtype=torch.float32, device=x_nhwc.device)
+                    if emit_gn else None)
+            conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
+            if call_log is not None:
+                call_log.append(("conv_halo4", shape + (("partial", tw),), flops))
+            _lib.check(L.fmc_conv3x3_halo4_fold_partial_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part),
+                                                             int(wide), tw, _stream()), "fmc_conv3x3_halo4_fold_partial_bf16")
+            return (out, part) if emit_gn else out
         part = torch.empty(n, 4 * L.fmc_conv3x3_halo4_row_blocks_per_image(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
         conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
         if call_log is not None:
@@ -2916,8 +3027,10 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
             raise RuntimeError("conv3x3: no kernel takes this shape with the shortcut in the reduction")
         want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0)
         dispatch_calls["conv3x3"]["own"] += 1
+        cs1 = xs.shape[1]
         y = conv3x3_halo(x_nchw.permute(0, 2, 3, 1), weight_cl, bias, emit_gn=want,
-                         shortcut=(xs.permute(0, 2, 3, 1), None if xs2 is None else xs2.permute(0, 2, 3, 1), w_sc, b_sc))
+                         shortcut=(xs.permute(0, 2, 3, 1), None if xs2 is None else xs2.permute(0, 2, 3, 1), w_sc, b_sc),
+                         partial_tiles=_shortcut_fold_partial(n, h, w, cin, cout, cs1 + (xs2.shape[1] if xs2 is not None else 0), cs1))
         return _gn_tagged(y, want, cout)
 
     def lib():
@@ -2961,8 +3074,8 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
     if upsample and temb is None and r is None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16:
         arm = conv3x3_upfold_arm(n, h // 2, w // 2, cin, cout)
         if arm is not None:
-            bn = 80 if arm == "halo4" else 160
-            want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and bn % (cout // 32) == 0 and (arm == "halo" or h * w >= GN_MIN_HW))
+            bn = 80 if arm in ("halo4", "halo4_partial") else 160
+            want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and bn % (cout // 32) == 0 and (arm in ("halo", "halo_partial") or h * w >= GN_MIN_HW))
             dispatch_calls["conv3x3"]["own"] += 1
             y = conv3x3_upfold(x, weight_cl, bias, emit_gn=want, arm=arm)
             return _gn_tagged(y, want, cout)
@@ -2973,6 +3086,14 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
         want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0 and not torch.is_grad_enabled())
         dispatch_calls["conv3x3"]["own"] += 1
         y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
+        return _gn_tagged(y, want, cout)
+    # (`PARTIAL_TILES` on: a width that is no multiple of 32 on the same tiles with a partly filled last column tile, where that measured faster)
+    if (PARTIAL_TILES and partial_conv_routed("halo", n, h, w, cin, cout) and CONV_HALO and not stride2 and w % 32 and (temb is None or temb.stride(1) == 1)
+            and conv3x3_halo_partial_supported(n, h, w, cin, cin, cout, upsample)
+            and n * _lib.load().fmc_conv3x3_halo_partial_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES):
+        want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0 and not torch.is_grad_enabled())
+        dispatch_calls["conv3x3"]["own"] += 1
+        y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=True)
         return _gn_tagged(y, want, cout)
     # ... and its 4-wave form for the small feature maps (images 8 / 16 pixels wide: the two inner levels; csrc/conv_halo4.hip), split over the
     # reduction where the tiles alone would leave most of the chip idle (5x8-pixel images: 64 tiles)
@@ -2986,6 +3107,18 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
                     and conv3x3_halo4_split(n, h, w, cin, cout) == 1)
         y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
         return _gn_tagged(y, want, cout)
+    # (`PARTIAL_TILES` on: a width that is no multiple of 8 on the same row blocks with a partly filled last one per image row)
+    if (PARTIAL_TILES and partial_conv_routed("halo4", n, h, w, cin, cout) and CONV_HALO and CONV_HALO4 and not stride2 and w % 8 and (temb is None or temb.stride(1) == 1)
+            and conv3x3_halo4_partial_supported(n, h, w, cin, cin, cout, upsample)):
+        L = _lib.load()
+        tw = int(L.fmc_conv3x3_halo4_partial_tw(h, w, 0))
+        split = conv3x3_halo4_split(n, h, w, cin, cout, tw=tw)
+        if L.fmc_conv3x3_halo4_partial_tiles(n, h, w, cout, 0, tw) * split >= CONV_HALO_MIN_TILES:
+            dispatch_calls["conv3x3"]["own"] += 1
+            want = bool(emit_gn and GN_EPILOGUE and h * w >= GN_MIN_HW and cout % 64 == 0 and 80 % (cout // 32) == 0 and not torch.is_grad_enabled()
+                        and split == 1)
+            y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=True, tw=tw)
+            return _gn_tagged(y, want, cout)
     if emit_gn and gn_emit_ok(n * h * w, cout, 9 * cin, h * w, x.dtype):
         dispatch_calls["conv3x3"]["own"] += 1
         y, tag = conv3x3_gn(x, weight_cl, bias, temb, r, temb_div, upsample, stride2)
