@@ -656,7 +656,9 @@ extern "C" int fmc_conv3x3_halo_pack_weight(const void* w, void* dst, int Cin, i
     return 0;
 }
 
-// (the conditions of the whole-tile and the PARTIAL entry points: the latter drop the width rule alone)
+// ---- host side of the launches.  Every launch form (plain, shortcut, fold) is written once, for whole column tiles (W % 32 == 0) and, `partial`,
+// for images of any width: the entry points without the width rule, tiles_x = ceil(W / 32), the PARTIAL instantiation of conv_halo_kernel.  Same packed
+// filters; a whole-tile shape gives the same bits on either.  The exported pairs (fmc_hip.h) are calls of these ----------------------------------------
 static int halo_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, bool any_width) {
     if (n_img < 1 || H < 1 || W < 1 || (!any_width && W % TW) || Cin % 64 || Cout % BN) return 0;
     if (Cin1 <= 0 || Cin1 > Cin || Cin1 % 64) return 0;
@@ -667,6 +669,52 @@ static int halo_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, i
     return 1;
 }
 
+static int halo_sc_ok(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1, bool any_width) {
+    if (!halo_shape_ok(n_img, H, W, Cin, Cin, Cout, 0, any_width)) return 0;      // the convolution's own conditions
+    return halo::sc_sources_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1);
+}
+
+static int halo_fold_ok(int n_img, int Hs, int Ws, int Cin, int Cout, bool any_width) {
+    if (!halo_shape_ok(n_img, Hs, Ws, Cin, Cin, Cout, 0, any_width)) return 0;    // the source-resolution convolution's own conditions
+    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
+    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
+    return 1;
+}
+
+// (whole tiles at a ragged width: the floor -- what the whole-tile count has always answered for a shape its launch refuses)
+static int halo_tiles_x(int W, bool partial) { return partial ? (W + TW - 1) / TW : W / TW; }
+static int halo_tiles_per_image(int H, int W, bool partial) { return ((H + TH - 1) / TH) * halo_tiles_x(W, partial); }
+
+// the grid of a filled parameter block (`phases`: 4 in phase mode) and the choice between the whole-tile and the PARTIAL instantiation
+template <int GN, bool PH, bool SC, class P_> static void halo_launch(P_& P, int phases, bool partial, void* stream) {
+    P.tiles_y = (P.H + TH - 1) / TH; P.tiles_x = halo_tiles_x(P.W, partial); P.tiles_n = phases * (P.cout / BN);
+    const dim3 grid((unsigned)(P.n_img * P.tiles_y * P.tiles_x * P.tiles_n));
+    if (partial) fmc_launch<conv_halo_kernel<GN, PH, SC, true>>(grid, dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+    else fmc_launch<conv_halo_kernel<GN, PH, SC>>(grid, dim3(512), LDS_BYTES, (hipStream_t)stream, P);
+}
+
+static const char* halo_width_rule(bool partial, const char* rule) { return partial ? "" : rule; }      // (the one clause in which the pairs' messages differ)
+
+static int halo_plain(bool partial, const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb, const void* residual,
+                      void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x,
+                      const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
+    if (!x2) Cin1 = Cin;
+    if (int e = halo::check_args(partial ? "conv3x3_halo_partial" : "conv3x3_halo", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride,
+                                 temb_img_div, gn_partials, Cout, BN, halo_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, partial),
+                                 "%s: needs %sCin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", halo_width_rule(partial, "W % 32 == 0, "), n_img, H, W, Cin1, Cin - Cin1, Cout,
+                                 upsample2x))
+        return e;
+    CHParams P;
+    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
+    P.gn_coef = gn_coef; P.gn_act = gn_act;
+    if (!gn_coef) halo_launch<0, false, false>(P, 1, partial, stream);
+    else if (gn_act) halo_launch<1, false, false>(P, 1, partial, stream);
+    else halo_launch<2, false, false>(P, 1, partial, stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_conv3x3_halo_partial_bf16" : "fmc_conv3x3_halo_bf16");
+    return 0;
+}
+
 extern "C" int fmc_conv3x3_halo_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x) {
     return halo_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, false);
 }
@@ -675,25 +723,22 @@ extern "C" int fmc_conv3x3_halo_partial_supported(int n_img, int H, int W, int C
     return halo_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, true);
 }
 
+extern "C" int fmc_conv3x3_halo_tiles_per_image(int H, int W) { return halo_tiles_per_image(H, W, false); }
+
+extern "C" int fmc_conv3x3_halo_partial_tiles_per_image(int H, int W) { return halo_tiles_per_image(H, W, true); }
+
 extern "C" int fmc_conv3x3_halo_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
                                      const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
                                      int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
-    if (!x2) Cin1 = Cin;
-    if (int e = halo::check_args("conv3x3_halo", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x),
-                                 "%s: needs W %% 32 == 0, Cin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
-        return e;
-    CHParams P;
-    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
-    P.gn_coef = gn_coef; P.gn_act = gn_act;
-    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = W / TW; P.tiles_n = Cout / BN;
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    if (!gn_coef) fmc_launch<conv_halo_kernel<0>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else if (gn_act) fmc_launch<conv_halo_kernel<1>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else fmc_launch<conv_halo_kernel<2>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_bf16");
-    return 0;
+    return halo_plain(false, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_coef,
+                      gn_act, gn_partials, stream);
+}
+
+extern "C" int fmc_conv3x3_halo_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                             const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                             int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
+    return halo_plain(true, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_coef,
+                      gn_act, gn_partials, stream);
 }
 
 // ---- shortcut mode: a ResnetBlock2D's conv2 with the block's 1x1 shortcut in the same reduction (see conv_halo_kernel) ------------------------------
@@ -724,29 +769,44 @@ extern "C" int64_t fmc_conv3x3_halo_sc_pack_source(int64_t chunk, int Cin, int C
 }
 
 extern "C" int fmc_conv3x3_halo_sc_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
-    if (!fmc_conv3x3_halo_supported(n_img, H, W, Cin, Cin, Cout, 0)) return 0;      // the convolution's own conditions
-    return halo::sc_sources_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1);
+    return halo_sc_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1, false);
+}
+
+extern "C" int fmc_conv3x3_halo_sc_partial_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
+    return halo_sc_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1, true);
+}
+
+static int halo_sc(bool partial, const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs, const void* xs2,
+                   int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, float* gn_partials,
+                   void* stream) {
+    const char* name = partial ? "conv3x3_halo_sc_partial" : "conv3x3_halo_sc";
+    if (!xs2) Cin_sc1 = Cin_sc;
+    if (int e = halo::check_args(name, true, x, nullptr, w_packed, bias, temb, nullptr, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 halo_sc_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1, partial),
+                                 "%s: needs %sCin %% 64 == 0, shortcut channels %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d Cout=%d shortcut=%d+%d)", halo_width_rule(partial, "W % 32 == 0, "), n_img, H, W, Cin, Cout, Cin_sc1,
+                                 Cin_sc - Cin_sc1))
+        return e;
+    if (int e = halo::check_sc_args(name, xs, xs2)) return e;
+    CHParamsSC P;
+    halo::fill_params(P, x, nullptr, Cin, w_packed, bias, temb, nullptr, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, 0, gn_partials, 9);
+    halo::fill_params_sc(P, xs, xs2, Cin_sc1, Cin_sc);
+    P.gn_coef = nullptr; P.gn_act = 0;
+    halo_launch<0, false, true>(P, 1, partial, stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_conv3x3_halo_sc_partial_bf16" : "fmc_conv3x3_halo_sc_bf16");
+    return 0;
 }
 
 extern "C" int fmc_conv3x3_halo_sc_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
                                         const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout,
                                         int64_t temb_row_stride, int temb_img_div, float* gn_partials, void* stream) {
-    if (!xs2) Cin_sc1 = Cin_sc;
-    if (int e = halo::check_args("conv3x3_halo_sc", true, x, nullptr, w_packed, bias, temb, nullptr, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_sc_supported(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1),
-                                 "%s: needs W %% 32 == 0, Cin %% 64 == 0, shortcut channels %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d Cout=%d shortcut=%d+%d)", n_img, H, W, Cin, Cout, Cin_sc1, Cin_sc - Cin_sc1))
-        return e;
-    if (int e = halo::check_sc_args("conv3x3_halo_sc", xs, xs2)) return e;
-    CHParamsSC P;
-    halo::fill_params(P, x, nullptr, Cin, w_packed, bias, temb, nullptr, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, 0, gn_partials, 9);
-    halo::fill_params_sc(P, xs, xs2, Cin_sc1, Cin_sc);
-    P.gn_coef = nullptr; P.gn_act = 0;
-    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = W / TW; P.tiles_n = Cout / BN;
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    fmc_launch<conv_halo_kernel<0, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_sc_bf16");
-    return 0;
+    return halo_sc(false, x, w_packed, bias, temb, out, xs, xs2, Cin_sc1, Cin_sc, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, gn_partials, stream);
+}
+
+extern "C" int fmc_conv3x3_halo_sc_partial_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
+                                                const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout,
+                                                int64_t temb_row_stride, int temb_img_div, float* gn_partials, void* stream) {
+    return halo_sc(true, x, w_packed, bias, temb, out, xs, xs2, Cin_sc1, Cin_sc, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, gn_partials, stream);
 }
 
 // ---- phase mode of the nearest-2x upsample convolutions (see conv_halo_kernel) ------------------------------------------------------------------
@@ -764,105 +824,33 @@ extern "C" int fmc_conv3x3_upfold_pack_weight(const void* w, void* dst, int Cin,
     return 0;
 }
 
-extern "C" int fmc_conv3x3_halo_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout) {
-    if (!fmc_conv3x3_halo_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0)) return 0;      // the source-resolution convolution's own conditions
-    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
-    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
-    return 1;
+extern "C" int fmc_conv3x3_halo_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout) { return halo_fold_ok(n_img, Hs, Ws, Cin, Cout, false); }
+
+extern "C" int fmc_conv3x3_halo_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout) { return halo_fold_ok(n_img, Hs, Ws, Cin, Cout, true); }
+
+static int halo_fold(bool partial, const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
+                     float* gn_partials, void* stream) {
+    if (int e = halo::check_args(partial ? "conv3x3_halo_fold_partial" : "conv3x3_halo_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1,
+                                 gn_partials, Cout, BN, halo_fold_ok(n_img, Hs, Ws, Cin, Cout, partial),
+                                 "%s: needs %sCin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
+                                 halo_width_rule(partial, "Ws % 32 == 0, "), n_img, Hs, Ws, Cin, Cout))
+        return e;
+    CHParams P;
+    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
+    P.gn_coef = nullptr; P.gn_act = 0;
+    halo_launch<0, true, false>(P, 4, partial, stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_conv3x3_halo_fold_partial_bf16" : "fmc_conv3x3_halo_fold_bf16");
+    return 0;
 }
 
 extern "C" int fmc_conv3x3_halo_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
                                           int Cout, float* gn_partials, void* stream) {
-    if (int e = halo::check_args("conv3x3_halo_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_fold_supported(n_img, Hs, Ws, Cin, Cout),
-                                 "%s: needs Ws %% 32 == 0, Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
-                                 n_img, Hs, Ws, Cin, Cout))
-        return e;
-    CHParams P;
-    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
-    P.gn_coef = nullptr; P.gn_act = 0;
-    P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = Ws / TW; P.tiles_n = 4 * (Cout / BN);
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    fmc_launch<conv_halo_kernel<0, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_bf16");
-    return 0;
-}
-
-extern "C" int fmc_conv3x3_halo_tiles_per_image(int H, int W) { return ((H + TH - 1) / TH) * (W / TW); }
-
-// ---- images of any width (PARTIAL, see conv_halo_kernel): the entry points above without the width rule, tiles_x = ceil(W / 32).  Same packed
-// filters; a whole-tile shape gives the bits of the entry point above ----------------------------------------------------------------------------------
-extern "C" int fmc_conv3x3_halo_partial_tiles_per_image(int H, int W) { return ((H + TH - 1) / TH) * ((W + TW - 1) / TW); }
-
-extern "C" int fmc_conv3x3_halo_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
-                                             const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                                             int temb_img_div, int upsample2x, const float* gn_coef, int gn_act, float* gn_partials, void* stream) {
-    if (!x2) Cin1 = Cin;
-    if (int e = halo::check_args("conv3x3_halo_partial", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_partial_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x),
-                                 "%s: needs Cin %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
-        return e;
-    CHParams P;
-    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
-    P.gn_coef = gn_coef; P.gn_act = gn_act;
-    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = (W + TW - 1) / TW; P.tiles_n = Cout / BN;
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    if (!gn_coef) fmc_launch<conv_halo_kernel<0, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else if (gn_act) fmc_launch<conv_halo_kernel<1, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    else fmc_launch<conv_halo_kernel<2, false, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_partial_bf16");
-    return 0;
-}
-
-extern "C" int fmc_conv3x3_halo_sc_partial_supported(int n_img, int H, int W, int Cin, int Cout, int Cin_sc, int Cin_sc1) {
-    if (!fmc_conv3x3_halo_partial_supported(n_img, H, W, Cin, Cin, Cout, 0)) return 0;
-    return halo::sc_sources_ok(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1);
-}
-
-extern "C" int fmc_conv3x3_halo_sc_partial_bf16(const void* x, const void* w_packed, const void* bias, const void* temb, void* out, const void* xs,
-                                                const void* xs2, int Cin_sc1, int Cin_sc, int n_img, int H, int W, int Cin, int Cout,
-                                                int64_t temb_row_stride, int temb_img_div, float* gn_partials, void* stream) {
-    if (!xs2) Cin_sc1 = Cin_sc;
-    if (int e = halo::check_args("conv3x3_halo_sc_partial", true, x, nullptr, w_packed, bias, temb, nullptr, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_sc_partial_supported(n_img, H, W, Cin, Cout, Cin_sc, Cin_sc1),
-                                 "%s: needs Cin %% 64 == 0, shortcut channels %% 64 == 0 (both sources), Cout %% 160 == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d Cout=%d shortcut=%d+%d)", n_img, H, W, Cin, Cout, Cin_sc1, Cin_sc - Cin_sc1))
-        return e;
-    if (int e = halo::check_sc_args("conv3x3_halo_sc_partial", xs, xs2)) return e;
-    CHParamsSC P;
-    halo::fill_params(P, x, nullptr, Cin, w_packed, bias, temb, nullptr, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, 0, gn_partials, 9);
-    halo::fill_params_sc(P, xs, xs2, Cin_sc1, Cin_sc);
-    P.gn_coef = nullptr; P.gn_act = 0;
-    P.tiles_y = (H + TH - 1) / TH; P.tiles_x = (W + TW - 1) / TW; P.tiles_n = Cout / BN;
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    fmc_launch<conv_halo_kernel<0, false, true, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_sc_partial_bf16");
-    return 0;
-}
-
-extern "C" int fmc_conv3x3_halo_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout) {
-    if (!fmc_conv3x3_halo_partial_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0)) return 0;
-    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
-    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
-    return 1;
+    return halo_fold(false, x, w_folded, bias, out, n_img, Hs, Ws, Cin, Cout, gn_partials, stream);
 }
 
 extern "C" int fmc_conv3x3_halo_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
                                                   int Cout, float* gn_partials, void* stream) {
-    if (int e = halo::check_args("conv3x3_halo_fold_partial", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo_fold_partial_supported(n_img, Hs, Ws, Cin, Cout),
-                                 "%s: needs Cin %% 64 == 0, Cout %% 160 == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d)",
-                                 n_img, Hs, Ws, Cin, Cout))
-        return e;
-    CHParams P;
-    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
-    P.gn_coef = nullptr; P.gn_act = 0;
-    P.tiles_y = (Hs + TH - 1) / TH; P.tiles_x = (Ws + TW - 1) / TW; P.tiles_n = 4 * (Cout / BN);
-    const unsigned grid = (unsigned)(n_img * P.tiles_y * P.tiles_x * P.tiles_n);
-    fmc_launch<conv_halo_kernel<0, true, false, true>>(dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, P);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo_fold_partial_bf16");
-    return 0;
+    return halo_fold(true, x, w_folded, bias, out, n_img, Hs, Ws, Cin, Cout, gn_partials, stream);
 }
 
 extern "C" int fmc_groupnorm_coef(const float* partials, int part_splits, const float* gamma, const float* beta, float* coef, float* stats,

@@ -460,11 +460,22 @@ __global__ __launch_bounds__(256) void conv_halo4_finish_kernel(const C4Params P
     }
 }
 
-template <int TW, int NWV, bool PH = false, bool PARTIAL = false> int launch_c4(C4Params& P, hipStream_t st) {
+// ---- host side.  Row blocks are 10 x 16 or 5 x 8 pixels (`tw` = 16 / 8), 2 / 8 of them a tile.  Whole row blocks: W % tw == 0; `partial`: images of
+// any width, ceil(W / tw) row blocks per image row with a partly filled last one (PARTIAL of conv_halo4_kernel).  Written once for both ------------------
+constexpr int c4_th(int tw) { return tw == 8 ? 5 : 10; }
+constexpr int c4_nb(int tw) { return tw == 8 ? 8 : 2; }
+int c4_tiles_y(int H, int tw) { return (H + c4_th(tw) - 1) / c4_th(tw); }
+// (whole row blocks at a ragged width: the floor -- what the whole-tile counts have always answered for a shape their launch refuses)
+int c4_tiles_x(int W, int tw, bool partial) { return partial ? (W + tw - 1) / tw : W / tw; }
+int c4_row_blocks(int H, int W, int tw, bool partial) { return c4_tiles_y(H, tw) * c4_tiles_x(W, tw, partial); }
+int c4_pixel_tiles(int n_img, int H, int W, int tw, bool partial) { return (n_img * c4_row_blocks(H, W, tw, partial) + c4_nb(tw) - 1) / c4_nb(tw); }
+
+template <int TW, int NWV, bool PH> int launch_c4(C4Params& P, bool partial, hipStream_t st) {
     using G = Geo<TW, NWV>;
-    P.tiles_y = (P.H + G::TH - 1) / G::TH;
-    P.tiles_x = PARTIAL ? (P.W + TW - 1) / TW : P.W / TW;
-    P.tiles_p = (P.n_img * P.tiles_y * P.tiles_x + G::NB - 1) / G::NB;
+    static_assert(G::TH == c4_th(TW) && G::NB == c4_nb(TW), "the host's tile counts are the kernel's geometry");
+    P.tiles_y = c4_tiles_y(P.H, TW);
+    P.tiles_x = c4_tiles_x(P.W, TW, partial);
+    P.tiles_p = c4_pixel_tiles(P.n_img, P.H, P.W, TW, partial);
     {   // XCD grid (see the kernel): FMC_C4_XCD = 0 contiguous ranges (rounds 5's order), 1 / 2 / 4 / 8 forced where it divides, unset = least fabric traffic
         static const int forced = fmc_env_int("FMC_C4_XCD", -1);
         const int tnv = P.tiles_n * P.splits;
@@ -478,13 +489,22 @@ template <int TW, int NWV, bool PH = false, bool PARTIAL = false> int launch_c4(
             }
         }
     }
-    fmc_launch<conv_halo4_kernel<TW, NWV, PH, PARTIAL>>(dim3((unsigned)(P.tiles_p * P.tiles_n * P.splits)), dim3(G::NT), G::LDS_BYTES, st, P);
+    const dim3 grid((unsigned)(P.tiles_p * P.tiles_n * P.splits));
+    if (partial) fmc_launch<conv_halo4_kernel<TW, NWV, PH, true>>(grid, dim3(G::NT), G::LDS_BYTES, st, P);
+    else fmc_launch<conv_halo4_kernel<TW, NWV, PH>>(grid, dim3(G::NT), G::LDS_BYTES, st, P);
     if (P.splits > 1) {
         const int64_t chunks = (int64_t)P.n_img * P.H * P.W * (P.cout / 8);
         const unsigned grid = (unsigned)((chunks + 255) / 256 < 2048 ? (chunks + 255) / 256 : 2048);
         hipLaunchKernelGGL(conv_halo4_finish_kernel, dim3(grid), dim3(256), 0, st, P);
     }
     return 0;
+}
+
+// the one choice of the instantiation: 5 x 8 row blocks on 4 waves, 10 x 16 on 4 or (wide) 8
+template <bool PH> void c4_launch(C4Params& P, int tw, int wide, bool partial, void* stream) {
+    if (tw == 8) launch_c4<8, 4, PH>(P, partial, (hipStream_t)stream);
+    else if (wide) launch_c4<16, 8, PH>(P, partial, (hipStream_t)stream);
+    else launch_c4<16, 4, PH>(P, partial, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -500,9 +520,11 @@ extern "C" int fmc_conv3x3_halo4_pack_weight(const void* w, void* dst, int Cin, 
     return 0;
 }
 
-// row blocks are 10 x 16 pixels where W % 16 == 0, else 5 x 8 (W % 8 == 0); any H
+// the whole-tile entry points pick the row blocks themselves: 10 x 16 pixels where W % 16 == 0, else 5 x 8 (W % 8 == 0); any H.  The partial ones take
+// `tw` from the caller: 16 (the only one of the wide form) or 8
 static int c4_tw(int W) { return W % 16 == 0 ? 16 : 8; }
-// (the conditions of the whole-tile and the PARTIAL entry points: the latter drop the width rule alone)
+static bool c4_tw_ok(int tw, int wide) { return tw == 16 || (tw == 8 && !wide); }
+// (the conditions of the whole-tile and the partial entry points: the latter drop the width rule alone)
 static int c4_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide, bool any_width) {
     if (n_img < 1 || H < 1 || W < 1 || Cin % 64 || Cout % (wide ? 160 : 80)) return 0;
     if (!any_width && (W < 8 || W % 8 || (wide && W % 16))) return 0;
@@ -514,166 +536,130 @@ static int c4_shape_ok(int n_img, int H, int W, int Cin, int Cin1, int Cout, int
     return 1;
 }
 
-extern "C" int fmc_conv3x3_halo4_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
-    return c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, false);
-}
-
-extern "C" int fmc_conv3x3_halo4_row_blocks_per_image(int H, int W) {
-    const int tw = c4_tw(W);
-    return (tw == 8 ? (H + 4) / 5 : (H + 9) / 10) * (W / tw);
-}
-
-extern "C" int fmc_conv3x3_halo4_tiles(int n_img, int H, int W, int Cout, int wide) {
-    const int nb = c4_tw(W) == 8 ? 8 : 2;
-    return (n_img * fmc_conv3x3_halo4_row_blocks_per_image(H, W) + nb - 1) / nb * (Cout / (wide ? 160 : 80));
-}
-
-/* As fmc_conv3x3_halo_bf16 (fmc_hip.h) without the GroupNorm operand path, for images 8 / 16 / 32 pixels wide; gn_partials
- * [n_img, fmc_conv3x3_halo4_row_blocks_per_image(H, W), 32, 2]; w_packed = fmc_conv3x3_halo4_pack_weight.  split_k > 1: the 64-channel chunks of the
- * reduction are dealt to split_k workgroups per tile (5x8-pixel images: 64 tiles on 256 CUs otherwise), fp32 partials in `workspace`
- * (>= split_k * n_img * H * W * Cout * 4 bytes), summed in a fixed order by a second launch that runs the epilogue; no statistics epilogue then. */
-extern "C" int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
-                                      const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                                      int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes,
-                                      int wide, void* stream) {
-    const int BN = wide ? 160 : 80;
-    if (!x2) Cin1 = Cin;
-    if (int e = halo::check_args("conv3x3_halo4", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo4_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide),
-                                 "%s: needs W %% 8 == 0 (wide: %% 16), Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d)", BN, n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x))
-        return e;
-    if (split_k < 1) split_k = 1;
-    if (split_k > Cin / 64) split_k = Cin / 64;
-    if (split_k > 1) {
-        if (gn_partials) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: the statistics epilogue is not available with split_k > 1");
-        if (!workspace || workspace_bytes < (int64_t)split_k * n_img * H * W * Cout * 4 || !fmc_aligned16(workspace))
-            FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4: split_k %d needs a 16-byte aligned workspace of %lld bytes", split_k, (long long)split_k * n_img * H * W * Cout * 4);
-    }
-    C4Params P;
-    halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
-    P.tiles_n = Cout / BN;
-    P.splits = split_k; P.ws = (float*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    if (c4_tw(W) == 8) launch_c4<8, 4>(P, st);
-    else if (wide) launch_c4<16, 8>(P, st);
-    else launch_c4<16, 4>(P, st);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_bf16");
-    return 0;
-}
-
-// ---- phase mode of the nearest-2x upsample convolutions on the small feature maps (see conv_halo4_kernel).  Hs, Ws = SOURCE size; w_folded =
-// fmc_conv3x3_upfold_pack_weight(filter, tile_channels = 160 if wide else 80) ---------------------------------------------------------------------
-extern "C" int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
-    if (!fmc_conv3x3_halo4_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0, wide)) return 0;      // the source-resolution convolution's own conditions
+static int c4_fold_ok(int n_img, int Hs, int Ws, int Cin, int Cout, int wide, bool any_width) {
+    if (!c4_shape_ok(n_img, Hs, Ws, Cin, Cin, Cout, 0, wide, any_width)) return 0;      // the source-resolution convolution's own conditions
     if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
     if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
     return 1;
 }
 
-extern "C" int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
-                                           int Cout, float* gn_partials, int wide, void* stream) {
-    const int BN = wide ? 160 : 80;
-    if (int e = halo::check_args("conv3x3_halo4_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo4_fold_supported(n_img, Hs, Ws, Cin, Cout, wide),
-                                 "%s: needs Ws %% 8 == 0 (wide: %% 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
-                                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d)", BN, n_img, Hs, Ws, Cin, Cout))
-        return e;
-    C4Params P;
-    halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
-    P.tiles_n = 4 * (Cout / BN);
-    P.splits = 1; P.ws = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (c4_tw(Ws) == 8) launch_c4<8, 4, true>(P, st);
-    else if (wide) launch_c4<16, 8, true>(P, st);
-    else launch_c4<16, 4, true>(P, st);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_fold_bf16");
-    return 0;
+static int c4_tiles(int n_img, int H, int W, int Cout, int wide, int tw, bool partial) {
+    return c4_pixel_tiles(n_img, H, W, tw, partial) * (Cout / (wide ? 160 : 80));
 }
 
-// ---- images of any width (PARTIAL, see conv_halo4_kernel): the entry points above without the width rule.  The caller names the row-block geometry:
-// tw = 16 (10 x 16-pixel row blocks; the only one of the wide form) or 8 (5 x 8); tiles_x = ceil(W / tw).  Same packed filters; a whole-tile shape at
-// the geometry the entry points above pick gives their bits -------------------------------------------------------------------------------------------
+extern "C" int fmc_conv3x3_halo4_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
+    return c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, false);
+}
+
 extern "C" int fmc_conv3x3_halo4_partial_supported(int n_img, int H, int W, int Cin, int Cin1, int Cout, int upsample2x, int wide) {
     return c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, true);
 }
 
-static int64_t c4_padded_pixels(int H, int W, int tw) {
-    const int th = tw == 8 ? 5 : 10;
-    return (int64_t)((H + th - 1) / th) * th * ((W + tw - 1) / tw) * tw;
-}
+extern "C" int fmc_conv3x3_halo4_row_blocks_per_image(int H, int W) { return c4_row_blocks(H, W, c4_tw(W), false); }
 
-// the default geometry: that of the whole-tile entry points where W % 8 == 0, else the one with fewer pad pixels over the image (ties: 16)
+extern "C" int fmc_conv3x3_halo4_partial_row_blocks_per_image(int H, int W, int tw) { return c4_row_blocks(H, W, tw, true); }
+
+extern "C" int fmc_conv3x3_halo4_tiles(int n_img, int H, int W, int Cout, int wide) { return c4_tiles(n_img, H, W, Cout, wide, c4_tw(W), false); }
+
+extern "C" int fmc_conv3x3_halo4_partial_tiles(int n_img, int H, int W, int Cout, int wide, int tw) { return c4_tiles(n_img, H, W, Cout, wide, tw, true); }
+
+static int64_t c4_padded_pixels(int H, int W, int tw) { return (int64_t)c4_row_blocks(H, W, tw, true) * c4_th(tw) * tw; }
+
+// the default geometry of a partial launch: that of the whole-tile entry points where W % 8 == 0, else the one with fewer pad pixels over the image (ties: 16)
 extern "C" int fmc_conv3x3_halo4_partial_tw(int H, int W, int wide) {
     if (wide) return 16;
     if (W % 8 == 0) return c4_tw(W);
     return c4_padded_pixels(H, W, 8) < c4_padded_pixels(H, W, 16) ? 8 : 16;
 }
 
-extern "C" int fmc_conv3x3_halo4_partial_row_blocks_per_image(int H, int W, int tw) {
-    return (tw == 8 ? (H + 4) / 5 : (H + 9) / 10) * ((W + tw - 1) / tw);
-}
+// the width clause and the tail of the shape message, the two places in which the pairs' messages differ
+static const char* c4_width_rule(bool partial, const char* whole) { return partial ? "tw 16 or 8 (wide: 16)" : whole; }
+struct C4TwTail {
+    char s[24];
+    C4TwTail(bool partial, int tw) { s[0] = 0; if (partial) snprintf(s, sizeof s, " tw=%d", tw); }
+};
 
-extern "C" int fmc_conv3x3_halo4_partial_tiles(int n_img, int H, int W, int Cout, int wide, int tw) {
-    const int nb = tw == 8 ? 8 : 2;
-    return (n_img * fmc_conv3x3_halo4_partial_row_blocks_per_image(H, W, tw) + nb - 1) / nb * (Cout / (wide ? 160 : 80));
-}
-
-/* As fmc_conv3x3_halo4_bf16 for any W >= 1; gn_partials [n_img, fmc_conv3x3_halo4_partial_row_blocks_per_image(H, W, tw), 32, 2]. */
-extern "C" int fmc_conv3x3_halo4_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
-                                              const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                                              int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace,
-                                              int64_t workspace_bytes, int wide, int tw, void* stream) {
+/* fmc_conv3x3_halo4_bf16 and fmc_conv3x3_halo4_partial_bf16 (fmc_hip.h): as fmc_conv3x3_halo_bf16 without the GroupNorm operand path; gn_partials
+ * [n_img, row blocks per image, 32, 2]; w_packed = fmc_conv3x3_halo4_pack_weight.  split_k > 1: the 64-channel chunks of the reduction are dealt to
+ * split_k workgroups per tile (5x8-pixel images: 64 tiles on 256 CUs otherwise), fp32 partials in `workspace` (>= split_k * n_img * H * W * Cout * 4
+ * bytes), summed in a fixed order by a second launch that runs the epilogue; no statistics epilogue then. */
+static int c4_plain(bool partial, int tw, const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                    const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x,
+                    float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes, int wide, void* stream) {
+    const char* name = partial ? "conv3x3_halo4_partial" : "conv3x3_halo4";
     const int BN = wide ? 160 : 80;
     if (!x2) Cin1 = Cin;
-    if (int e = halo::check_args("conv3x3_halo4_partial", true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo4_partial_supported(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide) && (tw == 16 || (tw == 8 && !wide)),
-                                 "%s: needs tw 16 or 8 (wide: 16), Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
-                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d tw=%d)", BN, n_img, H, W, Cin1, Cin - Cin1, Cout, upsample2x, tw))
+    if (int e = halo::check_args(name, true, x, x2, w_packed, bias, temb, residual, out, temb_row_stride, temb_img_div, gn_partials, Cout, BN,
+                                 c4_shape_ok(n_img, H, W, Cin, Cin1, Cout, upsample2x, wide, partial) && c4_tw_ok(tw, wide),
+                                 "%s: needs %s, Cin %% 64 == 0 (both sources), Cout %% %d == 0, operands < 2 GiB "
+                                 "(n=%d H=%d W=%d Cin=%d+%d Cout=%d ups=%d%s)", c4_width_rule(partial, "W % 8 == 0 (wide: % 16)"), BN, n_img, H, W, Cin1,
+                                 Cin - Cin1, Cout, upsample2x, C4TwTail(partial, tw).s))
         return e;
     if (split_k < 1) split_k = 1;
     if (split_k > Cin / 64) split_k = Cin / 64;
     if (split_k > 1) {
-        if (gn_partials) FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_partial: the statistics epilogue is not available with split_k > 1");
+        if (gn_partials) FMC_FAIL(FMC_E_SHAPE, "%s: the statistics epilogue is not available with split_k > 1", name);
         if (!workspace || workspace_bytes < (int64_t)split_k * n_img * H * W * Cout * 4 || !fmc_aligned16(workspace))
-            FMC_FAIL(FMC_E_SHAPE, "conv3x3_halo4_partial: split_k %d needs a 16-byte aligned workspace of %lld bytes", split_k,
-                     (long long)split_k * n_img * H * W * Cout * 4);
+            FMC_FAIL(FMC_E_SHAPE, "%s: split_k %d needs a 16-byte aligned workspace of %lld bytes", name, split_k, (long long)split_k * n_img * H * W * Cout * 4);
     }
     C4Params P;
     halo::fill_params(P, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, gn_partials, 9);
     P.tiles_n = Cout / BN;
     P.splits = split_k; P.ws = (float*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    if (tw == 8) launch_c4<8, 4, false, true>(P, st);
-    else if (wide) launch_c4<16, 8, false, true>(P, st);
-    else launch_c4<16, 4, false, true>(P, st);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_partial_bf16");
+    c4_launch<false>(P, tw, wide, partial, stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_conv3x3_halo4_partial_bf16" : "fmc_conv3x3_halo4_bf16");
     return 0;
 }
 
-extern "C" int fmc_conv3x3_halo4_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
-    if (!fmc_conv3x3_halo4_partial_supported(n_img, Hs, Ws, Cin, Cin, Cout, 0, wide)) return 0;
-    if ((int64_t)Cout * 16 * Cin * 2 >= (1ll << 31)) return 0;
-    if ((int64_t)n_img * Hs * Ws * 4 >= (1ll << 31)) return 0;
-    return 1;
+extern "C" int fmc_conv3x3_halo4_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                      const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                      int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace, int64_t workspace_bytes,
+                                      int wide, void* stream) {
+    return c4_plain(false, c4_tw(W), x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x,
+                    gn_partials, split_k, workspace, workspace_bytes, wide, stream);
 }
 
-extern "C" int fmc_conv3x3_halo4_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
-                                                   int Cout, float* gn_partials, int wide, int tw, void* stream) {
+extern "C" int fmc_conv3x3_halo4_partial_bf16(const void* x, const void* x2, int Cin1, const void* w_packed, const void* bias, const void* temb,
+                                              const void* residual, void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
+                                              int temb_img_div, int upsample2x, float* gn_partials, int split_k, void* workspace,
+                                              int64_t workspace_bytes, int wide, int tw, void* stream) {
+    return c4_plain(true, tw, x, x2, Cin1, w_packed, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x,
+                    gn_partials, split_k, workspace, workspace_bytes, wide, stream);
+}
+
+// ---- phase mode of the nearest-2x upsample convolutions on the small feature maps (see conv_halo4_kernel).  Hs, Ws = SOURCE size; w_folded =
+// fmc_conv3x3_upfold_pack_weight(filter, tile_channels = 160 if wide else 80) ---------------------------------------------------------------------
+extern "C" int fmc_conv3x3_halo4_fold_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
+    return c4_fold_ok(n_img, Hs, Ws, Cin, Cout, wide, false);
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_partial_supported(int n_img, int Hs, int Ws, int Cin, int Cout, int wide) {
+    return c4_fold_ok(n_img, Hs, Ws, Cin, Cout, wide, true);
+}
+
+static int c4_fold(bool partial, int tw, const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin, int Cout,
+                   float* gn_partials, int wide, void* stream) {
     const int BN = wide ? 160 : 80;
-    if (int e = halo::check_args("conv3x3_halo4_fold_partial", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1, gn_partials, Cout, BN,
-                                 fmc_conv3x3_halo4_fold_partial_supported(n_img, Hs, Ws, Cin, Cout, wide) && (tw == 16 || (tw == 8 && !wide)),
-                                 "%s: needs tw 16 or 8 (wide: 16), Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB "
-                                 "(n=%d Hs=%d Ws=%d Cin=%d Cout=%d tw=%d)", BN, n_img, Hs, Ws, Cin, Cout, tw))
+    if (int e = halo::check_args(partial ? "conv3x3_halo4_fold_partial" : "conv3x3_halo4_fold", false, x, nullptr, w_folded, bias, nullptr, nullptr, out, 0, 1,
+                                 gn_partials, Cout, BN, c4_fold_ok(n_img, Hs, Ws, Cin, Cout, wide, partial) && c4_tw_ok(tw, wide),
+                                 "%s: needs %s, Cin %% 64 == 0, Cout %% %d == 0, operands < 2 GiB (n=%d Hs=%d Ws=%d Cin=%d Cout=%d%s)",
+                                 c4_width_rule(partial, "Ws % 8 == 0 (wide: % 16)"), BN, n_img, Hs, Ws, Cin, Cout, C4TwTail(partial, tw).s))
         return e;
     C4Params P;
     halo::fill_params(P, x, nullptr, Cin, w_folded, bias, nullptr, nullptr, out, n_img, Hs, Ws, Cin, Cout, 0, 1, 0, gn_partials, 16);
     P.tiles_n = 4 * (Cout / BN);
     P.splits = 1; P.ws = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (tw == 8) launch_c4<8, 4, true, true>(P, st);
-    else if (wide) launch_c4<16, 8, true, true>(P, st);
-    else launch_c4<16, 4, true, true>(P, st);
-    FMC_CHECK_LAUNCH("fmc_conv3x3_halo4_fold_partial_bf16");
+    c4_launch<true>(P, tw, wide, partial, stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_conv3x3_halo4_fold_partial_bf16" : "fmc_conv3x3_halo4_fold_bf16");
     return 0;
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                           int Cout, float* gn_partials, int wide, void* stream) {
+    return c4_fold(false, c4_tw(Ws), x, w_folded, bias, out, n_img, Hs, Ws, Cin, Cout, gn_partials, wide, stream);
+}
+
+extern "C" int fmc_conv3x3_halo4_fold_partial_bf16(const void* x, const void* w_folded, const void* bias, void* out, int n_img, int Hs, int Ws, int Cin,
+                                                   int Cout, float* gn_partials, int wide, int tw, void* stream) {
+    return c4_fold(true, tw, x, w_folded, bias, out, n_img, Hs, Ws, Cin, Cout, gn_partials, wide, stream);
 }

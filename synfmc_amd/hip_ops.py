@@ -13,7 +13,7 @@ import atexit
 import ctypes
 import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -2175,6 +2175,76 @@ def conv3x3_halo_partial_supported(n: int, h: int, w: int, cin: int, cin1: int, 
     return bool(_lib.load().fmc_conv3x3_halo_partial_supported(n, h, w, cin, cin1, cout, int(upsample)))
 
 
+class HaloRoute(NamedTuple):
+    """One halo launch.  `kernel`: "halo" (10 x 32-pixel tiles, csrc/conv_halo.hip), "halo4" / "halo4w" (row blocks on 4 / 8 waves, csrc/conv_halo4.hip);
+    `partial`: the `*_partial_*` entry points (a partly filled last column tile); `tw`: the row-block width of a partial conv_halo4 launch (a whole-tile
+    one picks its own: None); `split`: workgroups per tile over the reduction; `bn`: output channels per tile."""
+    kernel: str
+    partial: bool = False
+    tw: Optional[int] = None
+    split: int = 1
+    bn: int = 160
+
+    @property
+    def arm(self) -> str:                                   # what `conv3x3_upfold_arm` answers
+        return self.kernel + ("_partial" if self.partial else "")
+    @property
+    def mark(self) -> tuple:                                # behind the shape of a `call_log` entry: bench.py tells the partial launches' shapes by it
+        return () if not self.partial else (("partial",) if self.kernel == "halo" else (("partial", self.tw),))
+    @property
+    def tail(self) -> tuple:                                # the entry point's arguments between the operands and the stream
+        return () if self.kernel == "halo" else (int(self.kernel == "halo4w"),) + ((self.tw,) if self.partial else ())
+
+    def entry(self, form: str, what: str):                  # (name, function) in C: `form` "" (plain) / "_sc" / "_fold", `what` "supported" / "bf16"
+        name = "fmc_conv3x3_%s%s%s_%s" % ("halo" if self.kernel == "halo" else "halo4", form, "_partial" if self.partial else "", what)
+        return name, getattr(_lib.load(), name)
+
+
+def _halo4_tw(h: int, w: int, wide: bool, tw: Optional[int] = None) -> int:
+    """The row-block width of a partial conv_halo4 launch: the caller's, else the library's choice for the image (`fmc_conv3x3_halo4_partial_tw`)."""
+    return int(_lib.load().fmc_conv3x3_halo4_partial_tw(h, w, int(wide))) if tw is None else int(tw)
+
+
+def _halo_tiles(route: HaloRoute, n: int, h: int, w: int, cout: int, phases: int = 1):
+    """(workgroups before any split over the reduction, statistics slots per image) of a launch on `n` images `h x w` (the SOURCE of a fold, which
+    has `phases` = 4 channel-tile sets and slots per pixel tile): what is held against `CONV_HALO_MIN_TILES` and what sizes the partials."""
+    L = _lib.load()
+    if route.kernel == "halo":
+        per = (L.fmc_conv3x3_halo_partial_tiles_per_image if route.partial else L.fmc_conv3x3_halo_tiles_per_image)(h, w)
+        return n * per * phases * (cout // 160), phases * per
+    wide = int(route.kernel == "halo4w")
+    if route.partial:
+        return (phases * L.fmc_conv3x3_halo4_partial_tiles(n, h, w, cout, wide, int(route.tw)),
+                phases * L.fmc_conv3x3_halo4_partial_row_blocks_per_image(h, w, int(route.tw)))
+    return phases * L.fmc_conv3x3_halo4_tiles(n, h, w, cout, wide), phases * L.fmc_conv3x3_halo4_row_blocks_per_image(h, w)
+
+
+def _halo_route(n: int, h: int, w: int, cin: int, cout: int, upsample: bool) -> Optional[HaloRoute]:
+    """The halo launch of a plain stride-1 convolution with output `h x w`, or None.  In this order: the 10 x 32-pixel tiles (1.75 - 1.95 x the ring
+    kernels wherever they fill the chip; tools/scratch/r05/bench_halo.py), whole, then partial; conv_halo4's row blocks (the two inner levels), split over
+    the reduction where the tiles alone would leave most of the chip idle, whole, then partial (`PARTIAL_TILES`, a routed kind, a width the whole ones refuse)."""
+    for kernel, partial in (("halo", False), ("halo", True), ("halo4", False), ("halo4", True)) if CONV_HALO else ():
+        if (kernel == "halo4" and not CONV_HALO4) or (partial and not (PARTIAL_TILES and partial_conv_routed(kernel, n, h, w, cin, cout)
+                                                                      and w % (32 if kernel == "halo" else 8))):
+            continue
+        route = HaloRoute(kernel, partial, bn=160 if kernel == "halo" else 80)
+        if not route.entry("", "supported")[1](n, h, w, cin, cin, cout, int(upsample), *route.tail[:1]):
+            continue
+        if kernel == "halo4":
+            tw = _halo4_tw(h, w, False) if partial else None
+            route = route._replace(tw=tw, split=conv3x3_halo4_split(n, h, w, cin, cout, tw=tw))
+        if _halo_tiles(route, n, h, w, cout)[0] * route.split >= CONV_HALO_MIN_TILES:
+            return route
+    return None
+
+
+def _halo_emit_gn(route: HaloRoute, emit_gn: bool, h: int, w: int, cout: int) -> bool:
+    """A halo launch with output `h x w` leaves the statistics of the GroupNorm that consumes it: asked for, no gradient, whole groups of an even number of
+    channels per channel tile; conv_halo4 only where that norm would otherwise read its input twice (the large feature maps) and without a split."""
+    return bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and route.bn % (cout // 32) == 0 and not torch.is_grad_enabled()
+                and (route.kernel == "halo" or (h * w >= GN_MIN_HW and route.split == 1)))
+
+
 def _w_packed(weight_cl: torch.Tensor, key: str, factor: int, fn: str, *args) -> torch.Tensor:
     """Channels-last 3x3 filter (physically `[Cout][3][3][Cin]`) -> a halo kernel's sub-tile order, cached on the weight per version under `key`:
     `factor` = 9 taps, or 16 for the folded filter of the phase mode; `fn(filter, packed, Cin, Cout, *args, stream)` is the C pack routine."""
@@ -2207,11 +2277,16 @@ def conv3x3_halo_sc_partial_supported(n: int, h: int, w: int, cin: int, cout: in
     return bool(_lib.load().fmc_conv3x3_halo_sc_partial_supported(n, h, w, cin, cout, cin_sc, cin_sc1))
 
 
-def _shortcut_fold_partial(n: int, h: int, w: int, cin: int, cout: int, cin_sc: int, cs1: int) -> bool:
-    """The shortcut fold of a width the whole-tile kernel refuses goes to the partial launch (`PARTIAL_TILES` on, the kind routed, the tiles fill the chip)."""
-    return bool(PARTIAL_TILES and partial_conv_routed("halo_sc", n, h, w, cin, cout) and not conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
-                and conv3x3_halo_sc_partial_supported(n, h, w, cin, cout, cin_sc, cs1)
-                and n * _lib.load().fmc_conv3x3_halo_partial_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES)
+def _shortcut_route(n: int, h: int, w: int, cin: int, cout: int, cin_sc: int, cs1: int) -> Optional[HaloRoute]:
+    """The launch of conv2 with the shortcut (`cin_sc` channels, `cs1` in the first source) in its reduction, or None: where the plain convolution goes to
+    the 10 x 32-pixel tiles (the same conditions) and the sources fit them; with `PARTIAL_TILES` and the kind routed, a width the whole tiles refuse too."""
+    for partial in (False, True):
+        if partial and not (PARTIAL_TILES and partial_conv_routed("halo_sc", n, h, w, cin, cout) and w % 32):
+            continue
+        route = HaloRoute("halo", partial)
+        if route.entry("_sc", "supported")[1](n, h, w, cin, cout, cin_sc, cs1) and _halo_tiles(route, n, h, w, cout)[0] >= CONV_HALO_MIN_TILES:
+            return route
+    return None
 
 
 def _w_halo_sc_packed(weight_cl: torch.Tensor, w_sc: torch.Tensor, bn: int = 160) -> torch.Tensor:
@@ -2227,23 +2302,23 @@ def _w_halo_sc_packed(weight_cl: torch.Tensor, w_sc: torch.Tensor, bn: int = 160
     return derived_on_owner(weight_cl, "_fmc_wtm", ("halo_sc", bn, w_sc.data_ptr(), w_sc._version, w_sc.storage_offset(), tuple(w_sc.shape)), build)[0]
 
 
-def shortcut_fold_ok(x_nchw: torch.Tensor, weight_cl: torch.Tensor, xs: torch.Tensor, xs2: Optional[torch.Tensor]) -> bool:
-    """conv2 of a ResnetBlock2D takes the block's 1x1 shortcut into its reduction: inference on channels-last bf16 images where `conv3x3` routes
-    the convolution to the 10 x 32-pixel-tile kernel (the same conditions) and the shortcut sources fit it."""
+def _shortcut_fold_route(x_nchw: torch.Tensor, weight_cl: torch.Tensor, xs: torch.Tensor, xs2: Optional[torch.Tensor]) -> Optional[HaloRoute]:
+    """conv2 of a ResnetBlock2D takes the block's 1x1 shortcut into its reduction: inference on channels-last bf16 images of one size, on the launch
+    `_shortcut_route` names.  The one decision `shortcut_fold_ok` and the `shortcut=` branch of `conv3x3` share."""
     if not (SHORTCUT_FOLD and CONV_HALO and not torch.is_grad_enabled() and x_nchw.is_cuda and weight_cl.dtype == torch.bfloat16
             and all(t is None or (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()) for t in (x_nchw, xs, xs2))
             and weight_cl.is_contiguous(memory_format=torch.channels_last)):
-        return False
+        return None
     n, cin, h, w = x_nchw.shape
     cout = weight_cl.shape[0]
     if weight_cl.shape[1] != cin or xs.shape[0] != n or tuple(xs.shape[2:]) != (h, w) or (xs2 is not None and (xs2.shape[0] != n or tuple(xs2.shape[2:]) != (h, w))):
-        return False
+        return None
     cs1 = xs.shape[1]
-    cin_sc = cs1 + (xs2.shape[1] if xs2 is not None else 0)
-    if (conv3x3_halo_sc_supported(n, h, w, cin, cout, cin_sc, cs1)
-            and n * _lib.load().fmc_conv3x3_halo_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES):
-        return True
-    return _shortcut_fold_partial(n, h, w, cin, cout, cin_sc, cs1)
+    return _shortcut_route(n, h, w, cin, cout, cs1 + (xs2.shape[1] if xs2 is not None else 0), cs1)
+
+
+def shortcut_fold_ok(x_nchw: torch.Tensor, weight_cl: torch.Tensor, xs: torch.Tensor, xs2: Optional[torch.Tensor]) -> bool:
+    return _shortcut_fold_route(x_nchw, weight_cl, xs, xs2) is not None
 
 
 def _gn_tagged(y, want: bool, cout: int):
@@ -2301,8 +2376,7 @@ def conv3x3_halo4_partial_supported(n: int, h: int, w: int, cin: int, cin1: int,
 def conv3x3_halo4_split(n: int, h: int, w: int, cin: int, cout: int, cus: int = 256, wide: bool = False, tw: Optional[int] = None) -> int:
     """Workgroups per tile: 1 where the tiles fill the chip, else the divisor of the chunk count that brings the launch closest to one round.
     `tw`: the row-block geometry of a partial-tile launch (the tile count is then that launch's)."""
-    L = _lib.load()
-    tiles = L.fmc_conv3x3_halo4_tiles(n, h, w, cout, int(wide)) if tw is None else L.fmc_conv3x3_halo4_partial_tiles(n, h, w, cout, int(wide), int(tw))
+    tiles = _halo_tiles(HaloRoute("halo4w" if wide else "halo4", tw is not None, tw), n, h, w, cout)[0]
     if tiles >= (3 * cus) // 4:
         return 1
     nchunk = cin // 64
@@ -2322,35 +2396,21 @@ def conv3x3_halo4(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb
     per image row; the partials are per (image, row block) of that geometry."""
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc)
     n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
-    L = _lib.load()
+    assert partial_tiles or tw is None, "conv3x3_halo4: the whole-tile launch picks its own row blocks"
+    tw = _halo4_tw(h, w, wide, tw) if partial_tiles else None
+    route = HaloRoute("halo4w" if wide else "halo4", bool(partial_tiles), tw)
     wp = _w_halo4_packed(weight_cl, wide)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
-    if partial_tiles:
-        tw = int(L.fmc_conv3x3_halo4_partial_tw(h, w, int(wide))) if tw is None else int(tw)
-        if split_k is None:
-            split_k = 1 if emit_gn else conv3x3_halo4_split(n, h, w, cin, cout, wide=wide, tw=tw)
-        ws, ws_bytes = (None, 0) if split_k <= 1 else _splitk_workspace(x_nhwc.device, split_k, n * h * w, cout)
-        part = (torch.empty(n, L.fmc_conv3x3_halo4_partial_row_blocks_per_image(h, w, tw), 32, 2, dtype=torch.float32, device=x_nhwc.device)
-                if emit_gn else None)
-        conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
-        if call_log is not None:
-            call_log.append(("conv_halo4", (n, h, w, cin, cout, bool(upsample), ("partial", tw)), 2.0 * n * h * w * cout * 9 * cin))
-        _lib.check(L.fmc_conv3x3_halo4_partial_bf16(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc),
-                                                    out.data_ptr(), n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div),
-                                                    int(upsample), _p(part), int(split_k), ws, ws_bytes, int(wide), tw, _stream()),
-                   "fmc_conv3x3_halo4_partial_bf16")
-        return (out, part) if emit_gn else out
-    assert tw is None, "conv3x3_halo4: the whole-tile launch picks its own row blocks"
     if split_k is None:
-        split_k = 1 if emit_gn else conv3x3_halo4_split(n, h, w, cin, cout, wide=wide)
+        split_k = 1 if emit_gn else conv3x3_halo4_split(n, h, w, cin, cout, wide=wide, tw=tw)
     ws, ws_bytes = (None, 0) if split_k <= 1 else _splitk_workspace(x_nhwc.device, split_k, n * h * w, cout)
-    part = torch.empty(n, L.fmc_conv3x3_halo4_row_blocks_per_image(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+    part = torch.empty(n, _halo_tiles(route, n, h, w, cout)[1], 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
     conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
     if call_log is not None:
-        call_log.append(("conv_halo4", (n, h, w, cin, cout, bool(upsample)), 2.0 * n * h * w * cout * 9 * cin))
-    _lib.check(L.fmc_conv3x3_halo4_bf16(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(),
-                                        n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(part), int(split_k),
-                                        ws, ws_bytes, int(wide), _stream()), "fmc_conv3x3_halo4_bf16")
+        call_log.append(("conv_halo4", (n, h, w, cin, cout, bool(upsample)) + route.mark, 2.0 * n * h * w * cout * 9 * cin))
+    name, fn = route.entry("", "bf16")
+    _lib.check(fn(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(), n, h, w, cin, cout,
+                  0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(part), int(split_k), ws, ws_bytes, *route.tail, _stream()), name)
     return (out, part) if emit_gn else out
 
 
@@ -2381,10 +2441,8 @@ def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=
     _dev(x_nhwc, weight_cl, bias, temb, residual_nhwc, x2_nhwc, gn_coef)
     n, h, w, c1, cin, cout = _halo_args(x_nhwc, weight_cl, temb, residual_nhwc, temb_div, upsample, x2_nhwc)
     assert gn_coef is None or (gn_coef.shape == (n, cin, 2) and gn_coef.dtype == torch.float32 and gn_coef.is_contiguous())
-    L = _lib.load()
-    tiles_fn = L.fmc_conv3x3_halo_partial_tiles_per_image if partial_tiles else L.fmc_conv3x3_halo_tiles_per_image
-    mark = ("partial",) if partial_tiles else ()
-    part = torch.empty(n, tiles_fn(h, w), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+    route = HaloRoute("halo", bool(partial_tiles))
+    part = torch.empty(n, _halo_tiles(route, n, h, w, cout)[1], 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
     if shortcut is not None:
         xs, xs2, w_sc, b_sc = shortcut
         _dev(xs, xs2, w_sc, b_sc)
@@ -2398,22 +2456,22 @@ def conv3x3_halo(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, temb=
         conv_halo_calls["conv"] += 1
         shortcut_fold_calls["folded"] += 1
         if call_log is not None:      # (a shape of its own: the longer launches do not enter the plain shapes' per-shape averages)
-            call_log.append(("conv_halo", (n, h, w, cin, cout, False, cin_sc) + mark, 2.0 * n * h * w * cout * (9 * cin + cin_sc)))
+            call_log.append(("conv_halo", (n, h, w, cin, cout, False, cin_sc) + route.mark, 2.0 * n * h * w * cout * (9 * cin + cin_sc)))
         # the shortcut bias rides as a one-row "temb" shared by all images: bias + temb are summed in fp32
-        fn = "fmc_conv3x3_halo_sc_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_sc_bf16"
-        _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), _p(b_sc), out.data_ptr(), xs.data_ptr(), _p(xs2), cs1, cin_sc,
-                                  n, h, w, cin, cout, cout, n, _p(part), _stream()), fn)
+        name, fn = route.entry("_sc", "bf16")
+        _lib.check(fn(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), _p(b_sc), out.data_ptr(), xs.data_ptr(), _p(xs2), cs1, cin_sc,
+                      n, h, w, cin, cout, cout, n, _p(part), _stream()), name)
         return (out, part) if emit_gn else out
     wp = _w_halo_packed(weight_cl)
     out = torch.empty(n, h, w, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
     conv_halo_calls["conv"] += 1
     conv_halo_calls["gn_fused"] += gn_coef is not None
     if call_log is not None:
-        call_log.append(("conv_halo", (n, h, w, cin, cout, bool(upsample)) + mark, 2.0 * n * h * w * cout * 9 * cin))
-    fn = "fmc_conv3x3_halo_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_bf16"
-    _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(),
-                              n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(gn_coef),
-                              int(gn_act), _p(part), _stream()), fn)
+        call_log.append(("conv_halo", (n, h, w, cin, cout, bool(upsample)) + route.mark, 2.0 * n * h * w * cout * 9 * cin))
+    name, fn = route.entry("", "bf16")
+    _lib.check(fn(x_nhwc.data_ptr(), _p(x2_nhwc), c1, wp.data_ptr(), _p(bias), _p(temb), _p(residual_nhwc), out.data_ptr(),
+                  n, h, w, cin, cout, 0 if temb is None else temb.stride(0), int(temb_div), int(upsample), _p(gn_coef),
+                  int(gn_act), _p(part), _stream()), name)
     return (out, part) if emit_gn else out
 
 
@@ -2457,38 +2515,32 @@ def conv3x3_upfold_reference(x_nchw: torch.Tensor, wf: torch.Tensor, bias: Optio
     return out if bias is None else out + bias[None, :, None, None]
 
 
+def _upfold_route(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[HaloRoute]:
+    """The phase-mode launch that takes the upsample convolution of `n` source images `hs x ws`, or None (the 9-tap path keeps the shape): the whole-tile
+    launches of sources at least `UPS_FOLD_MIN_WS` wide first, then, with `PARTIAL_TILES` on, the partial ones where `partial_conv_routed` says so."""
+    for kernel, partial in (("halo", False), ("halo4", False), ("halo", True), ("halo4", True)) if UPS_FOLD and CONV_HALO else ():
+        if (kernel == "halo4" and not CONV_HALO4) or (not partial and ws < UPS_FOLD_MIN_WS) or (
+                partial and not (PARTIAL_TILES and partial_conv_routed("upfold_" + kernel, n, hs, ws, cin, cout) and ws % (32 if kernel == "halo" else 8))):
+            continue
+        route = HaloRoute(kernel, partial, bn=160 if kernel == "halo" else 80)
+        if kernel == "halo4" and not partial and UPS_FOLD_WIDE and HaloRoute("halo4w").entry("_fold", "supported")[1](n, hs, ws, cin, cout, 1):
+            route = HaloRoute("halo4w")
+        if not route.entry("_fold", "supported")[1](n, hs, ws, cin, cout, *route.tail[:1]):
+            continue
+        if kernel == "halo4" and partial:
+            route = route._replace(tw=_halo4_tw(hs, ws, False))
+        if _halo_tiles(route, n, hs, ws, cout, phases=4)[0] >= CONV_HALO_MIN_TILES:
+            return route
+    return None
+
+
 def conv3x3_upfold_arm(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[str]:
     """Which phase-mode launch takes the upsample convolution of `n` source images `hs x ws`: "halo" (10 x 32 source tiles, csrc/conv_halo.hip),
     "halo4" / "halo4w" (320 source pixels of whole row blocks, csrc/conv_halo4.hip), or None (the 9-tap path keeps the shape).  With `PARTIAL_TILES`
     on, a source width none of them takes can go to "halo_partial" / "halo4_partial", the same launches with a partly filled last column tile, where
     `partial_conv_routed` says so."""
-    arm = _upfold_arm_whole(n, hs, ws, cin, cout)
-    if arm is not None or not (PARTIAL_TILES and UPS_FOLD and CONV_HALO):
-        return arm
-    L = _lib.load()
-    if (partial_conv_routed("upfold_halo", n, hs, ws, cin, cout) and ws % 32 and L.fmc_conv3x3_halo_fold_partial_supported(n, hs, ws, cin, cout)
-            and n * L.fmc_conv3x3_halo_partial_tiles_per_image(hs, ws) * 4 * (cout // 160) >= CONV_HALO_MIN_TILES):
-        return "halo_partial"
-    if (CONV_HALO4 and partial_conv_routed("upfold_halo4", n, hs, ws, cin, cout) and ws % 8 and L.fmc_conv3x3_halo4_fold_partial_supported(n, hs, ws, cin, cout, 0)
-            and 4 * L.fmc_conv3x3_halo4_partial_tiles(n, hs, ws, cout, 0, L.fmc_conv3x3_halo4_partial_tw(hs, ws, 0)) >= CONV_HALO_MIN_TILES):
-        return "halo4_partial"
-    return None
-
-
-def _upfold_arm_whole(n: int, hs: int, ws: int, cin: int, cout: int) -> Optional[str]:
-    if not (UPS_FOLD and CONV_HALO) or ws < UPS_FOLD_MIN_WS:
-        return None
-    L = _lib.load()
-    if (L.fmc_conv3x3_halo_fold_supported(n, hs, ws, cin, cout)
-            and n * L.fmc_conv3x3_halo_tiles_per_image(hs, ws) * 4 * (cout // 160) >= CONV_HALO_MIN_TILES):
-        return "halo"
-    if not CONV_HALO4:
-        return None
-    wide = UPS_FOLD_WIDE and bool(L.fmc_conv3x3_halo4_fold_supported(n, hs, ws, cin, cout, 1))
-    if (L.fmc_conv3x3_halo4_fold_supported(n, hs, ws, cin, cout, int(wide))
-            and 4 * L.fmc_conv3x3_halo4_tiles(n, hs, ws, cout, int(wide)) >= CONV_HALO_MIN_TILES):
-        return "halo4w" if wide else "halo4"
-    return None
+    route = _upfold_route(n, hs, ws, cin, cout)
+    return None if route is None else route.arm
 
 
 def _w_upfold_packed(weight_cl: torch.Tensor, tile_channels: int) -> torch.Tensor:
@@ -2514,39 +2566,19 @@ def conv3x3_upfold(x_nhwc: torch.Tensor, weight_cl: torch.Tensor, bias=None, emi
         arm, partial_tiles = arm[:-len("_partial")], True
     if arm not in ("halo", "halo4", "halo4w"):
         raise ValueError(f"conv3x3_upfold: no phase-mode launch for n={n} {hs}x{ws} {cin}->{cout} (arm {arm})")
-    L = _lib.load()
-    mark = ("partial",) if partial_tiles else ()
+    tw = _halo4_tw(hs, ws, arm == "halo4w", tw) if partial_tiles and arm != "halo" else None      # (conv_halo4's partial launches alone take one)
+    route = HaloRoute(arm, bool(partial_tiles), tw, bn=80 if arm == "halo4" else 160)
+    wp = _w_upfold_packed(weight_cl, route.bn)
     out = torch.empty(n, 2 * hs, 2 * ws, cout, dtype=x_nhwc.dtype, device=x_nhwc.device)
     shape, flops = (n, 2 * hs, 2 * ws, cin, cout, True), 2.0 * n * 4 * hs * ws * cout * 9 * cin      # (the algorithmic, 9-tap flops: useful-work rates)
+    part = torch.empty(n, _halo_tiles(route, n, hs, ws, cout, phases=4)[1], 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
+    family = "conv" if arm == "halo" else "conv4"
     conv_halo_calls["upfold"] = conv_halo_calls.get("upfold", 0) + 1
-    if arm == "halo":
-        wp = _w_upfold_packed(weight_cl, 160)
-        tiles_fn = L.fmc_conv3x3_halo_partial_tiles_per_image if partial_tiles else L.fmc_conv3x3_halo_tiles_per_image
-        part = torch.empty(n, 4 * tiles_fn(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
-        conv_halo_calls["conv"] += 1
-        if call_log is not None:
-            call_log.append(("conv_halo", shape + mark, flops))
-        fn = "fmc_conv3x3_halo_fold_partial_bf16" if partial_tiles else "fmc_conv3x3_halo_fold_bf16"
-        _lib.check(getattr(L, fn)(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), _stream()), fn)
-    else:
-        wide = arm == "halo4w"
-        wp = _w_upfold_packed(weight_cl, 160 if wide else 80)
-        if partial_tiles:
-            tw = int(L.fmc_conv3x3_halo4_partial_tw(hs, ws, int(wide))) if tw is None else int(tw)
-            part = (torch.empty(n, 4 * L.fmc_conv3x3_halo4_partial_row_blocks_per_image(hs, ws, tw), 32, 2, dtype=torch.float32, device=x_nhwc.device)
-                    if emit_gn else None)
-            conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
-            if call_log is not None:
-                call_log.append(("conv_halo4", shape + (("partial", tw),), flops))
-            _lib.check(L.fmc_conv3x3_halo4_fold_partial_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part),
-                                                             int(wide), tw, _stream()), "fmc_conv3x3_halo4_fold_partial_bf16")
-            return (out, part) if emit_gn else out
-        part = torch.empty(n, 4 * L.fmc_conv3x3_halo4_row_blocks_per_image(hs, ws), 32, 2, dtype=torch.float32, device=x_nhwc.device) if emit_gn else None
-        conv_halo_calls["conv4"] = conv_halo_calls.get("conv4", 0) + 1
-        if call_log is not None:
-            call_log.append(("conv_halo4", shape, flops))
-        _lib.check(L.fmc_conv3x3_halo4_fold_bf16(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), int(wide),
-                                                 _stream()), "fmc_conv3x3_halo4_fold_bf16")
+    conv_halo_calls[family] = conv_halo_calls.get(family, 0) + 1
+    if call_log is not None:
+        call_log.append(("conv_halo" if arm == "halo" else "conv_halo4", shape + route.mark, flops))
+    name, fn = route.entry("_fold", "bf16")
+    _lib.check(fn(x_nhwc.data_ptr(), wp.data_ptr(), _p(bias), out.data_ptr(), n, hs, ws, cin, cout, _p(part), *route.tail, _stream()), name)
     return (out, part) if emit_gn else out
 
 
@@ -3019,18 +3051,16 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
     import torch.nn.functional as F
 
     if shortcut is not None:
-        n, cin, h, w = x_nchw.shape
         cout = weight_cl.shape[0]
         xs, xs2, w_sc, b_sc = shortcut
         assert temb is None and residual_nchw is None and not upsample and tuple(stride) == (1, 1) and tuple(padding) == (1, 1)
-        if not shortcut_fold_ok(x_nchw, weight_cl, xs, xs2):
+        route = _shortcut_fold_route(x_nchw, weight_cl, xs, xs2)
+        if route is None:
             raise RuntimeError("conv3x3: no kernel takes this shape with the shortcut in the reduction")
-        want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0)
+        want = _halo_emit_gn(route, emit_gn, x_nchw.shape[2], x_nchw.shape[3], cout)
         dispatch_calls["conv3x3"]["own"] += 1
-        cs1 = xs.shape[1]
         y = conv3x3_halo(x_nchw.permute(0, 2, 3, 1), weight_cl, bias, emit_gn=want,
-                         shortcut=(xs.permute(0, 2, 3, 1), None if xs2 is None else xs2.permute(0, 2, 3, 1), w_sc, b_sc),
-                         partial_tiles=_shortcut_fold_partial(n, h, w, cin, cout, cs1 + (xs2.shape[1] if xs2 is not None else 0), cs1))
+                         shortcut=(xs.permute(0, 2, 3, 1), None if xs2 is None else xs2.permute(0, 2, 3, 1), w_sc, b_sc), partial_tiles=route.partial)
         return _gn_tagged(y, want, cout)
 
     def lib():
@@ -3072,53 +3102,22 @@ def conv3x3(x_nchw: torch.Tensor, weight_cl: torch.Tensor, bias, temb=None, resi
         h, w = h // 2, w // 2
     # the upsample convolutions at inference: four 2x2-tap convolutions of the source on the folded filter (4 taps per output instead of 9)
     if upsample and temb is None and r is None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and weight_cl.dtype == torch.bfloat16:
-        arm = conv3x3_upfold_arm(n, h // 2, w // 2, cin, cout)
-        if arm is not None:
-            bn = 80 if arm in ("halo4", "halo4_partial") else 160
-            want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and bn % (cout // 32) == 0 and (arm in ("halo", "halo_partial") or h * w >= GN_MIN_HW))
+        route = _upfold_route(n, h // 2, w // 2, cin, cout)
+        if route is not None:
+            want = _halo_emit_gn(route, emit_gn, h, w, cout)
             dispatch_calls["conv3x3"]["own"] += 1
-            y = conv3x3_upfold(x, weight_cl, bias, emit_gn=want, arm=arm)
+            y = conv3x3_upfold(x, weight_cl, bias, emit_gn=want, arm=route.arm)
             return _gn_tagged(y, want, cout)
-    # the halo-resident kernel (csrc/conv_halo.hip): 1.75 - 1.95 x the ring kernels wherever its 10 x 32 pixel x 160 channel tiles fill the chip
-    # (tools/scratch/r05/bench_halo.py); every such convolution also leaves the statistics of the GroupNorm that consumes its output
-    if (CONV_HALO and not stride2 and (temb is None or temb.stride(1) == 1) and conv3x3_halo_supported(n, h, w, cin, cin, cout, upsample)
-            and n * _lib.load().fmc_conv3x3_halo_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES):
-        want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0 and not torch.is_grad_enabled())
+    # the halo-resident kernels (`_halo_route`); every such convolution can also leave the statistics of the GroupNorm that consumes its output
+    route = _halo_route(n, h, w, cin, cout, upsample) if not stride2 and (temb is None or temb.stride(1) == 1) else None
+    if route is not None:
+        want = _halo_emit_gn(route, emit_gn, h, w, cout)
         dispatch_calls["conv3x3"]["own"] += 1
-        y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
+        if route.kernel == "halo":
+            y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=route.partial)
+        else:
+            y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=route.partial, tw=route.tw)
         return _gn_tagged(y, want, cout)
-    # (`PARTIAL_TILES` on: a width that is no multiple of 32 on the same tiles with a partly filled last column tile, where that measured faster)
-    if (PARTIAL_TILES and partial_conv_routed("halo", n, h, w, cin, cout) and CONV_HALO and not stride2 and w % 32 and (temb is None or temb.stride(1) == 1)
-            and conv3x3_halo_partial_supported(n, h, w, cin, cin, cout, upsample)
-            and n * _lib.load().fmc_conv3x3_halo_partial_tiles_per_image(h, w) * (cout // 160) >= CONV_HALO_MIN_TILES):
-        want = bool(emit_gn and GN_EPILOGUE and cout % 64 == 0 and 160 % (cout // 32) == 0 and not torch.is_grad_enabled())
-        dispatch_calls["conv3x3"]["own"] += 1
-        y = conv3x3_halo(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=True)
-        return _gn_tagged(y, want, cout)
-    # ... and its 4-wave form for the small feature maps (images 8 / 16 pixels wide: the two inner levels; csrc/conv_halo4.hip), split over the
-    # reduction where the tiles alone would leave most of the chip idle (5x8-pixel images: 64 tiles)
-    if (CONV_HALO and CONV_HALO4 and not stride2 and w % 8 == 0 and (temb is None or temb.stride(1) == 1)
-            and conv3x3_halo4_supported(n, h, w, cin, cin, cout, upsample)
-            and _lib.load().fmc_conv3x3_halo4_tiles(n, h, w, cout, 0) * conv3x3_halo4_split(n, h, w, cin, cout) >= CONV_HALO_MIN_TILES):
-        dispatch_calls["conv3x3"]["own"] += 1
-        # (statistics for the consuming GroupNorm where it would otherwise read its input twice -- the two-pass norm of the large feature maps -- and
-        #  the launch is not split over the reduction)
-        want = bool(emit_gn and GN_EPILOGUE and h * w >= GN_MIN_HW and cout % 64 == 0 and 80 % (cout // 32) == 0 and not torch.is_grad_enabled()
-                    and conv3x3_halo4_split(n, h, w, cin, cout) == 1)
-        y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want)
-        return _gn_tagged(y, want, cout)
-    # (`PARTIAL_TILES` on: a width that is no multiple of 8 on the same row blocks with a partly filled last one per image row)
-    if (PARTIAL_TILES and partial_conv_routed("halo4", n, h, w, cin, cout) and CONV_HALO and CONV_HALO4 and not stride2 and w % 8 and (temb is None or temb.stride(1) == 1)
-            and conv3x3_halo4_partial_supported(n, h, w, cin, cin, cout, upsample)):
-        L = _lib.load()
-        tw = int(L.fmc_conv3x3_halo4_partial_tw(h, w, 0))
-        split = conv3x3_halo4_split(n, h, w, cin, cout, tw=tw)
-        if L.fmc_conv3x3_halo4_partial_tiles(n, h, w, cout, 0, tw) * split >= CONV_HALO_MIN_TILES:
-            dispatch_calls["conv3x3"]["own"] += 1
-            want = bool(emit_gn and GN_EPILOGUE and h * w >= GN_MIN_HW and cout % 64 == 0 and 80 % (cout // 32) == 0 and not torch.is_grad_enabled()
-                        and split == 1)
-            y = conv3x3_halo4(x, weight_cl, bias, temb, r, temb_div, upsample, emit_gn=want, partial_tiles=True, tw=tw)
-            return _gn_tagged(y, want, cout)
     if emit_gn and gn_emit_ok(n * h * w, cout, 9 * cin, h * w, x.dtype):
         dispatch_calls["conv3x3"]["own"] += 1
         y, tag = conv3x3_gn(x, weight_cl, bias, temb, r, temb_div, upsample, stride2)

@@ -11,7 +11,8 @@ import torch
 from tests import conv_fwd_common as C
 from tests import conv_partial_common as P
 from tests import edge_guard_common as EG
-from tests import fake_kernels
+from tests import halo_host_surface_common as S
+from tests.conv_dispatch_standins import Launches as _Launches
 
 BF16 = torch.bfloat16
 
@@ -127,47 +128,6 @@ def test_case_references_meet_the_instruments_conditions(s, folded):
 
 
 # ---- 3. dispatch ---------------------------------------------------------------------------------------------------------------------------------------------
-class _Launches:
-    """Recording stand-ins for the launch wrappers `conv3x3` chooses between."""
-
-    def __init__(self, monkeypatch, K):
-        fake_kernels.install(monkeypatch)                                    # (no launch of the library from a host test)
-        self.log = []
-        monkeypatch.setattr(K, "conv3x3_supported", lambda x, w, stride, padding: True)
-        monkeypatch.setattr(K, "PARTIAL_CONV_RULES", False)                  # (the mechanics: every shape of a routed kind; the measured rule has its own test)
-        monkeypatch.setattr(K, "CONV_HALO_MIN_TILES", 1)
-        monkeypatch.setattr(K, "gn_emit_ok", lambda *a: False)
-
-        def out(x, w, ups):
-            n, h, wd, _ = x.shape
-            return torch.zeros(n, 2 * h if ups else h, 2 * wd if ups else wd, w.shape[0], dtype=x.dtype)
-
-        def halo(x, w, bias=None, temb=None, res=None, temb_div=1, upsample=False, x2_nhwc=None, gn_coef=None, gn_act=True, emit_gn=False, shortcut=None,
-                 partial_tiles=False):
-            self.log.append(("halo_sc" if shortcut is not None else "halo", partial_tiles))
-            return (out(x, w, upsample), torch.zeros(1)) if emit_gn else out(x, w, upsample)
-
-        def halo4(x, w, bias=None, temb=None, res=None, temb_div=1, upsample=False, x2_nhwc=None, emit_gn=False, split_k=None, wide=False,
-                  partial_tiles=False, tw=None):
-            self.log.append(("halo4", partial_tiles, tw))
-            return (out(x, w, upsample), torch.zeros(1)) if emit_gn else out(x, w, upsample)
-
-        def upfold(x, w, bias=None, emit_gn=False, arm=None, partial_tiles=False, tw=None):
-            self.log.append(("upfold", arm))
-            return (out(x, w, True), torch.zeros(1)) if emit_gn else out(x, w, True)
-
-        def ring(x, w, bias=None, temb=None, res=None, tile=0, temb_div=1, upsample=False, stride2=False, **kw):
-            self.log.append(("ring",))
-            return out(x, w, upsample)
-        for name, fn in (("conv3x3_halo", halo), ("conv3x3_halo4", halo4), ("conv3x3_upfold", upfold), ("conv3x3_bf16", ring)):
-            monkeypatch.setattr(K, name, fn)
-        monkeypatch.setattr(K, "_pick", lambda *a, **kw: 1)
-
-    def take(self):
-        log, self.log = self.log, []
-        return log
-
-
 def _conv_args(n, h, w, cin, cout):
     x = torch.zeros(n, h, w, cin, dtype=BF16).permute(0, 3, 1, 2)
     wt = torch.zeros(cout, cin, 3, 3, dtype=BF16).contiguous(memory_format=torch.channels_last)
@@ -239,24 +199,29 @@ def test_conv3x3_dispatch_switch_off_and_on(monkeypatch, K):
 
 def test_shortcut_fold_dispatch(monkeypatch, K):
     calls = _Launches(monkeypatch, K)
+    partial = lambda *a: getattr(K._shortcut_route(*a), "partial", False)    # the shortcut route asked for "partial" (no route: no)
     args = (4, 8, 48, 320, 320, 640, 320)
-    assert not K._shortcut_fold_partial(*args)                               # switch off
+    assert not partial(*args)                                                # switch off
     monkeypatch.setattr(K, "PARTIAL_TILES", True)
     monkeypatch.setattr(K, "PARTIAL_CONV_ROUTED", frozenset(("halo_sc",)))
-    assert K._shortcut_fold_partial(*args) and not K._shortcut_fold_partial(4, 8, 64, 320, 320, 640, 320)      # a whole-tile width keeps its launch
-    assert not K._shortcut_fold_partial(4, 8, 48, 320, 240, 640, 320)
-    monkeypatch.setattr(K, "shortcut_fold_ok", lambda *a: True)
-    x, wt = _conv_args(4, 8, 48, 320, 320)
-    xs = torch.zeros(4, 8, 48, 320, dtype=BF16).permute(0, 3, 1, 2)
+    assert partial(*args) and not partial(4, 8, 64, 320, 320, 640, 320)      # a whole-tile width keeps its launch
+    assert not partial(4, 8, 48, 320, 240, 640, 320)
+    # (storage-less operands that say they are on the GPU: `conv3x3` asks the same route as `shortcut_fold_ok`, which looks at them)
+    x, wt = S.image(4, 8, 48, 320, nchw=True, cuda=True), S.filter_cl(320, 320)
+    xs = S.image(4, 8, 48, 320, nchw=True, cuda=True)
     with torch.no_grad():
-        K.conv3x3(x, wt, None, shortcut=(xs, xs, torch.zeros(320, 640, dtype=BF16), None))
+        assert K.shortcut_fold_ok(x, wt, xs, xs)
+        K.conv3x3(x, wt, None, shortcut=(xs, xs, S.image(320, 640), None))
         assert calls.take() == [("halo_sc", True)]
-        x, wt = _conv_args(4, 8, 64, 320, 320)
-        xs = torch.zeros(4, 8, 64, 320, dtype=BF16).permute(0, 3, 1, 2)
-        K.conv3x3(x, wt, None, shortcut=(xs, xs, torch.zeros(320, 640, dtype=BF16), None))
+        x, xs = S.image(4, 8, 64, 320, nchw=True, cuda=True), S.image(4, 8, 64, 320, nchw=True, cuda=True)
+        assert K.shortcut_fold_ok(x, wt, xs, xs)
+        K.conv3x3(x, wt, None, shortcut=(xs, xs, S.image(320, 640), None))
         assert calls.take() == [("halo_sc", False)]
     monkeypatch.setattr(K, "PARTIAL_CONV_ROUTED", frozenset(("halo",)))
-    assert not K._shortcut_fold_partial(*args)
+    assert not partial(*args)
+    x, xs = S.image(4, 8, 48, 320, nchw=True, cuda=True), S.image(4, 8, 48, 320, nchw=True, cuda=True)
+    with torch.no_grad():
+        assert not K.shortcut_fold_ok(x, wt, xs, xs)
 
 
 def test_routing_rule_restates_the_measured_table(K):
