@@ -357,66 +357,61 @@ void geglu_pipe_kernel(const GPParams P) {
 }  // namespace
 
 // variant: 0 = 80-row tiles, 4 waves, 32 gated columns per wave (C = 320 | 640; weights packed with group 32); 1 = 160-row tiles, 8 waves, 16 gated columns
-// per wave (C = 320 only, M % 160 == 0; weights packed with group 16)
-extern "C" int fmc_geglu_pipe_supported(int64_t M, int cff, int C, int variant) {
-    const bool common = M > 0 && cff > 0 && cff % 128 == 0 && M * (int64_t)cff * 2 < ((int64_t)1 << 31) && (int64_t)2 * cff * C * 2 < ((int64_t)1 << 31) &&
-                        M * (int64_t)C * 2 < ((int64_t)1 << 31);
-    if (variant == 1) return common && C == 320 && M % 160 == 0;
-    return common && (C == 320 || C == 640) && M % 80 == 0;
+// per wave (C = 320 only; weights packed with group 16).  Whole tiles: M % 80 == 0 (variant 1: M % 160 == 0).  `any_rows` (the partial-tile entry point): any
+// M >= 1, the bounds on the row count padded to whole 160-row tiles (what a tile-major result spans)
+static bool pipe_shape_ok(int64_t M, int cff, int C, int variant, bool any_rows) {
+    const int64_t Mp = any_rows ? (M + 159) / 160 * 160 : M;
+    const bool common = M > 0 && cff > 0 && cff % 128 == 0 && Mp * (int64_t)cff * 2 < ((int64_t)1 << 31) && (int64_t)2 * cff * C * 2 < ((int64_t)1 << 31) &&
+                        Mp * (int64_t)C * 2 < ((int64_t)1 << 31);
+    // inherited, not derived: the whole-tile rule takes any variant other than 1 as the 80-row form (the launcher checks `variant` itself)
+    if (variant == 1) return common && C == 320 && (any_rows || M % 160 == 0);
+    return (variant == 0 || !any_rows) && common && (C == 320 || C == 640) && (any_rows || M % 80 == 0);
 }
 
-extern "C" int fmc_geglu_pipe_ln_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed, const void* bias,
-                                      int64_t M, int cff, int C, int out_blocked, int variant, void* stream) {
-    if (!h || !out || !ln_gamma || !ln_beta || !w_packed) FMC_FAIL(FMC_E_NULL, "geglu_pipe_ln_bf16: NULL tensor");
-    if ((variant != 0 && variant != 1) || !fmc_geglu_pipe_supported(M, cff, C, variant) || (out_blocked && (M % 160 || cff % 32)))
-        FMC_FAIL(FMC_E_SHAPE, "geglu_pipe_ln_bf16: C in {320, 640} (variant 1: 320), M %% 80 == 0 (%% 160 tile-major / variant 1), cff %% 128 == 0, tensors below "
-                              "2 GiB (got M=%lld cff=%d C=%d variant=%d)", (long long)M, cff, C, variant);
-    if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_packed) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_beta) || (bias && ((uintptr_t)bias & 7)))
-        FMC_FAIL(FMC_E_ALIGN, "geglu_pipe_ln_bf16: tensors must be 16-byte aligned");
-    GPParams P;
-    P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
-    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
-    constexpr int lds320 = 80 * 320 * 2 + 640, lds640 = 80 * 640 * 2 + 640, lds320w = 160 * 320 * 2 + 1280;
-    hipStream_t st = (hipStream_t)stream;
-    // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
-    if (variant == 0 && C == 320) fmc_launch<geglu_pipe_kernel<320, 4, 5, 4>>(dim3((unsigned)(M / 80)), dim3(256), lds320, st, P);
-    else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4>>(dim3((unsigned)(M / 80)), dim3(256), lds640, st, P);
-    else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2>>(dim3((unsigned)(M / 160)), dim3(512), lds320w, st, P);
-    FMC_CHECK_LAUNCH("fmc_geglu_pipe_ln_bf16");
-    return 0;
-}
+extern "C" int fmc_geglu_pipe_supported(int64_t M, int cff, int C, int variant) { return pipe_shape_ok(M, cff, C, variant, false); }
+extern "C" int fmc_geglu_pipe_partial_supported(int64_t M, int cff, int C, int variant) { return pipe_shape_ok(M, cff, C, variant, true); }
 
-// Partly filled last tile (geglu_pipe_kernel<..., PARTIAL_ = true>): any M >= 1, ceil(M / ROWS) workgroups.  Decision on the two ends of the tile:
+// `partial`: a partly filled last tile (geglu_pipe_kernel<..., PARTIAL_ = true>) -- any M >= 1, ceil(M / ROWS) workgroups.  Decision on the two ends of the tile:
 //   * reads: the source row of the `h` DMA is CLAMPED to the tile's last valid row, as the fused attention blocks do -- every address lies inside the
 //     tensor and nothing rests on what an out-of-range LDS-DMA leaves in LDS.  A pad row is the last valid row again: finite wherever that row is;
 //   * stores: a pad row's store carries its whole byte offset in the per-lane operand and that operand is selected out of range (0x80000000), so the
 //     descriptor's range check drops it whichever way the hardware treats the scalar offset; the scalar offset is 0.  Row-major the range ends at row
 //     M; tile-major it is built from the padded size ceil(M / 160) * 160 rows, `out` must own that much, and its pad rows are never written.
 // Valid rows go through the same instructions in the same order as in the whole-tile form: their bits are the same.
-extern "C" int fmc_geglu_pipe_partial_supported(int64_t M, int cff, int C, int variant) {
-    const int64_t Mp = (M + 159) / 160 * 160;
-    const bool common = M > 0 && cff > 0 && cff % 128 == 0 && Mp * (int64_t)cff * 2 < ((int64_t)1 << 31) && (int64_t)2 * cff * C * 2 < ((int64_t)1 << 31) &&
-                        Mp * (int64_t)C * 2 < ((int64_t)1 << 31);
-    if (variant == 1) return common && C == 320;
-    return variant == 0 && common && (C == 320 || C == 640);
+template <bool PARTIAL>
+static void pipe_launch(const GPParams& P, int C, int variant, hipStream_t st) {
+    constexpr int lds320 = 80 * 320 * 2 + 640, lds640 = 80 * 640 * 2 + 640, lds320w = 160 * 320 * 2 + 1280;
+    const unsigned g80 = (unsigned)((P.M + 79) / 80), g160 = (unsigned)((P.M + 159) / 160);          // (whole tiles: M / 80, M / 160)
+    if (variant == 0 && C == 320) fmc_launch<geglu_pipe_kernel<320, 4, 5, 4, PARTIAL>>(dim3(g80), dim3(256), lds320, st, P);
+    else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4, PARTIAL>>(dim3(g80), dim3(256), lds640, st, P);
+    else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2, PARTIAL>>(dim3(g160), dim3(512), lds320w, st, P);
+}
+
+static int pipe_run(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed, const void* bias, int64_t M, int cff,
+                    int C, int out_blocked, int variant, void* stream, bool partial) {
+    const char* name = partial ? "geglu_pipe_ln_partial_bf16" : "geglu_pipe_ln_bf16";
+    if (!h || !out || !ln_gamma || !ln_beta || !w_packed) FMC_FAIL(FMC_E_NULL, "%s: NULL tensor", name);
+    if ((!partial && ((variant != 0 && variant != 1) || (out_blocked && (M % 160 || cff % 32)))) || !pipe_shape_ok(M, cff, C, variant, partial))
+        FMC_FAIL(FMC_E_SHAPE, "%s: C in {320, 640} (variant 1: 320), %s (got M=%lld cff=%d C=%d variant=%d)", name,
+                 partial ? "M >= 1, cff % 128 == 0, padded tensors below 2 GiB" : "M % 80 == 0 (% 160 tile-major / variant 1), cff % 128 == 0, tensors below 2 GiB",
+                 (long long)M, cff, C, variant);
+    if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_packed) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_beta) || (bias && ((uintptr_t)bias & 7)))
+        FMC_FAIL(FMC_E_ALIGN, "%s: tensors must be 16-byte aligned", name);
+    GPParams P;
+    P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
+    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
+    if (partial) pipe_launch<true>(P, C, variant, (hipStream_t)stream);
+    else pipe_launch<false>(P, C, variant, (hipStream_t)stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_geglu_pipe_ln_partial_bf16" : "fmc_geglu_pipe_ln_bf16");
+    return 0;
+}
+
+extern "C" int fmc_geglu_pipe_ln_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed, const void* bias,
+                                      int64_t M, int cff, int C, int out_blocked, int variant, void* stream) {
+    return pipe_run(h, out, ln_gamma, ln_beta, ln_eps, w_packed, bias, M, cff, C, out_blocked, variant, stream, false);
 }
 
 extern "C" int fmc_geglu_pipe_ln_partial_bf16(const void* h, void* out, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w_packed,
                                               const void* bias, int64_t M, int cff, int C, int out_blocked, int variant, void* stream) {
-    if (!h || !out || !ln_gamma || !ln_beta || !w_packed) FMC_FAIL(FMC_E_NULL, "geglu_pipe_ln_partial_bf16: NULL tensor");
-    if (!fmc_geglu_pipe_partial_supported(M, cff, C, variant))
-        FMC_FAIL(FMC_E_SHAPE, "geglu_pipe_ln_partial_bf16: C in {320, 640} (variant 1: 320), M >= 1, cff %% 128 == 0, padded tensors below 2 GiB (got M=%lld "
-                              "cff=%d C=%d variant=%d)", (long long)M, cff, C, variant);
-    if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_packed) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_beta) || (bias && ((uintptr_t)bias & 7)))
-        FMC_FAIL(FMC_E_ALIGN, "geglu_pipe_ln_partial_bf16: tensors must be 16-byte aligned");
-    GPParams P;
-    P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps;
-    P.w = (const bf16_t*)w_packed; P.bias = (const bf16_t*)bias; P.M = M; P.cff = cff; P.out_blocked = out_blocked != 0;
-    constexpr int lds320 = 80 * 320 * 2 + 640, lds640 = 80 * 640 * 2 + 640, lds320w = 160 * 320 * 2 + 1280;
-    hipStream_t st = (hipStream_t)stream;
-    if (variant == 0 && C == 320) fmc_launch<geglu_pipe_kernel<320, 4, 5, 4, true>>(dim3((unsigned)((M + 79) / 80)), dim3(256), lds320, st, P);
-    else if (variant == 0) fmc_launch<geglu_pipe_kernel<640, 4, 5, 4, true>>(dim3((unsigned)((M + 79) / 80)), dim3(256), lds640, st, P);
-    else fmc_launch<geglu_pipe_kernel<320, 8, 10, 2, true>>(dim3((unsigned)((M + 159) / 160)), dim3(512), lds320w, st, P);
-    FMC_CHECK_LAUNCH("fmc_geglu_pipe_ln_partial_bf16");
-    return 0;
+    return pipe_run(h, out, ln_gamma, ln_beta, ln_eps, w_packed, bias, M, cff, C, out_blocked, variant, stream, true);
 }

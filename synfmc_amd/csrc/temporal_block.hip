@@ -771,6 +771,17 @@ extern "C" int fmc_xattn_pack_kv40(const void* kv, void* out, int batch, int S, 
     return 0;
 }
 
+// The instantiation of temporal_block_kernel for (merge, stats, partial), temporal (XATT = false) or text cross-attention form; the persistent grid: one
+// workgroup per tile, at most one per CU
+template <bool XATT>
+static void tb_launch(const TBParams& P, bool merge, bool stats, bool partial, hipStream_t st) {
+    const int cus = fmc_cu_count();
+    const dim3 grid((unsigned)(P.tiles < cus ? P.tiles : cus)), block(512);
+    auto pick = [&](auto M, auto S, auto PT) { fmc_launch<temporal_block_kernel<XATT ? false : M.value, S.value, XATT, PT.value>>(grid, block, TB_LDS, st, P); };
+    auto on = [](bool flag, auto f) { flag ? f(std::true_type{}) : f(std::false_type{}); };
+    on(merge, [&](auto M) { on(stats, [&](auto S) { on(partial, [&](auto PT) { pick(M, S, PT); }); }); });
+}
+
 // The text cross-attention block of the spatial transformer at the 40x64 level in one launch (see fmc_xattn_block640_bf16): tokens h [images][hw][320],
 // hw % 160 == 0, 8 heads x 40; w_q_packed = hip_ops.pack_xattn_q40, w_out_tm = hip_ops._w_tilemajor, kvfrag = fmc_xattn_pack_kv40; optional row statistics.
 // `partial`: fmc_xattn_block320_partial_bf16 -- any hw >= 1; a text's segment of images_per_text * hw rows ends in a partly filled tile
@@ -795,16 +806,7 @@ static int xattn_block320_run(const void* h, void* out, const float* ln_gamma, c
     if (partial) P.tiles = (n_images / images_per_text) * (int)(((int64_t)images_per_text * hw + TB_ROWS - 1) / TB_ROWS);
     P.scale_log2 = scale * 1.4426950408889634f;
     P.dbg_times = nullptr;
-    const int cus = fmc_cu_count();
-    const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
-    // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
-    if (!partial) {
-        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-        else fmc_launch<temporal_block_kernel<false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-    } else {
-        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-        else fmc_launch<temporal_block_kernel<false, true, true, true>>(dim3(grid), dim3(512), TB_LDS, (hipStream_t)stream, P);
-    }
+    tb_launch<true>(P, false, ln_stats != nullptr, partial, (hipStream_t)stream);
     FMC_CHECK_LAUNCH(partial ? "fmc_xattn_block320_partial_bf16" : "fmc_xattn_block320_bf16");
     return 0;
 }
@@ -841,24 +843,19 @@ static int temporal_block_run(const void* h, void* out, const float* ln_gamma, c
                               float merge_scale, const void* w_qkv_packed, const void* w_out_tm, const void* b_out, float* ln_stats, float ln_stats_eps,
                               int n_clips, int frames, int hw, int channels, int heads, float scale, void* stream, bool partial) {
     if (!h || !out || !ln_gamma || !ln_bpe || !w_qkv_packed || !w_out_tm) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: NULL tensor");
-    if (channels == 640 && frames == 16 && heads == 8 && hw > 0 && n_clips > 0) {     // the 20x32 level: its own kernel and weight formats (see fmc_hip.h)
-        if ((w_merge_tm != nullptr) != (pose_term != nullptr)) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: w_merge and pose_term come together");
-        if (ln_stats) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: no row statistics at C = 640");
-        if ((int64_t)n_clips * frames * hw * channels * 2 >= ((int64_t)1 << 31)) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: tensor of 2 GiB or more");
-        if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_qkv_packed) || !fmc_aligned16(w_out_tm) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_bpe) ||
-            (w_merge_tm && (!fmc_aligned16(w_merge_tm) || !fmc_aligned16(pose_term))) || (b_out && !fmc_aligned16(b_out)))
-            FMC_FAIL(FMC_E_ALIGN, "temporal_block_bf16: tensors must be 16-byte aligned");
-        return fmc_temporal_block640_launch(h, out, ln_gamma, ln_bpe, ln_eps, w_merge_tm, pose_term, merge_scale, w_qkv_packed, w_out_tm, b_out, n_clips, hw, scale,
-                                            (hipStream_t)stream, partial);
-    }
-    if (frames != 16 || channels != 320 || heads != 8 || hw <= 0 || (!partial && hw % 10) || n_clips <= 0)
+    const bool c640 = channels == 640 && frames == 16 && heads == 8 && hw > 0 && n_clips > 0;     // the 20x32 level: its own kernel and weight formats (see fmc_hip.h)
+    if (!c640 && (frames != 16 || channels != 320 || heads != 8 || hw <= 0 || (!partial && hw % 10) || n_clips <= 0))
         FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: the fused block exists for F = 16, C = 320, 8 heads, pixels %% 10 == 0 (got F=%d C=%d H=%d hw=%d)", frames,
                  channels, heads, hw);
     if ((w_merge_tm != nullptr) != (pose_term != nullptr)) FMC_FAIL(FMC_E_NULL, "temporal_block_bf16: w_merge and pose_term come together");
+    if (c640 && ln_stats) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: no row statistics at C = 640");
     if ((int64_t)n_clips * frames * hw * channels * 2 >= ((int64_t)1 << 31)) FMC_FAIL(FMC_E_SHAPE, "temporal_block_bf16: tensor of 2 GiB or more");
     if (!fmc_aligned16(h) || !fmc_aligned16(out) || !fmc_aligned16(w_qkv_packed) || !fmc_aligned16(w_out_tm) || !fmc_aligned16(ln_gamma) || !fmc_aligned16(ln_bpe) ||
         (w_merge_tm && (!fmc_aligned16(w_merge_tm) || !fmc_aligned16(pose_term))) || (b_out && !fmc_aligned16(b_out)) || (ln_stats && ((uintptr_t)ln_stats & 7)))
         FMC_FAIL(FMC_E_ALIGN, "temporal_block_bf16: tensors must be 16-byte aligned");
+    if (c640)                                                                                  // (its `hw % 5` refusal comes behind these checks, as it did)
+        return fmc_temporal_block640_launch(h, out, ln_gamma, ln_bpe, ln_eps, w_merge_tm, pose_term, merge_scale, w_qkv_packed, w_out_tm, b_out, n_clips, hw, scale,
+                                            (hipStream_t)stream, partial);
     TBParams P{};
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_bpe = ln_bpe; P.ln_eps = ln_eps;
     P.w_merge = (const bf16_t*)w_merge_tm; P.pose_term = (const bf16_t*)pose_term; P.merge_scale = merge_scale;
@@ -868,28 +865,8 @@ static int temporal_block_run(const void* h, void* out, const float* ln_gamma, c
     P.total_rows = (int64_t)n_clips * frames * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
     P.dbg_times = g_tb_dbg;
-    const int cus = fmc_cu_count();
-    const unsigned grid = (unsigned)(P.tiles < cus ? P.tiles : cus);
-    hipStream_t st = (hipStream_t)stream;
-    if (!partial) {
-        if (w_merge_tm) {                                  // (branch order = the order hipcc emits the instantiations in, kept as it was: see fmc_launch)
-            if (!ln_stats) fmc_launch<temporal_block_kernel<true, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
-            else fmc_launch<temporal_block_kernel<true, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        } else {
-            if (!ln_stats) fmc_launch<temporal_block_kernel<false, false>>(dim3(grid), dim3(512), TB_LDS, st, P);
-            else fmc_launch<temporal_block_kernel<false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        }
-        FMC_CHECK_LAUNCH("fmc_temporal_block_bf16");
-        return 0;
-    }
-    if (w_merge_tm) {
-        if (!ln_stats) fmc_launch<temporal_block_kernel<true, false, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        else fmc_launch<temporal_block_kernel<true, true, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-    } else {
-        if (!ln_stats) fmc_launch<temporal_block_kernel<false, false, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-        else fmc_launch<temporal_block_kernel<false, true, false, true>>(dim3(grid), dim3(512), TB_LDS, st, P);
-    }
-    FMC_CHECK_LAUNCH("fmc_temporal_block_partial_bf16");
+    tb_launch<false>(P, w_merge_tm != nullptr, ln_stats != nullptr, partial, (hipStream_t)stream);
+    FMC_CHECK_LAUNCH(partial ? "fmc_temporal_block_partial_bf16" : "fmc_temporal_block_bf16");
     return 0;
 }
 

@@ -851,6 +851,19 @@ __global__ __launch_bounds__(256) void xattn_pack_kv_kernel(const bf16_t* __rest
 
 }  // namespace
 
+// The instantiation of temporal_block640_kernel for (merge, partial), temporal (XATT = false) or text cross-attention form
+template <bool XATT>
+static void t6_launch(const T6Params& P, unsigned grid, bool merge, bool partial, hipStream_t st) {
+    auto pick = [&](auto M, auto PT) { fmc_launch<temporal_block640_kernel<XATT ? false : M.value, XATT, PT.value>>(dim3(grid), dim3(512), T6_LDS, st, P); };
+    auto on = [](bool flag, auto f) { flag ? f(std::true_type{}) : f(std::false_type{}); };
+    on(merge, [&](auto M) { on(partial, [&](auto PT) { pick(M, PT); }); });
+}
+
+// tiles of `rows` rows each over `segments` runs of `seg_rows` rows: whole tiles, or (`partial`) the last tile of a run partly filled
+static int64_t t6_tiles(int64_t segments, int64_t seg_rows, int rows, bool partial) {
+    return segments * (partial ? (seg_rows + rows - 1) / rows : seg_rows / rows);
+}
+
 // called by fmc_temporal_block_bf16 (temporal_block.hip) for channels == 640; the arguments are already checked for NULL / alignment there
 int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma, const float* ln_bpe, float ln_eps, const void* w_merge_frag,
                                  const void* pose_term, float merge_scale, const void* w_qkv_packed, const void* w_out_frag, const void* b_out,
@@ -860,17 +873,10 @@ int fmc_temporal_block640_launch(const void* h, void* out, const float* ln_gamma
     P.h = (const bf16_t*)h; P.out = (bf16_t*)out; P.ln_gamma = ln_gamma; P.ln_bpe = ln_bpe; P.ln_eps = ln_eps;
     P.w_merge = (const bf16_t*)w_merge_frag; P.pose_term = (const bf16_t*)pose_term; P.merge_scale = merge_scale;
     P.w_qkv = (const bf16_t*)w_qkv_packed; P.w_out = (const bf16_t*)w_out_frag; P.b_out = (const bf16_t*)b_out;
-    P.n_clips = n_clips; P.hw = hw; P.tpc = partial ? (hw + 4) / 5 : hw / 5;
+    P.n_clips = n_clips; P.hw = hw; P.tpc = (int)t6_tiles(1, hw, 5, partial);
     P.total_rows = (int64_t)n_clips * T6_F * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
-    const unsigned grid = (unsigned)(n_clips * P.tpc);
-    if (!partial) {
-        if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
-        else fmc_launch<temporal_block640_kernel<false, false>>(dim3(grid), dim3(512), T6_LDS, st, P);
-    } else {
-        if (w_merge_frag) fmc_launch<temporal_block640_kernel<true, false, true>>(dim3(grid), dim3(512), T6_LDS, st, P);
-        else fmc_launch<temporal_block640_kernel<false, false, true>>(dim3(grid), dim3(512), T6_LDS, st, P);
-    }
+    t6_launch<false>(P, (unsigned)(n_clips * P.tpc), w_merge_frag != nullptr, partial, st);
     FMC_CHECK_LAUNCH(partial ? "fmc_temporal_block_partial_bf16 (C = 640)" : "fmc_temporal_block_bf16 (C = 640)");
     return 0;
 }
@@ -898,13 +904,8 @@ static int xattn_block640_run(const void* h, void* out, const float* ln_gamma, c
     P.n_clips = 1; P.hw = hw; P.tpc = 1;
     P.total_rows = (int64_t)n_images * hw;
     P.scale_log2 = scale * 1.4426950408889634f;
-    if (!partial) {
-        const unsigned grid = (unsigned)(P.total_rows / T6_ROWS);
-        fmc_launch<temporal_block640_kernel<false, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
-    } else {
-        const unsigned grid = (unsigned)((n_images / images_per_text) * (((int64_t)images_per_text * hw + T6_ROWS - 1) / T6_ROWS));
-        fmc_launch<temporal_block640_kernel<false, true, true>>(dim3(grid), dim3(512), T6_LDS, (hipStream_t)stream, P);
-    }
+    // (whole tiles: hw % 80 == 0, so the tiles of the texts' runs are total_rows / 80)
+    t6_launch<true>(P, (unsigned)t6_tiles(n_images / images_per_text, (int64_t)images_per_text * hw, T6_ROWS, partial), false, partial, (hipStream_t)stream);
     FMC_CHECK_LAUNCH(partial ? "fmc_xattn_block640_partial_bf16" : "fmc_xattn_block640_bf16");
     return 0;
 }

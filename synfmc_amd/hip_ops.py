@@ -1081,9 +1081,7 @@ def pack_temporal_qkv80(w_qkv: torch.Tensor, heads: int = 8) -> torch.Tensor:
 
 def temporal_block_supported(h: torch.Tensor, heads: int) -> bool:
     """`[B, F, hw, C]` bf16 tokens the fused block takes: F = 16, 8 heads, C = 320 with hw % 10 == 0 or C = 640 with hw % 5 == 0, inference."""
-    return (h.is_cuda and h.dtype == torch.bfloat16 and h.ndim == 4 and h.is_contiguous() and h.shape[1] == 16 and heads == 8
-            and ((h.shape[3] == 320 and h.shape[2] % 10 == 0) or (h.shape[3] == 640 and h.shape[2] % 5 == 0 and TEMPORAL_FUSED_640))
-            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled())
+    return _temporal_block_ok(h, heads, any_rows=False)
 
 
 TEMPORAL_FUSED_640 = os.environ.get("FMC_TEMPORAL_FUSED_640", "1") != "0"      # A/B switch: the 20x32-level blocks on the un-fused chain
@@ -1105,11 +1103,10 @@ def temporal_block(h: torch.Tensor, ln_gamma: torch.Tensor, ln_bpe: torch.Tensor
     stats = torch.empty(B * F * hw, 2, dtype=torch.float32, device=h.device) if stats_eps is not None else None
     _log_call("fused_block", ("temporal", B * F * hw, C, w_merge_tm is not None) + ((("partial", temporal_tile_count(B, hw, C)),) if partial_tiles else ()),
               2.0 * B * F * hw * C * C * (5 if w_merge_tm is not None else 4) + 4.0 * B * F * hw * F * C)
-    fn = _lib.load().fmc_temporal_block_partial_bf16 if partial_tiles else _lib.load().fmc_temporal_block_bf16
+    name, fn = _entry("fmc_temporal_block_bf16", partial_tiles)
     _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_bpe.data_ptr(), float(ln_eps), _p(w_merge_tm),
                   _p(pose_term), float(merge_scale), w_qkv_packed.data_ptr(), w_out_tm.data_ptr(), _p(b_out),
-                  _p(stats), float(stats_eps or 0.0), B, F, hw, C, 8, float(scale), _stream()),
-               "fmc_temporal_block_partial_bf16" if partial_tiles else "fmc_temporal_block_bf16")
+                  _p(stats), float(stats_eps or 0.0), B, F, hw, C, 8, float(scale), _stream()), name)
     return out if stats is None else (out, stats)
 
 
@@ -1131,10 +1128,7 @@ def pack_xattn_q40(w_q: torch.Tensor, heads: int = 8) -> torch.Tensor:
 def xattn_block_supported(h: torch.Tensor, kv_tokens: int, heads: int) -> bool:
     """`[images, hw, C]` bf16 tokens the fused text cross-attention block takes: 8 heads, at most 80 text tokens, inference; C = 640 with hw % 80 == 0
     or C = 320 with hw % 160 == 0."""
-    if not (h.is_cuda and h.dtype == torch.bfloat16 and h.ndim == 3 and h.is_contiguous() and heads == 8 and 0 < kv_tokens <= 80
-            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
-        return False
-    return (XATTN_FUSED_640 and h.shape[2] == 640 and h.shape[1] % 80 == 0) or (XATTN_FUSED_320 and h.shape[2] == 320 and h.shape[1] % 160 == 0)
+    return _xattn_block_ok(h, kv_tokens, heads, any_rows=False)
 
 
 xattn_block640_supported = xattn_block_supported
@@ -1169,24 +1163,17 @@ def xattn_block(h: torch.Tensor, ln_gamma: torch.Tensor, ln_btab: torch.Tensor, 
     B, S, C2 = kv.shape
     assert C in (320, 640) and C2 == 2 * C and kv.stride(2) == 1 and kv.stride(1) == C2 and N % images_per_text == 0 and N // images_per_text == B
     out = torch.empty_like(h)
-    L = _lib.load()
     _log_call("fused_block", ("xattn", N * hw, C, S) + ((("partial", xattn_tile_count(N, hw, images_per_text, C)),) if partial_tiles else ()),
               2.0 * N * hw * C * C * 2 + 4.0 * N * hw * S * C)
     if frag is None:
         frag = xattn_pack_kv(kv)
     assert frag.numel() == B * 8 * (12800 if C == 640 else 7680) and frag.dtype == h.dtype
-    if C == 640:
-        assert stats_eps is None
-        fn = L.fmc_xattn_block640_partial_bf16 if partial_tiles else L.fmc_xattn_block640_bf16
-        _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
-                      frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), N, hw, S, images_per_text, float(scale), _stream()),
-                   "fmc_xattn_block640_partial_bf16" if partial_tiles else "fmc_xattn_block640_bf16")
-        return out
+    assert C == 320 or stats_eps is None
     stats = torch.empty(N * hw, 2, dtype=torch.float32, device=h.device) if stats_eps is not None else None
-    fn = L.fmc_xattn_block320_partial_bf16 if partial_tiles else L.fmc_xattn_block320_bf16
-    _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(),
-                  frag.data_ptr(), w_out_packed.data_ptr(), _p(b_out), _p(stats), float(stats_eps or 0.0), N, hw, S, images_per_text,
-                  float(scale), _stream()), "fmc_xattn_block320_partial_bf16" if partial_tiles else "fmc_xattn_block320_bf16")
+    name, fn = _entry("fmc_xattn_block%d_bf16" % C, partial_tiles)
+    _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_btab.data_ptr(), float(ln_eps), w_q_packed.data_ptr(), frag.data_ptr(),
+                  w_out_packed.data_ptr(), _p(b_out), *((_p(stats), float(stats_eps or 0.0)) if C == 320 else ()), N, hw, S, images_per_text,
+                  float(scale), _stream()), name)
     return out if stats is None else (out, stats)
 
 
@@ -1289,20 +1276,50 @@ def ff_mxfp8_ok(h: torch.Tensor, w_proj: torch.Tensor, w_out: torch.Tensor, resi
     return mxfp8_supported(M, inner, C, True) and mxfp8_supported(M, n_out, inner, False)
 
 
-def _tile_units(C: int, xattn: bool) -> int:
-    """What a tile of the fused blocks holds: pixels (x 16 frames) of the temporal form, rows of the text cross-attention form."""
+# ---- tile forms of the fused blocks and the feed-forward chain: what a tile holds, and whether the last one may be partly filled --------------------------
+# pixels (x 16 frames) of a clip; rows of a text's segment; rows of the GEMMs that read the feed-forward's intermediate; rows its LayerNorm + GEGLU kernels step by
+_TILE_UNITS = {"temporal": {320: 10, 640: 5}, "xattn": {320: 160, 640: 80}, "ff": 160, "ff_ln": 80}
+
+
+def _tile_units(C: int, kind: str) -> int:
+    """What a tile of form `kind` holds at width C."""
+    units = _TILE_UNITS[kind]
+    if isinstance(units, int):
+        return units
     assert C in (320, 640)
-    return (160 if C == 320 else 80) if xattn else (10 if C == 320 else 5)
+    return units[C]
+
+
+class TileForm(NamedTuple):
+    """`units` pixels or rows per tile; `any_rows`: any count >= 1, the last tile partly filled (the `_partial` entry points) -- else the count divides."""
+    units: int
+    any_rows: bool
+
+    def takes(self, n: int) -> bool:
+        return n >= 1 if self.any_rows else n % self.units == 0
+
+    def tiles(self, n: int) -> int:                         # (the ceiling: n / units where the count divides)
+        return -(-n // self.units)
+
+
+def _tile_form(kind: str, C: int, any_rows: bool) -> TileForm:
+    return TileForm(_tile_units(C, kind), any_rows)
+
+
+def _entry(whole: str, partial: bool):
+    """(name, function) in C of a launch entry point: `whole` or its partial-tile twin (`..._partial_bf16`, `fmc_linear_bf16_<form>_partial`)."""
+    name = whole if not partial else (whole[:-5] + "_partial_bf16" if whole.endswith("_bf16") else whole + "_partial")
+    return name, getattr(_lib.load(), name)
 
 
 def temporal_tile_count(n_clips: int, hw: int, C: int) -> int:
     """Tiles (= the grid before the persistent cap at C = 320) of `fmc_temporal_block_partial_bf16`: ceil(hw / 10 | 5) per clip."""
-    return n_clips * -(-hw // _tile_units(C, False))
+    return n_clips * _tile_form("temporal", C, True).tiles(hw)
 
 
 def temporal_tile(t: int, hw: int, C: int):
     """Tile t of the temporal form -> (clip, first pixel, valid pixels): the kernel's `tile_row0` / `tile_valid`."""
-    px = _tile_units(C, False)
+    px = _tile_units(C, "temporal")
     per_clip = -(-hw // px)
     clip, p0 = t // per_clip, (t % per_clip) * px
     return clip, p0, min(px, hw - p0)
@@ -1310,35 +1327,45 @@ def temporal_tile(t: int, hw: int, C: int):
 
 def xattn_tile_count(n_images: int, hw: int, images_per_text: int, C: int) -> int:
     """Tiles of `fmc_xattn_block320 | 640_partial_bf16`: a segment = the `images_per_text * hw` rows of one text, ceil(rows / 160 | 80) tiles each."""
-    return (n_images // images_per_text) * -(-(images_per_text * hw) // _tile_units(C, True))
+    return (n_images // images_per_text) * _tile_form("xattn", C, True).tiles(images_per_text * hw)
 
 
 def xattn_tile(t: int, seg_rows: int, C: int):
     """Tile t of the text cross-attention form -> (segment = text, first global row, valid rows); a tile never holds rows of two texts."""
-    rows = _tile_units(C, True)
+    rows = _tile_units(C, "xattn")
     per_seg = -(-seg_rows // rows)
     seg, r0 = t // per_seg, (t % per_seg) * rows
     return seg, seg * seg_rows + r0, min(rows, seg_rows - r0)
 
 
 def _on_gpu(t: torch.Tensor) -> bool:
-    """(its own function so that the host tests can exercise every other condition of the two predicates below on CPU tensors)"""
+    """(its own function so that the host tests can exercise every other condition of the partial-tile predicates below on CPU tensors)"""
     return t.is_cuda
+
+
+def _temporal_block_ok(h: torch.Tensor, heads: int, any_rows: bool) -> bool:
+    # (inherited, not derived, here and in `_xattn_block_ok`: the whole-tile predicate asks the tensor itself, the partial-tile one the hook above)
+    return ((_on_gpu(h) if any_rows else h.is_cuda) and h.dtype == torch.bfloat16 and h.ndim == 4 and h.is_contiguous() and h.shape[1] == 16 and heads == 8
+            and (h.shape[3] == 320 or (h.shape[3] == 640 and TEMPORAL_FUSED_640)) and _tile_form("temporal", h.shape[3], any_rows).takes(h.shape[2])
+            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled())
+
+
+def _xattn_block_ok(h: torch.Tensor, kv_tokens: int, heads: int, any_rows: bool) -> bool:
+    if not ((_on_gpu(h) if any_rows else h.is_cuda) and h.dtype == torch.bfloat16 and h.ndim == 3 and h.is_contiguous() and heads == 8 and 0 < kv_tokens <= 80
+            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
+        return False
+    C = h.shape[2]
+    return bool(((XATTN_FUSED_640 and C == 640) or (XATTN_FUSED_320 and C == 320)) and _tile_form("xattn", C, any_rows).takes(h.shape[1]))
 
 
 def temporal_block_partial_supported(h: torch.Tensor, heads: int) -> bool:
     """`temporal_block_supported` without the divisibility of hw: what `temporal_block(..., partial_tiles=True)` takes."""
-    return (_on_gpu(h) and h.dtype == torch.bfloat16 and h.ndim == 4 and h.is_contiguous() and h.shape[1] == 16 and heads == 8 and h.shape[2] >= 1
-            and (h.shape[3] == 320 or (h.shape[3] == 640 and TEMPORAL_FUSED_640))
-            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled())
+    return _temporal_block_ok(h, heads, any_rows=True)
 
 
 def xattn_block_partial_supported(h: torch.Tensor, kv_tokens: int, heads: int) -> bool:
     """`xattn_block_supported` without the divisibility of hw: what `xattn_block(..., partial_tiles=True)` takes."""
-    if not (_on_gpu(h) and h.dtype == torch.bfloat16 and h.ndim == 3 and h.is_contiguous() and heads == 8 and 0 < kv_tokens <= 80 and h.shape[1] >= 1
-            and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
-        return False
-    return (XATTN_FUSED_640 and h.shape[2] == 640) or (XATTN_FUSED_320 and h.shape[2] == 320)
+    return _xattn_block_ok(h, kv_tokens, heads, any_rows=True)
 
 
 GEGLU_DIRECT_640 = os.environ.get("FMC_GEGLU_DIRECT_640", "1") != "0"      # A/B switch: LayerNorm + GEGLU projection of the 20x32 level with the A operand resident
@@ -1402,32 +1429,27 @@ def geglu_ln_pipe(h: torch.Tensor, ln_gamma: torch.Tensor, ln_beta: torch.Tensor
     _dev(h, ln_gamma, ln_beta, w_packed, bias)
     C = h.shape[-1]
     M = h.numel() // C
-    if partial_tiles:
-        if blocked:          # ceil(M / 160) whole tiles; the tensor handed on is the [..., cff]-shaped head of that storage
-            out = torch.empty(ff_blocked_numel(M, cff), dtype=h.dtype, device=h.device)[:M * cff].view(*h.shape[:-1], cff)
-        else:
-            out = torch.empty(*h.shape[:-1], cff, dtype=h.dtype, device=h.device)
-        _log_call("geglu_direct", (M, 2 * cff, C, "partial"), 2.0 * M * 2 * cff * C)
-        _lib.check(_lib.load().fmc_geglu_pipe_ln_partial_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), float(ln_eps),
-                                                              w_packed.data_ptr(), _p(bias), M, cff, C, int(blocked), int(variant), _stream()),
-                   "fmc_geglu_pipe_ln_partial_bf16")
-        return out
-    out = torch.empty(*h.shape[:-1], cff, dtype=h.dtype, device=h.device)
-    _log_call("geglu_direct", (M, 2 * cff, C), 2.0 * M * 2 * cff * C)
-    _lib.check(_lib.load().fmc_geglu_pipe_ln_bf16(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), float(ln_eps), w_packed.data_ptr(),
-                                                  _p(bias), M, cff, C, int(blocked), int(variant), _stream()), "fmc_geglu_pipe_ln_bf16")
+    if partial_tiles and blocked:          # ceil(M / 160) whole tiles; the tensor handed on is the [..., cff]-shaped head of that storage
+        out = torch.empty(ff_blocked_numel(M, cff), dtype=h.dtype, device=h.device)[:M * cff].view(*h.shape[:-1], cff)
+    else:
+        out = torch.empty(*h.shape[:-1], cff, dtype=h.dtype, device=h.device)
+    _log_call("geglu_direct", (M, 2 * cff, C) + (("partial",) if partial_tiles else ()), 2.0 * M * 2 * cff * C)
+    name, fn = _entry("fmc_geglu_pipe_ln_bf16", partial_tiles)
+    _lib.check(fn(h.data_ptr(), out.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), float(ln_eps), w_packed.data_ptr(), _p(bias), M, cff, C, int(blocked),
+                  int(variant), _stream()), name)
     return out
 
 
 # ---- the feed-forward chain at any row count: partly filled last tile (csrc/geglu_pipe.hip, csrc/gemm_conv.hip: PARTIAL) --------------------------------
 # M is one flat row count: ceil(M / 160) tiles, only the last one ragged.  Taken by `FeedForward.forward_ln` with `PARTIAL_TILES` on.
-def ff_tile_count(M: int, rows: int = 160) -> int:
-    return -(-M // rows)
+def ff_tile_count(M: int, rows: int = _TILE_UNITS["ff"]) -> int:
+    return TileForm(rows, True).tiles(M)
 
 
 def ff_blocked_numel(M: int, K: int) -> int:
     """Elements of the tile-major intermediate: ceil(M / 160) WHOLE tiles of `[K / 32][160][32]`."""
-    return ff_tile_count(M) * 160 * K
+    form = _tile_form("ff", 0, True)
+    return form.tiles(M) * form.units * K
 
 
 def _ff_on_gpu(t: torch.Tensor) -> bool:
@@ -1436,10 +1458,8 @@ def _ff_on_gpu(t: torch.Tensor) -> bool:
 
 
 def geglu_pipe_partial_supported(M: int, cff: int, C: int, variant: int) -> bool:
-    """`fmc_geglu_pipe_partial_supported` (host arithmetic only; tests compare the two)."""
-    Mp = ff_tile_count(M) * 160
-    common = M > 0 and cff > 0 and cff % 128 == 0 and Mp * cff * 2 < (1 << 31) and 2 * cff * C * 2 < (1 << 31) and Mp * C * 2 < (1 << 31)
-    return bool(common and ((variant == 1 and C == 320) or (variant == 0 and C in (320, 640))))
+    """What `geglu_ln_pipe(..., partial_tiles=True)` takes of a shape: the rule is written once, in csrc/geglu_pipe.hip (`pipe_shape_ok`)."""
+    return bool(_lib.load().fmc_geglu_pipe_partial_supported(M, cff, C, variant))
 
 
 def geglu_pipe_partial_variant(C: int) -> int:
@@ -1447,39 +1467,62 @@ def geglu_pipe_partial_variant(C: int) -> int:
     return 1 if C == 320 else 0
 
 
-def geglu_ln_partial_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
-    """`geglu_ln_direct_ok` without the divisibility of M: what `geglu_ln_pipe(..., partial_tiles=True)` takes (both levels on the pipe kernel)."""
+def _geglu_ln_ok(h: torch.Tensor, weight: torch.Tensor, any_rows: bool) -> bool:
     C = h.shape[-1]
     M = h.numel() // max(C, 1)
-    if not (_ff_on_gpu(h) and h.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and h.is_contiguous() and weight.shape[1] == C
-            and M >= 1 and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled() and GEGLU_PIPE):
+    cff = weight.shape[0] // 2
+    # (inherited, not derived: the whole-tile predicate asks the tensor itself, the partial-tile one this family's own hook)
+    if not ((_ff_on_gpu(h) if any_rows else h.is_cuda) and h.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and h.is_contiguous() and weight.shape[1] == C
+            and _tile_form("ff_ln", C, any_rows).takes(M) and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
         return False
     if not ((GEGLU_DIRECT_640 and C == 640) or (GEGLU_DIRECT_320 and C == 320)):
         return False
-    return geglu_pipe_partial_supported(M, weight.shape[0] // 2, C, geglu_pipe_partial_variant(C))
+    # inherited, not derived: whole tiles ask for the direct kernels' chunks of cff and leave `GEGLU_PIPE` to `geglu_ln_pipe_ok`; a partly filled tile exists
+    # on the pipe kernel alone, so its switch and its shape rule (cff % 128, the padded sizes) decide
+    if any_rows:
+        return bool(GEGLU_PIPE and geglu_pipe_partial_supported(M, cff, C, geglu_pipe_partial_variant(C)))
+    return cff % (320 if C == 640 else 160) == 0
 
 
-def geglu_direct_blocked_partial_ok(h: torch.Tensor, w2: torch.Tensor, residual) -> bool:
-    """`geglu_direct_blocked_ok` without `M % 160 == 0`: ceil(M / 160) tiles, more of them than CUs, the padded intermediate below 2 GiB."""
+def geglu_ln_partial_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
+    """`geglu_ln_direct_ok` without the divisibility of M: what `geglu_ln_pipe(..., partial_tiles=True)` takes (both levels on the pipe kernel)."""
+    return _geglu_ln_ok(h, weight, any_rows=True)
+
+
+def _geglu_blocked_ok(h: torch.Tensor, w2: torch.Tensor, residual, any_rows: bool) -> bool:
     C = h.shape[-1]
     M = h.numel() // C
     N2, Cff = w2.shape
-    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and M >= 1 and N2 % 320 == 0 and Cff % 64 == 0
-            and ff_tile_count(M) * (N2 // 320) > _cus(h.device) and ff_blocked_numel(M, Cff) * 2 < (1 << 31) and N2 * Cff * 2 < (1 << 31)
+    form = _tile_form("ff", C, any_rows)
+    # inherited, not derived: Cff % 32 on whole tiles, Cff % 64 and the weight's own 2 GiB bound on partly filled ones.  (The intermediate's bound is the
+    # padded count in both: on whole tiles that IS M * Cff)
+    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and form.takes(M) and N2 % 320 == 0 and Cff % (64 if any_rows else 32) == 0
+            and form.tiles(M) * (N2 // 320) > _cus(h.device) and ff_blocked_numel(M, Cff) * 2 < (1 << 31) and (not any_rows or N2 * Cff * 2 < (1 << 31))
             and w2.dtype == torch.bfloat16 and w2.is_contiguous()
             and (residual is None or (residual.is_contiguous() and residual.dtype == h.dtype)) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
 
 
-def ff_tail_partial_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor]) -> bool:
-    """`ff_tail_ok` without `M % 160 == 0`: at least as many tiles (ceil) as CUs, the padded intermediate below 2 GiB."""
+def geglu_direct_blocked_partial_ok(h: torch.Tensor, w2: torch.Tensor, residual) -> bool:
+    """`geglu_direct_blocked_ok` without `M % 160 == 0`: ceil(M / 160) tiles, more of them than CUs, the padded intermediate below 2 GiB."""
+    return _geglu_blocked_ok(h, w2, residual, any_rows=True)
+
+
+def _ff_tail_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor], any_rows: bool) -> bool:
     C = h.shape[-1]
     M = h.numel() // C
+    form = _tile_form("ff", C, any_rows)
+    # inherited, not derived: `>=` against the CU count where the blocked pair asks `>`; the folded weight's own 2 GiB bound on partly filled tiles only
     return (FF_TAIL and not torch.is_grad_enabled() and h.dtype == torch.bfloat16 and h.is_contiguous() and wp.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16
             and wp.ndim == 2 and wp.shape[1] == w2.shape[0] == C and wp.shape[0] % 320 == 0 and C % 64 == 0 and w2.shape[1] % 64 == 0
-            and M >= 1 and ff_tile_count(M) * (wp.shape[0] // 320) >= _cus(h.device) and ff_tile_count(M) * 160 * max(w2.shape[1], C) * 2 < (1 << 31)
-            and wp.shape[0] * (w2.shape[1] + C) * 2 < (1 << 31)
+            and form.takes(M) and form.tiles(M) * (wp.shape[0] // 320) >= _cus(h.device) and ff_blocked_numel(M, max(w2.shape[1], C)) * 2 < (1 << 31)
+            and (not any_rows or wp.shape[0] * (w2.shape[1] + C) * 2 < (1 << 31))
             and tail_residual is not None and tail_residual.dtype == h.dtype and tail_residual.is_contiguous()
             and tail_residual.numel() == M * wp.shape[0] and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+
+
+def ff_tail_partial_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor]) -> bool:
+    """`ff_tail_ok` without `M % 160 == 0`: at least as many tiles (ceil) as CUs, the padded intermediate below 2 GiB."""
+    return _ff_tail_ok(h, w2, wp, tail_residual, any_rows=True)
 
 
 def _blocked_storage_ok(xb: torch.Tensor, M: int, K: int) -> bool:
@@ -1487,11 +1530,7 @@ def _blocked_storage_ok(xb: torch.Tensor, M: int, K: int) -> bool:
 
 
 def geglu_ln_direct_ok(h: torch.Tensor, weight: torch.Tensor) -> bool:
-    C = h.shape[-1]
-    if not (h.is_cuda and h.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and h.is_contiguous() and weight.shape[1] == C
-            and (h.numel() // C) % 80 == 0 and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
-        return False
-    return (GEGLU_DIRECT_640 and C == 640 and (weight.shape[0] // 2) % 320 == 0) or (GEGLU_DIRECT_320 and C == 320 and (weight.shape[0] // 2) % 160 == 0)
+    return _geglu_ln_ok(h, weight, any_rows=False)
 
 
 GEGLU_DIRECT_BLOCKED = os.environ.get("FMC_GEGLU_DIRECT_BLOCKED", "1") != "0"   # A/B switch: the level-0 feed-forward's intermediate tile-major (below)
@@ -1501,12 +1540,7 @@ def geglu_direct_blocked_ok(h: torch.Tensor, w2: torch.Tensor, residual) -> bool
     """Level 0 (C = 320): `geglu_ln_direct(..., blocked=True)` + `linear_from_blocked` -- the second GEMM (K = 1280, N = 320) streams a 210-MB operand in
     128-byte row pieces 2560 bytes apart when it is row-major; tile-major it requests contiguous 10-KiB blocks (113 -> 99 us isolated,
     tools/scratch/r05/bench_ffblk.py).  No gain measured at C = 640 (74.6 / 75.2 us), so only this level takes it."""
-    C = h.shape[-1]
-    M = h.numel() // C
-    N2, Cff = w2.shape
-    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and M % 160 == 0 and N2 % 320 == 0 and Cff % 32 == 0 and (M // 160) * (N2 // 320) > _cus(h.device)
-            and M * Cff * 2 < (1 << 31) and w2.dtype == torch.bfloat16 and w2.is_contiguous()
-            and (residual is None or (residual.is_contiguous() and residual.dtype == h.dtype)) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+    return _geglu_blocked_ok(h, w2, residual, any_rows=False)
 
 
 def geglu_ln_direct(h: torch.Tensor, ln_gamma: torch.Tensor, ln_beta: torch.Tensor, ln_eps: float, w_packed: torch.Tensor, bias: Optional[torch.Tensor],
@@ -2012,17 +2046,12 @@ def linear_from_blocked(xb: torch.Tensor, weight: torch.Tensor, bias, residual, 
         out = torch.empty(*xb.shape[:-1], N, dtype=xb.dtype, device=xb.device)
     assert out.is_contiguous() and out.numel() == M * N and out.dtype == xb.dtype
     wt = _w_tilemajor(weight) if W_TILEMAJOR else weight
-    if partial_tiles:
-        assert _blocked_storage_ok(xb, M, Kd), "linear_from_blocked: the tile-major operand does not own its padded storage"
-        _log_call("own_linear", (M, N, Kd, "from-blocked-partial", int(residual is not None)), 2.0 * M * N * Kd)
-        _lib.check(_lib.load().fmc_linear_bf16_ffblk_partial(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd,
-                                                             0 if residual is None else N, float(alpha), int(W_TILEMAJOR), _stream()),
-                   "fmc_linear_bf16_ffblk_partial")
-        return out
-    _log_call("own_linear", (M, N, Kd, "from-blocked", int(residual is not None)), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_ffblk(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd,
-                                                 0 if residual is None else N, float(alpha), 0, 1, 0, None, None, None, int(W_TILEMAJOR), _stream()),
-               "fmc_linear_bf16_ffblk")
+    assert not partial_tiles or _blocked_storage_ok(xb, M, Kd), "linear_from_blocked: the tile-major operand does not own its padded storage"
+    _log_call("own_linear", (M, N, Kd, "from-blocked-partial" if partial_tiles else "from-blocked", int(residual is not None)), 2.0 * M * N * Kd)
+    name, fn = _entry("fmc_linear_bf16_ffblk", partial_tiles)
+    # (the whole-tile entry point is the general blocked GEMM: no GEGLU, no LayerNorm epilogue -- the arguments the partial one does not have)
+    _lib.check(fn(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, 0 if residual is None else N, float(alpha),
+                  *(() if partial_tiles else (0, 1, 0, None, None, None)), int(W_TILEMAJOR), _stream()), name)
     return out
 
 
@@ -2032,13 +2061,7 @@ FF_TAIL = os.environ.get("FMC_FF_TAIL", "1") != "0"             # A/B switch: fe
 def ff_tail_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor]) -> bool:
     """`proj_out(ff2(g) + b2 + h) + bp + x` as ONE launch on the tile-major intermediate (`ff_tail`): the level-0 transformers, where both GEMMs are
     HBM passes (K = 1280 and K = 320 on 81 920 rows) -- the folded product reads g, h and x once and writes once, the block's output is never stored."""
-    C = h.shape[-1]
-    M = h.numel() // C
-    return (FF_TAIL and not torch.is_grad_enabled() and h.dtype == torch.bfloat16 and h.is_contiguous() and wp.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16
-            and wp.ndim == 2 and wp.shape[1] == w2.shape[0] == C and wp.shape[0] % 320 == 0 and C % 64 == 0 and w2.shape[1] % 64 == 0
-            and M % 160 == 0 and (M // 160) * (wp.shape[0] // 320) >= _cus(h.device) and M * max(w2.shape[1], C) * 2 < (1 << 31)
-            and tail_residual is not None and tail_residual.dtype == h.dtype and tail_residual.is_contiguous()
-            and tail_residual.numel() == M * wp.shape[0] and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+    return _ff_tail_ok(h, w2, wp, tail_residual, any_rows=False)
 
 
 def fold_ff_tail(w2: torch.Tensor, b2: Optional[torch.Tensor], wp: torch.Tensor, bp: Optional[torch.Tensor]):
@@ -2066,23 +2089,16 @@ def ff_tail(mid_blocked: torch.Tensor, h: torch.Tensor, w_cat: torch.Tensor, b_c
     M = h.numel() // C
     assert mid_blocked.numel() == M * (Kd - C) and tail_residual.numel() == M * N
     out = torch.empty_like(tail_residual)
-    if partial_tiles:
-        assert _blocked_storage_ok(mid_blocked, M, Kd - C), "ff_tail: the tile-major operand does not own its padded storage"
-        wt = _w_tilemajor(w_cat) if W_TILEMAJOR else w_cat
-        _log_call("own_linear", (M, N, Kd, "ff-tail-partial", 1), 2.0 * M * N * Kd)
-        _lib.check(_lib.load().fmc_linear_bf16_fftail_partial(mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(),
-                                                              out.data_ptr(), M, N, Kd, Kd - C, C, N, None, 0, int(W_TILEMAJOR), _stream()),
-                   "fmc_linear_bf16_fftail_partial")
-        return out
+    assert not partial_tiles or _blocked_storage_ok(mid_blocked, M, Kd - C), "ff_tail: the tile-major operand does not own its padded storage"
     part = None
-    if gn_hw and gn_emit_ok(M, N, Kd, gn_hw, h.dtype):
+    if gn_hw and not partial_tiles and gn_emit_ok(M, N, Kd, gn_hw, h.dtype):
         part = torch.empty(M // gn_hw, gn_hw // 160, 32, 2, dtype=torch.float32, device=h.device)
         gn_epilogue_calls["emitted"] += 1
     wt = _w_tilemajor(w_cat) if W_TILEMAJOR else w_cat
-    _log_call("own_linear", (M, N, Kd, "ff-tail", 1), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_fftail(mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(), out.data_ptr(),
-                                                  M, N, Kd, Kd - C, C, N, _p(part), int(gn_hw if part is not None else 0), int(W_TILEMAJOR), _stream()),
-               "fmc_linear_bf16_fftail")
+    _log_call("own_linear", (M, N, Kd, "ff-tail-partial" if partial_tiles else "ff-tail", 1), 2.0 * M * N * Kd)
+    name, fn = _entry("fmc_linear_bf16_fftail", partial_tiles)
+    _lib.check(fn(mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(), out.data_ptr(), M, N, Kd, Kd - C,
+                  C, N, _p(part), int(gn_hw if part is not None else 0), int(W_TILEMAJOR), _stream()), name)
     if part is not None:
         out._fmc_gn = (part, N)
     return out

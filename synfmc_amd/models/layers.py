@@ -15,7 +15,7 @@ from __future__ import annotations
 import os
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -824,6 +824,16 @@ class GEGLU(nn.Module):
         return K.geglu(self.proj(K.resolve_pending_ln(hidden_states)))
 
 
+class FFRoute(NamedTuple):
+    """One run of `FeedForward.forward_ln`.  `kernel`: "pipe" (csrc/geglu_pipe.hip, `variant` 0 = 80-row / 1 = 160-row form) or "direct" (`variant` -1);
+    `partial`: the partial-tile entry points; `blocked`: the intermediate tile-major; `tail`: output projection + the caller's proj_out as one launch."""
+    kernel: str
+    variant: int
+    partial: bool
+    blocked: bool
+    tail: bool
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, dim_out=None, mult=4, dropout=0.0, activation_fn="geglu", final_dropout=False):
         super().__init__()
@@ -839,35 +849,21 @@ class FeedForward(nn.Module):
         return derived(self, "_tail_fold", [out.weight, out.bias, wp, bp], lambda: K.fold_ff_tail(out.weight, out.bias, wp, bp))
 
     def ln_partial_route(self, h) -> bool:
-        """A row count that does not fill whole tiles, `hip_ops.PARTIAL_TILES` on: `forward_ln` normalises `h` itself on the partial-tile entry points
-        (so the producer of `h` leaves no row statistics).  Never where the whole-tile route exists."""
+        """A row count that does not fill whole tiles, `hip_ops.PARTIAL_TILES` on: `forward_ln` runs on the partial-tile entry points.  Never where the whole-tile
+        route exists; C = 640 only with `hip_ops.GEGLU_PIPE_640`, as on whole tiles (the 80-row form measured level with the un-fused pair, profiles/partial_tiles.md 10)."""
         w = self.net[0].proj.weight
-        # (C = 640: only with `hip_ops.GEGLU_PIPE_640`, as on whole tiles -- the 80-row form measured level with the un-fused pair there,
-        #  profiles/partial_tiles.md section 10)
         return bool(K.PARTIAL_TILES and not torch.is_grad_enabled() and (h.shape[-1] == 320 or K.GEGLU_PIPE_640)
                     and not K.geglu_ln_direct_ok(h, w) and K.geglu_ln_partial_ok(h, w))
 
-    def _forward_ln_partial(self, h, norm, residual, tail):
-        """`forward_ln` on a partly filled last tile: the pipe kernel, then `ff_tail` where the whole-tile route would use it, else the ordinary
-        output projection."""
-        proj, out = self.net[0], self.net[2]
-        w = proj.proj.weight
-        var = K.geglu_pipe_partial_variant(h.shape[-1])
-        frag = derived(self, "_geglu_frag_partial", [w], lambda: K.pack_geglu_frag(w, 16 if var == 1 else 32), extra=(var,))
-        # the tile-major intermediate only in front of `ff_tail`: `linear_from_blocked(..., partial_tiles=True)` measured slower than the ordinary output
-        # projection on the row-major intermediate at these row counts (profiles/partial_tiles.md section 10) and is not routed to
-        folded = (tail is not None and residual is h and K.geglu_direct_blocked_partial_ok(h, out.weight, residual)
-                  and K.ff_tail_partial_ok(h, out.weight, tail[0], tail[2]))
-        mid = K.geglu_ln_pipe(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=folded,
-                              variant=var, partial_tiles=True)
-        if folded:
-            wc, bc = self._tail_weights(tail[0], tail[1])
-            # (`tail[3]`, gn_hw, is not passed on: the partial tail leaves no GroupNorm partial sums, and the consumer without an `_fmc_gn` tag computes its
-            #  own statistics, as it does wherever `hip_ops.gn_emit_ok` fails)
-            y = K.ff_tail(mid, h, wc, bc, tail[2], partial_tiles=True)
-            y._fmc_tail = True
-            return y
-        return out(mid, residual=residual)
+    def normalises_input(self, h, partial_tiles: bool = True) -> bool:
+        """`forward_ln` normalises `h` itself, so its producer must leave no row statistics.  `partial_tiles=False`: on whole tiles alone (inherited:
+        `BasicTransformerBlock.forward` plans the un-fused attention's LayerNorm epilogue by that; statistics on `h` then keep it off the partial route)."""
+        return bool(K.geglu_ln_direct_ok(h, self.net[0].proj.weight) or (partial_tiles and self.ln_partial_route(h)))
+
+    def wants_row_stats(self, h, partial: bool) -> bool:
+        """The fused attention block that produces `h` leaves the (mean, rstd) of its rows for the GEGLU projection's LayerNorm-in-GEMM: the 40x64 level, while
+        the feed-forward does not normalise itself; behind a partial-tile launch only where the consuming GEMM takes them at a ragged row count (`hip_ops.lnc_ok`)."""
+        return bool(h.shape[-1] == 320 and not self.normalises_input(h) and (not partial or K.lnc_ok(h, self.net[0].proj.weight)))
 
     def mxfp8_route(self, h, residual) -> bool:
         """`hip_ops.FP8_FF` on: the feed-forward runs on the block-scaled e4m3 GEMMs (csrc/gemm_mxfp8.hip).  Inference on bf16 storage only: marked-trainable
@@ -888,35 +884,53 @@ class FeedForward(nn.Module):
         y = K.linear_mxfp8(mq, ms, w2q, w2s, out.bias, None if residual is None else residual.reshape(-1, out.weight.shape[0]))
         return y.view(*h.shape[:-1], out.weight.shape[0])
 
-    def forward_ln(self, h, norm, residual, tail=None):
-        """`ff(norm(h)) + residual` with LayerNorm + GEGLU projection as one launch where `hip_ops.geglu_ln_direct` exists (the 20x32 level), else None.
-        `tail = (W_p, b_p, x, gn_hw)`: the caller's next op is `proj_out(.) + x` -- where `hip_ops.ff_tail_ok` holds the result is THAT (tagged `_fmc_tail`)."""
-        proj, out = self.net[0], self.net[2]
-        w = proj.proj.weight
-        pending = getattr(h, "_fmc_pending_add", None) is not None or getattr(h, "_fmc_ln", None) is not None \
-            or getattr(h, "_fmc_pending_ln", None) is not None
-        if K.FP8_FF and not pending and not torch.is_grad_enabled() and self.mxfp8_route(h, residual):
-            return self._forward_ln_mxfp8(h, norm, residual)
-        if not pending and self.ln_partial_route(h):
-            return self._forward_ln_partial(h, norm, residual, tail)
-        if not K.geglu_ln_direct_ok(h, w) or pending:
+    def ln_route(self, h, residual, tail):
+        """How `forward_ln` runs: "mxfp8", an `FFRoute`, or None (the caller's un-fused chain).  In this order: the MXFP8 chain (`hip_ops.FP8_FF`), the
+        partial-tile route where the whole-tile one does not exist, the whole-tile route."""
+        out, w = self.net[2], self.net[0].proj.weight
+        if getattr(h, "_fmc_pending_add", None) is not None or getattr(h, "_fmc_ln", None) is not None or getattr(h, "_fmc_pending_ln", None) is not None:
+            return None                                     # (somebody else normalises)
+        if K.FP8_FF and not torch.is_grad_enabled() and self.mxfp8_route(h, residual):
+            return "mxfp8"
+        C = h.shape[-1]
+        foldable = tail is not None and residual is h
+        if self.ln_partial_route(h):
+            # (tile-major only in front of `ff_tail`: `linear_from_blocked(..., partial_tiles=True)` measured slower than the ordinary output projection on
+            #  the row-major intermediate at these row counts, profiles/partial_tiles.md section 10, and is not routed to)
+            folded = foldable and K.geglu_direct_blocked_partial_ok(h, out.weight, residual) and K.ff_tail_partial_ok(h, out.weight, tail[0], tail[2])
+            return FFRoute("pipe", K.geglu_pipe_partial_variant(C), True, folded, folded)
+        if not K.geglu_ln_direct_ok(h, w):
             return None
-        M = h.numel() // h.shape[-1]
-        pipe = K.geglu_ln_pipe_ok(h, w) and (h.shape[-1] == 320 or K.GEGLU_PIPE_640)
-        var = K.geglu_pipe_variant(M, h.shape[-1]) if pipe else -1
-        frag = derived(self, "_geglu_frag", [w], lambda: K.pack_geglu_frag(w, 16 if var == 1 else 32) if pipe else K.pack_geglu_frag80(w), extra=(var,))
+        pipe = K.geglu_ln_pipe_ok(h, w) and (C == 320 or K.GEGLU_PIPE_640)
         blocked = K.geglu_direct_blocked_ok(h, out.weight, residual)
-        if pipe:      # the gate in the shadow of the next chunk's MFMAs (csrc/geglu_pipe.hip, round 6)
-            mid = K.geglu_ln_pipe(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=blocked,
-                                  variant=var)
+        return FFRoute("pipe" if pipe else "direct", K.geglu_pipe_variant(h.numel() // C, C) if pipe else -1, False, blocked,
+                       blocked and foldable and K.ff_tail_ok(h, out.weight, tail[0], tail[2]))
+
+    def forward_ln(self, h, norm, residual, tail=None):
+        """`ff(norm(h)) + residual` with LayerNorm + GEGLU projection as one launch where `ln_route` finds one (the 20x32 and 40x64 levels), else None.
+        `tail = (W_p, b_p, x, gn_hw)`: the caller's next op is `proj_out(.) + x` -- where the route says so the result is THAT (tagged `_fmc_tail`)."""
+        route = self.ln_route(h, residual, tail)
+        if route is None:
+            return None
+        if route == "mxfp8":
+            return self._forward_ln_mxfp8(h, norm, residual)
+        proj, out = self.net[0], self.net[2]
+        w, var = proj.proj.weight, route.variant
+        # (two cache slots, as before: a model that meets whole and ragged row counts in turn keeps both packs instead of rebuilding one per call)
+        frag = derived(self, "_geglu_frag_partial" if route.partial else "_geglu_frag", [w],
+                       lambda: K.pack_geglu_frag(w, 16 if var == 1 else 32) if route.kernel == "pipe" else K.pack_geglu_frag80(w), extra=(var,))
+        ln = (h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2)
+        if route.kernel == "pipe":      # the gate in the shadow of the next chunk's MFMAs (csrc/geglu_pipe.hip, round 6)
+            mid = K.geglu_ln_pipe(*ln, blocked=route.blocked, variant=var, partial_tiles=route.partial)
         else:
-            mid = K.geglu_ln_direct(h, f32_param(norm, "weight"), f32_param(norm, "bias"), norm.eps, frag, proj.proj.bias, w.shape[0] // 2, blocked=blocked)
-        if blocked and tail is not None and residual is h and K.ff_tail_ok(h, out.weight, tail[0], tail[2]):
+            mid = K.geglu_ln_direct(*ln, blocked=route.blocked)
+        if route.tail:
             wc, bc = self._tail_weights(tail[0], tail[1])
-            y = K.ff_tail(mid, h, wc, bc, tail[2], tail[3])
+            # (a partial tail leaves no GroupNorm partial sums: the consumer without an `_fmc_gn` tag computes its own, as wherever `hip_ops.gn_emit_ok` fails)
+            y = K.ff_tail(mid, h, wc, bc, tail[2], 0 if route.partial else tail[3], partial_tiles=route.partial)
             y._fmc_tail = True
             return y
-        if blocked:
+        if route.blocked:
             return K.linear_from_blocked(mid, out.weight, out.bias, residual)
         return out(mid, residual=residual)
 
@@ -986,17 +1000,14 @@ class BasicTransformerBlock(nn.Module):
         h = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
         kv, frag = attn.text_kv(encoder_hidden_states, w_kv)           # (once per clip, not per step)
         per_text = h.shape[0] // encoder_hidden_states.shape[0]
-        if h.shape[2] == 640:
-            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
-        # the 40x64 level: the feed-forward's norm3 is applied by its GEGLU projection from the row statistics this launch leaves
-        # (the feed-forward normalises its input itself: no statistics to leave; nor where a ragged row count keeps its GEMM from taking them, `hip_ops.lnc_ok`)
-        # (nor where the feed-forward takes the partial-tile route, which normalises too)
-        if K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) or self.ff.ln_partial_route(h) or (partial and not K.lnc_ok(h, self.ff.net[0].proj.weight)):
-            return K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, frag=frag, partial_tiles=partial)
-        out, stats = K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps,
-                                   frag=frag, partial_tiles=partial)
-        K.ln_epilogue_calls["emitted"] += 1
-        out._fmc_ln = (stats, self.norm3._ln_key(None, 1, 1), True)
+        # the 40x64 level: the feed-forward's norm3 is applied by its GEGLU projection from the row statistics this launch leaves (`FeedForward.wants_row_stats`)
+        stats = self.ff.wants_row_stats(h, partial)
+        out = K.xattn_block(h, gc, bc, self.norm2.eps, wq_p, kv, wo_p, attn.to_out[0].bias, attn.scale, per_text, stats_eps=self.norm3.eps if stats else None,
+                            frag=frag, partial_tiles=partial)
+        if stats:
+            out, row_stats = out
+            K.ln_epilogue_calls["emitted"] += 1
+            out._fmc_ln = (row_stats, self.norm3._ln_key(None, 1, 1), True)
         return out
 
     def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None,
@@ -1032,7 +1043,7 @@ class BasicTransformerBlock(nn.Module):
         if fuse2:                                   # (the fused block normalises its input itself and wants it materialised)
             self.attn1.__dict__["_lazy_res"] = False
             self.attn1.__dict__["_next_ln"] = None
-        ff_direct = not torch.is_grad_enabled() and hidden_states.ndim == 3 and K.geglu_ln_direct_ok(hidden_states, self.ff.net[0].proj.weight)
+        ff_direct = not torch.is_grad_enabled() and hidden_states.ndim == 3 and self.ff.normalises_input(hidden_states, partial_tiles=False)
         if fuse2:
             pass
         elif self.attn2 is not None:

@@ -144,42 +144,47 @@ class TemporalTransformerBlock(nn.Module):
         self.ff_norm = LayerNorm(dim)
 
     # ---- the fused attention block (`fmc_temporal_block_bf16`, round 4) -------------------------------------------------------------------
-    def fused_blocks_ok(self, hidden_states, attention_mask, cross_attention_kwargs, supported=None) -> bool:
-        """Every attention block of this transformer block can run as ONE launch each (LayerNorm + pe -> [Camera-Adapter merge] -> q | k | v ->
+    def fused_route(self, hidden_states, attention_mask, cross_attention_kwargs) -> Optional[str]:
+        """"whole": every attention block of this transformer block can run as ONE launch each (LayerNorm + pe -> [Camera-Adapter merge] -> q | k | v ->
         attention over the frames -> out-projection + residual): inference, bf16 `[B, 16, P, 320]` tokens with P % 10 == 0 or `[B, 16, P, 640]` with P % 5 == 0, 8 heads, plain /
-        Camera-Adapter / frozen-LoRA processors, nothing applied after the output projection.  Anything else keeps the un-fused chain.
-        `supported`: the shape predicate (default `hip_ops.temporal_block_supported`: whole tiles; see `fused_blocks_partial_ok`)."""
-        supported = K.temporal_block_supported if supported is None else supported
+        Camera-Adapter / frozen-LoRA processors, nothing applied after the output projection.  "partial": the same but for P % 10 (P % 5), which the
+        partial-tile entry point does not ask for (`hip_ops.temporal_block(..., partial_tiles=True)`; `forward` takes it only with `hip_ops.PARTIAL_TILES` on).
+        None: anything else keeps the un-fused chain."""
+        route = "whole"
         if not TEMPORAL_FUSED or attention_mask is not None or hidden_states.ndim != 4:
-            return False
+            return None
         for blk in self.attention_blocks:
             proc = blk.processor
             if not isinstance(proc, (AttnProcessor, LoRAAttnProcessor, PoseAdaptorAttnProcessor, LORAPoseAdaptorAttnProcessor)):
-                return False
-            if not supported(hidden_states, blk.heads) or blk.inner_dim != hidden_states.shape[-1]:
-                return False
+                return None
+            if route == "whole" and not K.temporal_block_supported(hidden_states, blk.heads):
+                route = "partial"
+            if (route == "partial" and not K.temporal_block_partial_supported(hidden_states, blk.heads)) or blk.inner_dim != hidden_states.shape[-1]:
+                return None
             if (blk.residual_connection or blk.rescale_output_factor != 1.0 or blk.__dict__.get("_fp8_scales") is not None
                     or blk.to_q.weight.dtype != torch.bfloat16 or getattr(blk, "is_cross", False)):
-                return False
+                return None
             if isinstance(proc, (PoseAdaptorAttnProcessor, LORAPoseAdaptorAttnProcessor)):
                 pf = cross_attention_kwargs.get("pose_feature")
                 if pf is None or not (proc.query_condition and proc.key_value_condition) or proc.merge_wb(hidden_states)[0].dtype != torch.bfloat16:
-                    return False
+                    return None
                 # (what the un-fused `_merge` falls back on -- a pose feature of another dtype or shape -- must fall back here too)
                 if pf.dtype != torch.bfloat16 or not K._on_gpu(pf):
-                    return False
+                    return None
                 if pf.ndim == 5:
                     b, c, f, hh, ww = pf.shape
                     if (b, f, hh * ww, c) != tuple(hidden_states.shape):
-                        return False
+                        return None
                 elif tuple(pf.shape) != tuple(hidden_states.shape):
-                    return False
-        return True
+                    return None
+        return route
+
+    def fused_blocks_ok(self, hidden_states, attention_mask, cross_attention_kwargs) -> bool:
+        return self.fused_route(hidden_states, attention_mask, cross_attention_kwargs) == "whole"
 
     def fused_blocks_partial_ok(self, hidden_states, attention_mask, cross_attention_kwargs) -> bool:
-        """`fused_blocks_ok` for any number of pixels P >= 1: the conditions are the same but for P % 10 (P % 5), which the partial-tile entry point
-        does not ask for (`hip_ops.temporal_block(..., partial_tiles=True)`).  `forward` asks this only with `hip_ops.PARTIAL_TILES` on."""
-        return self.fused_blocks_ok(hidden_states, attention_mask, cross_attention_kwargs, K.temporal_block_partial_supported)
+        """(what the partial-tile entry point takes: whole tiles too)"""
+        return self.fused_route(hidden_states, attention_mask, cross_attention_kwargs) is not None
 
     def _fused_constants(self, i, frames):
         """(gamma fp32, beta + pe rows fp32 `[frames, C]`) of attention block i, cached on the block."""
@@ -210,7 +215,7 @@ class TemporalTransformerBlock(nn.Module):
             return K._w_tilemajor(wm)
         return derived(proc, "_fused_wm", [wm], lambda: K.pack_w_frag80(wm))
 
-    def _forward_fused(self, hidden_states, cross_attention_kwargs, tail=None, partial=False):
+    def _forward_fused(self, hidden_states, cross_attention_kwargs, tail, partial):
         frames = hidden_states.shape[1]
         h = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
         n_blocks = len(self.attention_blocks)
@@ -235,10 +240,8 @@ class TemporalTransformerBlock(nn.Module):
                 assert pose.shape == h.shape, "pose_feature does not match the hidden states"
                 wm, bm = proc.merge_wb(h)               # (the bf16 shadows of marked fp32 masters)
                 kw = dict(w_merge_tm=self._merge_packed(proc, wm), pose_term=proc._pose_term(pose, wm, bm, s), merge_scale=s)
-            # (row statistics for the feed-forward's LayerNorm-in-GEMM: the 40x64 level, and only while the feed-forward does not normalise its input itself)
-            last = i == n_blocks - 1 and h.shape[-1] == 320 and not K.geglu_ln_direct_ok(h, self.ff.net[0].proj.weight) and not self.ff.ln_partial_route(h)
-            if partial and last:                        # (a ragged row count: only where the consuming GEMM takes the statistics, `hip_ops.lnc_ok`)
-                last = K.lnc_ok(h, self.ff.net[0].proj.weight)
+            # (row statistics for the feed-forward's LayerNorm-in-GEMM: `FeedForward.wants_row_stats`)
+            last = i == n_blocks - 1 and self.ff.wants_row_stats(h, partial)
             out = K.temporal_block(h, gamma, bpe, self.norms[i].eps, w_qkv, w_o, attn.to_out[0].bias, attn.scale,
                                    stats_eps=self.ff_norm.eps if last else None, partial_tiles=partial, **kw)
             h, stats = out if last else (out, None)
@@ -255,11 +258,10 @@ class TemporalTransformerBlock(nn.Module):
 
     def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None,
                 cross_attention_kwargs: Dict[str, Any] = {}, tail=None):
-        if not torch.is_grad_enabled() and self.fused_blocks_ok(hidden_states, attention_mask, cross_attention_kwargs):
-            return self._forward_fused(hidden_states, cross_attention_kwargs, tail)
-        # a feature map that does not fill whole tiles: the same launches with a partly filled last tile, behind `hip_ops.PARTIAL_TILES` (default off)
-        if K.PARTIAL_TILES and not torch.is_grad_enabled() and self.fused_blocks_partial_ok(hidden_states, attention_mask, cross_attention_kwargs):
-            return self._forward_fused(hidden_states, cross_attention_kwargs, tail, partial=True)
+        # (a feature map that does not fill whole tiles: the same launches with a partly filled last tile, behind `hip_ops.PARTIAL_TILES`, default off)
+        route = None if torch.is_grad_enabled() else self.fused_route(hidden_states, attention_mask, cross_attention_kwargs)
+        if route == "whole" or (route == "partial" and K.PARTIAL_TILES):
+            return self._forward_fused(hidden_states, cross_attention_kwargs, tail, route == "partial")
         if hidden_states.ndim == 4:
             frames, inner = hidden_states.shape[1], hidden_states.shape[2]
         else:

@@ -17,6 +17,7 @@ import torch
 from tests import edge_guard_common as EG
 from tests import fake_kernels
 from tests import ff_partial_common as FFC
+from tests.fused_host_surface_common import claims_gpu
 
 
 @pytest.fixture()
@@ -132,13 +133,7 @@ class _Calls:
         monkeypatch.setattr(K, "_ff_on_gpu", lambda t: True)
         monkeypatch.setattr(K, "_cus", lambda device: cus)
 
-        def direct_ok(h, weight):        # `hip_ops.geglu_ln_direct_ok` without `h.is_cuda` (the predicate itself is left as it is)
-            C = h.shape[-1]
-            if not (h.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and h.is_contiguous() and weight.shape[1] == C
-                    and (h.numel() // C) % 80 == 0 and h.numel() * 2 < (1 << 31) and not torch.is_grad_enabled()):
-                return False
-            return (K.GEGLU_DIRECT_640 and C == 640 and (weight.shape[0] // 2) % 320 == 0) or (K.GEGLU_DIRECT_320 and C == 320 and (weight.shape[0] // 2) % 160 == 0)
-        monkeypatch.setattr(K, "geglu_ln_direct_ok", direct_ok)
+        monkeypatch.setattr(K, "geglu_ln_direct_ok", claims_gpu(K.geglu_ln_direct_ok))   # (the whole-tile predicate asks the tensor, not a hook)
 
         def pipe(h, g, b, eps, frag, bias, cff, blocked=False, variant=0, partial_tiles=False):
             self.log.append(("geglu_ln_pipe", partial_tiles, blocked, variant))
