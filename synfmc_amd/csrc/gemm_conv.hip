@@ -2822,16 +2822,62 @@ void launch_gemm_k320(GemmParams& P, hipStream_t st) {
     }
 }
 
-// tile 16: plain grid only (whole rounds are the point); N must be a multiple of 320 (GEGLU: weight rows per 16 = [8 value | 8 gate])
-bool gemm160_ok(const GemmParams& P) {
-    return P.N % 320 == 0 && !P.sk && (!P.a2 || P.a_blocked);   // (split_k > 1: plain epilogue only -- set_split_k has checked; a2: the persistent form's A2 variant, linear_impl has checked)
+// ---- tile 16 (160 x 320 tiles) and its persistent form gemm160p_kernel<EPI, 5, ...>: the grid, the LDS and what a shape must be, each stated once ----
+constexpr int64_t GIB2 = (int64_t)1 << 31;                                   // an operand's bytes stay below this: 32-bit offsets in the buffer descriptors
+inline int persistent_cus() { return fmc_cu_count() & ~7; }                  // the grid of the persistent kernels: whole groups of eight (one CU per XCD)
+bool a_rows_fit(int64_t M, int64_t ld, int64_t cols) { return ((M - 1) * ld + cols) * 2 < GIB2; }      // row-major A rows with a stride: up to the end of the last row
+bool weight_fits(int64_t rows, int64_t K) { return rows * K * 2 < GIB2; }                              // the weight [N, K] (per-image weights: all images' rows)
+enum class Rows { Whole, Ceil };                                             // M % 160 == 0 | any M, the last tile partly filled (the PARTIAL forms)
+// the tile-major intermediate [tiles][cols / 32][160][32]: exact, or padded to whole tiles (the last tile's blocks are read whole)
+int64_t blocked_bytes(int64_t M, int64_t cols, Rows rows) { return (rows == Rows::Ceil ? (M + 159) / 160 * 160 : M) * cols * 2; }
+enum class Tiles { MoreThanCus, AtLeastCus };                                // tiles against the grid: strictly more | also launches of exactly one round
+// does (M, N) take the persistent form?  FMC_G160_PERSIST, a grid of at least 8, N % 320, M % 160 (or any M), the tile count against the CUs
+bool g160_persistent_shape(int64_t M, int N, Tiles tiles, Rows rows) {
+    const int cus = persistent_cus();
+    if (g160_persist() == 0 || cus < 8 || N % 320 || (rows == Rows::Whole && M % 160)) return false;
+    const int64_t t = (M + 159) / 160 * (N / 320);
+    return tiles == Tiles::AtLeastCus ? t >= cus : t > cus;
 }
+
+constexpr size_t g160p_lds(int epi) {
+    const size_t ring = (size_t)3 * (160 + 320) * 32 * sizeof(bf16_t), dummies = 1024;     // three stages of 32-deep sub-tiles of both operands; the KiB of the requests past the last tile
+    // the epilogue's staging tile + the LayerNorm tables / GroupNorm scratch behind it: GEGLU [160][168] | plain [80][328] per pass
+    return ring + dummies + (epi == 1 ? (size_t)160 * 168 * 2 + 4096 : (size_t)80 * 328 * 2 + 5120);
+}
+void g160_tile_order(GemmParams& P, bool token, int bm = 160) {      // bm x 320 tiles (256 rows: tile 17)
+    P.tiles_m = (int)((P.M + bm - 1) / bm); P.tiles_n = P.N / 320; P.tap_outer = 0;
+    P.group_m = xcd_group_m(P, token, 32.0, 320, bm);
+}
+
+// the persistent launch: which form <EPI, 5, LN, LNC, A2, IMG, PARTIAL> (the argument checks have seen to what each one needs); the plain epilogue has them all:
+//   4 | 5: per-image weights / fp32 bias rows, without | with the LayerNorm statistics   6: two-segment reduction (tile-major first segment)
+//   1: this GEMM applies the LayerNorm of its input rows   2: LayerNorm output (N == 320, no GroupNorm partials)   3: LayerNorm statistics
+//   7 | 8: partly filled last tile (`partial`), one | two segments
+template <int EPI>
+void launch_gemm160p(GemmParams& P, hipStream_t st, bool partial = false) {
+    constexpr size_t lds = g160p_lds(EPI);
+    constexpr bool e0 = EPI == 0;
+    const int form = partial ? (P.a2 ? 8 : 7) : e0 && P.bias_img ? (P.ln_stats ? 5 : 4) : e0 && P.a2 ? 6 : P.lnc_stats ? 1 : e0 && P.ln_out ? 2 : e0 && P.ln_stats ? 3 : 0;
+    const dim3 grid((unsigned)persistent_cus()), block(512);
+    if (form == 0) fmc_launch<gemm160p_kernel<EPI, 5>>(grid, block, lds, st, P);
+    else if (form == 1) fmc_launch<gemm160p_kernel<EPI, 5, 0, 1>>(grid, block, lds, st, P);
+    if constexpr (EPI == 0) {
+        if (form == 2) fmc_launch<gemm160p_kernel<0, 5, 1>>(grid, block, lds, st, P);
+        else if (form == 3) fmc_launch<gemm160p_kernel<0, 5, 2>>(grid, block, lds, st, P);
+        else if (form == 4) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 1>>(grid, block, lds, st, P);
+        else if (form == 5) fmc_launch<gemm160p_kernel<0, 5, 2, 0, 0, 1>>(grid, block, lds, st, P);
+        else if (form == 6) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1>>(grid, block, lds, st, P);
+        else if (form == 7) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 0, 1>>(grid, block, lds, st, P);
+        else if (form == 8) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1, 0, 1>>(grid, block, lds, st, P);
+    }
+}
+
+// tile 16: plain grid only (whole rounds are the point); N must be a multiple of 320 (GEGLU: weight rows per 16 = [8 value | 8 gate])
+// (split_k > 1: plain epilogue only -- set_split_k has checked; a2: the persistent form's A2 variant, linear_impl has checked)
+bool gemm160_ok(const GemmParams& P) { return P.N % 320 == 0 && !P.sk && (!P.a2 || P.a_blocked); }
 template <int MODE, int EPI>
 void launch_gemm160(GemmParams& P, hipStream_t st) {
-    P.tiles_m = (int)((P.M + 159) / 160);
-    P.tiles_n = P.N / 320;
-    P.tap_outer = 0;
-    P.group_m = xcd_group_m(P, MODE == 0, 32.0, 320, 160);
+    g160_tile_order(P, MODE == 0);
     constexpr size_t lds = (size_t)5 * (160 + 320) * 32 * sizeof(bf16_t) + 1024;          // five sub-tile buffers + the dummies' KiB
     static_assert(lds >= (size_t)160 * 328 * 2 && lds >= (size_t)160 * 164 * 4, "epilogue staging fits the operand buffers");
     constexpr auto plain = gemm160_kernel<MODE, EPI>;
@@ -2845,30 +2891,10 @@ void launch_gemm160(GemmParams& P, hipStream_t st) {
     }
     if constexpr (MODE == 0) {
         // more tiles than CUs on a token projection: the persistent form (the next tile's operands stream in under this tile's epilogue)
-        const int persist = g160_persist();
-        const int cus = fmc_cu_count() & ~7;
         // (FMC_G160_PERSIST=2: also launches of exactly one round -- tiles == CUs, the level-1 N = 640 projections -- A/B switch)
         // (a tile-major A operand exists in the persistent form only: it also takes launches of exactly one round -- the two halves of a split feed-forward)
-        if (persist && !P.f32io && P.M % 160 == 0 && ((persist == 2 || P.a_blocked || P.bias_img) ? P.tiles_m * P.tiles_n >= cus : P.tiles_m * P.tiles_n > cus) && cus >= 8) {
-            constexpr size_t ldsp = (size_t)3 * (160 + 320) * 32 * sizeof(bf16_t) + 1024 + (EPI == 1 ? (size_t)160 * 168 * 2 + 4096 : (size_t)80 * 328 * 2 + 5120);
-            // which form <EPI, 5, LN, LNC, A2, IMG> (linear_impl has checked what each one needs); the plain epilogue (EPI 0) has them all:
-            //   4 | 5: per-image weights / fp32 bias rows, without | with the LayerNorm statistics   6: two-segment reduction (tile-major first segment)
-            //   1: this GEMM applies the LayerNorm of its input rows   2: LayerNorm output (N == 320, no GroupNorm partials)   3: LayerNorm statistics
-            // (the launches below stand in the order hipcc is to emit the instantiations in, kept as it was: see fmc_launch)
-            const bool e0 = EPI == 0;
-            const int form = e0 && P.bias_img ? (P.ln_stats ? 5 : 4) : e0 && P.a2 ? 6 : P.lnc_stats ? 1 : e0 && P.ln_out ? 2 : e0 && P.ln_stats ? 3 : 0;
-            const dim3 grid((unsigned)cus), block(512);
-            if (form == 0) fmc_launch<gemm160p_kernel<EPI, 5>>(grid, block, ldsp, st, P);
-            else if (form == 1) fmc_launch<gemm160p_kernel<EPI, 5, 0, 1>>(grid, block, ldsp, st, P);
-            if constexpr (EPI == 0) {
-                if (form == 2) fmc_launch<gemm160p_kernel<0, 5, 1>>(grid, block, ldsp, st, P);
-                else if (form == 3) fmc_launch<gemm160p_kernel<0, 5, 2>>(grid, block, ldsp, st, P);
-                else if (form == 4) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 1>>(grid, block, ldsp, st, P);
-                else if (form == 5) fmc_launch<gemm160p_kernel<0, 5, 2, 0, 0, 1>>(grid, block, ldsp, st, P);
-                else if (form == 6) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1>>(grid, block, ldsp, st, P);
-            }
-            return;
-        }
+        const Tiles tiles = g160_persist() == 2 || P.a_blocked || P.bias_img ? Tiles::AtLeastCus : Tiles::MoreThanCus;
+        if (!P.f32io && g160_persistent_shape(P.M, P.N, tiles, Rows::Whole)) { launch_gemm160p<EPI>(P, st); return; }
     }
     // (not reached with ln_out / ln_stats / lnc_stats set: linear_impl checks the persistent form's conditions)
     fmc_launch<plain>(dim3((unsigned)(P.tiles_m * P.tiles_n)), dim3(512), lds, st, P);
@@ -2876,17 +2902,14 @@ void launch_gemm160(GemmParams& P, hipStream_t st) {
 
 // tile 17: 256 x 320 tiles, persistent, GEGLU epilogue only (the feed-forward input projections: M % 256 == 0, more tiles than CUs)
 bool gemm256p_ok(const GemmParams& P) {
-    const int cus = fmc_cu_count() & ~7;
+    const int cus = persistent_cus();
     return P.N % 320 == 0 && P.M % 256 == 0 && !P.sk && !P.a2 && P.split_k == 1 && !P.f32io && cus >= 8 && (P.M / 256) * (P.N / 320) > cus;
 }
 void launch_gemm256p(GemmParams& P, hipStream_t st) {
-    P.tiles_m = (int)(P.M / 256);
-    P.tiles_n = P.N / 320;
-    P.tap_outer = 0;
-    P.group_m = xcd_group_m(P, true, 32.0, 320, 256);
+    g160_tile_order(P, true, 256);                          // (M % 256 == 0: gemm256p_ok)
     constexpr size_t ldsp = (size_t)3 * (256 + 320) * 32 * sizeof(bf16_t) + 1024 + (size_t)128 * 168 * 2;
     static_assert(ldsp <= 160 * 1024, "ring + staging fit the LDS");
-    fmc_launch<gemm160p_kernel<1, 8>>(dim3((unsigned)(fmc_cu_count() & ~7)), dim3(512), ldsp, st, P);
+    fmc_launch<gemm160p_kernel<1, 8>>(dim3((unsigned)persistent_cus()), dim3(512), ldsp, st, P);
 }
 
 bool gemm8_ok(GemmParams& P) {
@@ -2894,7 +2917,7 @@ bool gemm8_ok(GemmParams& P) {
     const int64_t a_elems = P.hw > 1 ? (P.ups == 1 ? (P.M / 4) * (int64_t)P.cin : P.M * (int64_t)P.cin * (P.ups == 2 ? 4 : 1))
                                      : (P.a2 && P.a_blocked ? P.M * (int64_t)P.ksplit : (P.M - 1) * P.lda + P.K);
     P.a_bytes = a_elems * 2;
-    return P.split_k == 1 && (!P.a2 || P.a_blocked) && P.a_bytes < ((int64_t)1 << 31) && (int64_t)P.N * P.K * 2 < ((int64_t)1 << 31);
+    return P.split_k == 1 && (!P.a2 || P.a_blocked) && P.a_bytes < GIB2 && weight_fits(P.N, P.K);
 }
 
 // tile arms (fmc_hip.h): geometry x k-tile depth x ring depth
@@ -2959,15 +2982,9 @@ void launch_gemm(GemmParams& P, int tile, hipStream_t st) {
 }
 
 int set_split_k(GemmParams& P, int split_k, void* workspace, int64_t workspace_bytes, bool plain_epilogue, const char* who) {
-    P.split_k = 1;
-    P.ws = nullptr;
-    P.sk = 0;
-    P.sk_t0 = 0;
-    P.sk_flags = nullptr;
-    P.sk_ws_bytes = 0;
+    P.split_k = 1;                                        // (P comes zero-initialised: no workspace, no stream-K until the code below says so)
     P.sk_hybrid = split_k == -2;
     P.sk_lock = split_k == -3 ? 1 : (split_k <= -16 ? -split_k - 16 : 0);      // k-lockstep split on the 8-phase arms (other arms: plain stream-K)
-    P.sk_lock_len = 0;
     if (split_k <= -16 && (P.sk_lock < 2 || P.sk_lock > 64)) FMC_FAIL(FMC_E_SHAPE, "%s: split_k %d (k-lockstep chunks = -split_k - 16 in 2..64)", who, split_k);
     if (split_k == -1 || split_k == -2 || split_k == -3 || split_k <= -16) {                // stream-K: [4096 B of flags (zero on entry and on return) | partials]
         if (!workspace || !fmc_aligned16(workspace) || workspace_bytes < 8192)
@@ -2988,231 +3005,263 @@ int set_split_k(GemmParams& P, int split_k, void* workspace, int64_t workspace_b
     return 0;
 }
 
-}  // namespace
+// What an entry point asks of the token GEMM: one named field per argument, in the order the designated initialisers of the entry points name them; an entry
+// point names the ones it has.  The defaults are what the entry points without the argument passed before this struct existed (tile 16, no split, alpha 1).
+struct LinearReq {
+    const char* who = "linear_bf16";                          // the entry point, for the messages that name it
+    const void *x = nullptr, *x2 = nullptr, *w = nullptr, *bias = nullptr, *residual = nullptr, *residual2 = nullptr;      // x2: segment [k_split, K) of the reduction
+    void *out = nullptr, *workspace = nullptr, *stream = nullptr;
+    void *gn_partials = nullptr, *ln_out = nullptr;           // producer of a GroupNorm: partial sums per 160-row tile; of a LayerNorm: its output, or (ln_stats) the rows' statistics
+    float* ln_stats = nullptr;
+    const float *ln_gamma = nullptr, *ln_beta = nullptr, *ln_pe = nullptr, *lnc_stats = nullptr, *lnc_c = nullptr, *lnc_bias = nullptr;     // lnc_*: consumer of a LayerNorm, applied in the epilogue
+    const float* bias_img = nullptr;                          // per-image weights and fp32 bias rows, images of img_rows rows
+    int64_t M = 0, ldx = 0, ldx2 = 0, ldres = 0, ldo = 0, workspace_bytes = 0;
+    int N = 0, K = 0, k_split = 0, epilogue = 0, tile = 16, split_k = 1, f32io = 0, gn_hw = 0, ln_pe_inner = 1, ln_pe_frames = 1, a_blocked = 0, out_blocked = 0, w_tilemajor = 0, img_rows = 0;
+    float alpha = 1.f, ln_eps = 0.f;
+};
 
-static int linear_impl(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                       int N, int K, int64_t ldx, int64_t ldres, int64_t ldo, float alpha, int epilogue, int tile,
-                       int split_k, void* workspace, int64_t workspace_bytes, const void* x2, int64_t ldx2,
-                       int k_split, const void* residual2, void* stream, int f32io, void* gn_partials = nullptr, int gn_hw = 0,
-                       void* ln_out = nullptr, const float* ln_gamma = nullptr, const float* ln_beta = nullptr, float ln_eps = 0.f,
-                       const float* ln_pe = nullptr, int ln_pe_inner = 1, int ln_pe_frames = 1, float* ln_stats = nullptr,
-                       const float* lnc_stats = nullptr, const float* lnc_c = nullptr, const float* lnc_bias = nullptr, int a_blocked = 0,
-                       int out_blocked = 0, int w_tilemajor = 0, const float* bias_img = nullptr, int img_rows = 0) {
-    if (!x || !w || !out) FMC_FAIL(FMC_E_NULL, "linear_bf16: NULL tensor");
-    if (tile == 18) { tile = 16; w_tilemajor = 1; }           // tile 18 = tile 16 on a weight pre-packed tile-major (fmc_hip.h)
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK_MAX || N % 8 || ldx % 8 || ldo % (f32io ? 4 : 8) || (residual && ldres % (f32io ? 4 : 8)))
+// every field of GemmParams a token GEMM sets from its request, whole and partly filled tiles alike, on a zero-initialised P (set_split_k and the launchers add theirs)
+void linear_params(GemmParams& P, const LinearReq& R) {
+    P.a = (const bf16_t*)R.x; P.w = (const bf16_t*)R.w; P.bias = (const bf16_t*)R.bias; P.res = (const bf16_t*)R.residual; P.res2 = (const bf16_t*)R.residual2;
+    P.out = (bf16_t*)R.out; P.M = R.M; P.N = R.N; P.K = R.K; P.lda = R.ldx; P.ldres = R.ldres; P.ldo = R.ldo; P.hw = 1; P.alpha = R.alpha; P.temb_div = 1; P.f32io = R.f32io;
+    P.gn_part = (float*)R.gn_partials; P.gn_hw = R.gn_hw; P.lnc_stats = R.lnc_stats; P.lnc_c = R.lnc_c; P.lnc_bias = R.lnc_bias;
+    P.a_blocked = R.a_blocked; P.out_blocked = R.out_blocked; P.w_blocked = R.w_tilemajor != 0;
+    if (R.bias_img) { P.bias_img = R.bias_img; P.w_img_stride = (int64_t)R.N * R.K; P.img_rows = R.img_rows; }
+    P.ln_stats = R.ln_stats; P.ln_out = (bf16_t*)R.ln_out; P.ln_gamma = R.ln_gamma; P.ln_beta = R.ln_beta; P.ln_eps = R.ln_eps; P.ln_pe = R.ln_pe;
+    P.ln_pe_inner = R.ln_pe_inner; P.ln_pe_frames = R.ln_pe_frames; P.a2 = (const bf16_t*)R.x2; P.lda2 = R.ldx2; P.ksplit = R.x2 ? R.k_split : 0;
+}
+
+int linear_impl(LinearReq R) {
+    if (!R.x || !R.w || !R.out) FMC_FAIL(FMC_E_NULL, "linear_bf16: NULL tensor");
+    if (R.tile == 18) { R.tile = 16; R.w_tilemajor = 1; }     // tile 18 = tile 16 on a weight pre-packed tile-major (fmc_hip.h)
+    const int64_t M = R.M;
+    const int N = R.N, K = R.K, tile = R.tile, split_k = R.split_k, f32io = R.f32io;
+    if (M <= 0 || N <= 0 || K <= 0 || K % BK_MAX || N % 8 || R.ldx % 8 || R.ldo % (f32io ? 4 : 8) || (R.residual && R.ldres % (f32io ? 4 : 8)))
         FMC_FAIL(FMC_E_SHAPE, "linear_bf16: need K%%64==0, N%%8==0 and strides %%8==0 (M=%lld N=%d K=%d)", (long long)M, N, K);
-    if (f32io && (x2 || split_k < 0)) FMC_FAIL(FMC_E_SHAPE, "linear_x3_f32: no two-source operand (split it into one buffer) and no stream-K");
-    if (epilogue != 0 && epilogue != 1) FMC_FAIL(FMC_E_SHAPE, "linear_bf16: epilogue %d", epilogue);
-    if (epilogue == 1 && (N % 64 || residual)) FMC_FAIL(FMC_E_SHAPE, "linear_bf16: GEGLU needs N%%64==0 and no residual");
-    if (!fmc_aligned16(x) || !fmc_aligned16(w) || !fmc_aligned16(out) || (residual && !fmc_aligned16(residual)) ||
-        (bias && !fmc_aligned16(bias)))
+    if (f32io && (R.x2 || split_k < 0)) FMC_FAIL(FMC_E_SHAPE, "linear_x3_f32: no two-source operand (split it into one buffer) and no stream-K");
+    if (R.epilogue != 0 && R.epilogue != 1) FMC_FAIL(FMC_E_SHAPE, "linear_bf16: epilogue %d", R.epilogue);
+    if (R.epilogue == 1 && (N % 64 || R.residual)) FMC_FAIL(FMC_E_SHAPE, "linear_bf16: GEGLU needs N%%64==0 and no residual");
+    if (!fmc_aligned16(R.x) || !fmc_aligned16(R.w) || !fmc_aligned16(R.out) || (R.residual && !fmc_aligned16(R.residual)) || (R.bias && !fmc_aligned16(R.bias)))
         FMC_FAIL(FMC_E_ALIGN, "linear_bf16: tensors must be 16-byte aligned");
-    GemmParams P{};
-    P.a = (const bf16_t*)x; P.w = (const bf16_t*)w; P.bias = (const bf16_t*)bias; P.temb = nullptr;
-    if (residual2 && (!residual || !fmc_aligned16(residual2)))
-        FMC_FAIL(FMC_E_NULL, "linear_bf16: residual2 needs residual (same row stride) and 16-byte alignment");
-    P.res = (const bf16_t*)residual; P.res2 = (const bf16_t*)residual2; P.out = (bf16_t*)out;
-    P.M = M; P.N = N; P.K = K; P.lda = ldx; P.ldres = ldres; P.ldo = ldo;
-    P.img_h = P.img_w = P.cin = 0; P.hw = 1; P.alpha = alpha; P.temb_ld = 0; P.temb_div = 1; P.ups = 0;
-    P.f32io = f32io;
-    if (gn_partials && (f32io || epilogue != 0 || tile != 16 || split_k != 1 || gn_hw <= 0 || gn_hw % 160 || M % gn_hw || N % 320 || (x2 && !a_blocked) ||
-                        ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31)))
+    if (R.residual2 && (!R.residual || !fmc_aligned16(R.residual2))) FMC_FAIL(FMC_E_NULL, "linear_bf16: residual2 needs residual (same row stride) and 16-byte alignment");
+    const bool operands_fit = a_rows_fit(M, R.ldx, K) && weight_fits(N, K);      // x and w below 2 GiB
+    const bool not_t16 = f32io || tile != 16 || split_k != 1;                    // what every epilogue feature below refuses: fp32 storage, another tile, a split
+    if (R.gn_partials && (not_t16 || R.epilogue != 0 || R.gn_hw <= 0 || R.gn_hw % 160 || M % R.gn_hw || N % 320 || (R.x2 && !R.a_blocked) || !operands_fit))
         FMC_FAIL(FMC_E_SHAPE, "linear_bf16: GroupNorm partials come out of tile 16's plain bf16 epilogue only (N %% 320 == 0, pixels per image %% 160 == 0)");
-    P.gn_part = (float*)gn_partials; P.gn_hw = gn_hw;
-    if (lnc_stats) {                                          // consumer: LayerNorm of the A rows applied in the epilogue (W pre-scaled by gamma)
-        const int cus = fmc_cu_count() & ~7;
-        if (f32io || tile != 16 || split_k != 1 || gn_partials || ln_out || ln_stats || x2 || bias || residual || residual2 || alpha != 1.f || N % 320 ||
-            M % 160 || (M / 160) * (N / 320) <= cus || cus < 8 || !lnc_c || !lnc_bias || !fmc_aligned16(lnc_c) || !fmc_aligned16(lnc_bias) ||
-            ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31) ||
-            g160_persist() == 0)
-            FMC_FAIL(FMC_E_SHAPE, "linear_bf16_lnc: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, more tiles than CUs, no bf16 bias / "
-                                  "residual, alpha 1)");
-    }
-    P.lnc_stats = lnc_stats; P.lnc_c = lnc_c; P.lnc_bias = lnc_bias;
-    if (a_blocked || out_blocked) {                           // tile-major intermediate of the feed-forward: persistent form of tile 16 only
-        const int cus = fmc_cu_count() & ~7;
-        // (x2 with a tile-major x: the reduction's second segment [k_split, K) comes from row-major x2 -- gemm160p_kernel's A2 variant, plain epilogue,
-        //  GroupNorm partials allowed: fmc_linear_bf16_fftail)
-        if (f32io || tile != 16 || split_k != 1 || (gn_partials && !(a_blocked && x2 && !out_blocked)) || (x2 && (!a_blocked || out_blocked)) || N % 320 || M % 160 || cus < 8 ||
-            (out_blocked && (M / 160) * (N / 320) <= cus) ||                      // (the GEGLU epilogue that writes tile-major is the persistent form's)
-            (a_blocked && (M / 160) * (N / 320) < cus) ||
-            (a_blocked && (epilogue != 0 || ldx != (x2 ? k_split : K) || K % 32)) ||
-            (x2 && (ln_out || ln_stats || lnc_stats || ((M - 1) * ldx2 + (K - k_split)) * 2 >= ((int64_t)1 << 31))) || (out_blocked && (epilogue != 1 || ldo != N / 2 || (N / 2) % 32)) ||
-            (int64_t)M * (a_blocked ? K : N / 2) * 2 >= ((int64_t)1 << 31) || g160_persist() == 0)
-            FMC_FAIL(FMC_E_SHAPE, "linear_bf16: the tile-major feed-forward intermediate needs tile 16's persistent form (M %% 160 == 0, N %% 320 == 0, "
-                                  "more tiles than CUs, dense rows)");
-    }
-    P.a_blocked = a_blocked; P.out_blocked = out_blocked;
-    P.bias_img = nullptr; P.w_img_stride = 0; P.img_rows = 0;
-    if (bias_img) {                                           // per-image weights (a GroupNorm folded in): persistent form of tile 16, plain epilogue
-        const int cus = fmc_cu_count() & ~7;
-        if (f32io || epilogue != 0 || tile != 16 || split_k != 1 || gn_partials || x2 || bias || residual || residual2 || alpha != 1.f || ln_out || lnc_stats ||
-            a_blocked || out_blocked || N % 320 || M % 160 || (M / 160) * (N / 320) < cus || cus < 8 || img_rows < 160 || img_rows % 160 || M % img_rows ||
-            ((uintptr_t)bias_img & 15) || ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (M / img_rows) * (int64_t)N * K * 2 >= ((int64_t)1 << 31) ||
-            g160_persist() == 0)
-            FMC_FAIL(FMC_E_SHAPE, "linear_bf16_imgw: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, at least as many tiles as CUs, images of a multiple "
-                                  "of 160 rows, no bf16 bias / residual, all weights < 2 GiB)");
-        P.bias_img = bias_img; P.w_img_stride = (int64_t)N * K; P.img_rows = img_rows;
-    }
-    if (ln_out || ln_stats) {
-        const int cus = fmc_cu_count() & ~7;
-        if ((ln_out != nullptr) == (ln_stats != nullptr)) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: exactly one of ln_out / ln_stats");
-        if (f32io || epilogue != 0 || tile != 16 || split_k != 1 || gn_partials || x2 || N != 320 || M % 160 || (bias_img ? M / 160 < cus : M / 160 <= cus) || cus < 8 ||
-            (ln_out && (!ln_gamma || !ln_beta || !fmc_aligned16(ln_out))) || (ln_stats && ((uintptr_t)ln_stats & 7)) || (ln_pe && (ln_pe_inner <= 0 || ln_pe_inner % 160 || ln_pe_frames <= 0)) ||
-            ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || g160_persist() == 0)
+    // consumer: LayerNorm of the A rows applied in the epilogue (W pre-scaled by gamma).  (Inherited, not derived: strictly more tiles than CUs)
+    if (R.lnc_stats && (not_t16 || R.gn_partials || R.ln_out || R.ln_stats || R.x2 || R.bias || R.residual || R.residual2 || R.alpha != 1.f || !operands_fit ||
+                        !g160_persistent_shape(M, N, Tiles::MoreThanCus, Rows::Whole) || !R.lnc_c || !R.lnc_bias || !fmc_aligned16(R.lnc_c) || !fmc_aligned16(R.lnc_bias)))
+        FMC_FAIL(FMC_E_SHAPE, "linear_bf16_lnc: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, more tiles than CUs, no bf16 bias / "
+                              "residual, alpha 1)");
+    // tile-major intermediate of the feed-forward: persistent form of tile 16 only.  x2 with a tile-major x: the reduction's second segment [k_split, K) comes
+    // from row-major x2 -- gemm160p_kernel's A2 variant, plain epilogue, GroupNorm partials allowed (fmc_linear_bf16_fftail).  (Inherited, not derived: the GEGLU
+    // epilogue that writes tile-major asks strictly more tiles than CUs, a tile-major A alone also takes launches of exactly one round; the intermediate's bound
+    // reads K even where only [0, k_split) of it is tile-major)
+    if ((R.a_blocked || R.out_blocked) &&
+        (not_t16 || (R.gn_partials && !(R.a_blocked && R.x2 && !R.out_blocked)) || (R.x2 && (!R.a_blocked || R.out_blocked)) ||
+         !g160_persistent_shape(M, N, R.out_blocked ? Tiles::MoreThanCus : Tiles::AtLeastCus, Rows::Whole) ||
+         (R.a_blocked && (R.epilogue != 0 || R.ldx != (R.x2 ? R.k_split : K) || K % 32)) || (R.out_blocked && (R.epilogue != 1 || R.ldo != N / 2 || (N / 2) % 32)) ||
+         (R.x2 && (R.ln_out || R.ln_stats || R.lnc_stats || !a_rows_fit(M, R.ldx2, K - R.k_split))) || blocked_bytes(M, R.a_blocked ? K : N / 2, Rows::Whole) >= GIB2))
+        FMC_FAIL(FMC_E_SHAPE, "linear_bf16: the tile-major feed-forward intermediate needs tile 16's persistent form (M %% 160 == 0, N %% 320 == 0, "
+                              "more tiles than CUs, dense rows)");
+    // per-image weights (a GroupNorm folded in): persistent form of tile 16, plain epilogue.  (Inherited, not derived: also launches of exactly one round)
+    if (R.bias_img && (not_t16 || R.epilogue != 0 || R.gn_partials || R.x2 || R.bias || R.residual || R.residual2 || R.alpha != 1.f || R.ln_out || R.lnc_stats ||
+                       R.a_blocked || R.out_blocked || !g160_persistent_shape(M, N, Tiles::AtLeastCus, Rows::Whole) || R.img_rows < 160 || R.img_rows % 160 ||
+                       M % R.img_rows || ((uintptr_t)R.bias_img & 15) || !a_rows_fit(M, R.ldx, K) || !weight_fits(M / R.img_rows * N, K)))
+        FMC_FAIL(FMC_E_SHAPE, "linear_bf16_imgw: tile 16's persistent form only (bf16, N %% 320 == 0, M %% 160 == 0, at least as many tiles as CUs, images of a multiple "
+                              "of 160 rows, no bf16 bias / residual, all weights < 2 GiB)");
+    if (R.ln_out || R.ln_stats) {
+        if ((R.ln_out != nullptr) == (R.ln_stats != nullptr)) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: exactly one of ln_out / ln_stats");
+        // (inherited, not derived: N == 320, a tile holds whole rows; strictly more tiles than CUs, with per-image weights that form's own "at least as many")
+        if (not_t16 || R.epilogue != 0 || R.gn_partials || R.x2 || N != 320 || !g160_persistent_shape(M, N, R.bias_img ? Tiles::AtLeastCus : Tiles::MoreThanCus, Rows::Whole) ||
+            (R.ln_out && (!R.ln_gamma || !R.ln_beta || !fmc_aligned16(R.ln_out))) || (R.ln_stats && ((uintptr_t)R.ln_stats & 7)) ||
+            (R.ln_pe && (R.ln_pe_inner <= 0 || R.ln_pe_inner % 160 || R.ln_pe_frames <= 0)) || !a_rows_fit(M, R.ldx, K))
             FMC_FAIL(FMC_E_SHAPE, "linear_bf16_ln: the LayerNorm output comes out of tile 16's persistent form only (bf16, N == 320, M %% 160 == 0, "
                                   "M / 160 > CUs, plain epilogue, positional-encoding frames of a multiple of 160 rows)");
     }
-    P.ln_stats = ln_stats;
-    P.ln_out = (bf16_t*)ln_out; P.ln_gamma = ln_gamma; P.ln_beta = ln_beta; P.ln_eps = ln_eps; P.ln_pe = ln_pe;
-    P.ln_pe_inner = ln_pe_inner; P.ln_pe_frames = ln_pe_frames;
-    if (x2 && (k_split <= 0 || k_split >= K || k_split % BK_MAX || ldx2 % 8 || !fmc_aligned16(x2)))
-        FMC_FAIL(FMC_E_SHAPE, "linear_bf16: two-source input needs 0 < k_split < K, k_split %% 64 == 0 (k_split=%d K=%d)", k_split, K);
-    P.a2 = (const bf16_t*)x2; P.lda2 = ldx2; P.ksplit = x2 ? k_split : 0;
-    hipStream_t st = (hipStream_t)stream;
+    if (R.x2 && (R.k_split <= 0 || R.k_split >= K || R.k_split % BK_MAX || R.ldx2 % 8 || !fmc_aligned16(R.x2)))
+        FMC_FAIL(FMC_E_SHAPE, "linear_bf16: two-source input needs 0 < k_split < K, k_split %% 64 == 0 (k_split=%d K=%d)", R.k_split, K);
     if (tile < 0 || tile > GEMM_TILE_MAX) FMC_FAIL(FMC_E_SHAPE, "linear_bf16: tile %d", tile);
-    P.w_blocked = 0;
-    if (w_tilemajor) {                                        // no other kernel can read that weight: everything that would leave tile 16 is an error
-        if (tile != 16 || f32io || N % 320 || (x2 && !a_blocked) || split_k < 1 || ((M - 1) * ldx + K) * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31))
-            FMC_FAIL(FMC_E_SHAPE, "linear_bf16: a tile-major weight (tile 18) needs bf16, N %% 320 == 0, no two-source operand, no stream-K, operands < 2 GiB");
-        P.w_blocked = 1;
-    }
-    if (int rc = set_split_k(P, split_k, workspace, workspace_bytes, epilogue == 0, "linear_bf16")) return rc;
-    if (epilogue == 0) launch_gemm<0, 0>(P, tile, st); else launch_gemm<0, 1>(P, tile, st);
+    // a tile-major weight: no other kernel can read it, everything that would leave tile 16 is an error
+    if (R.w_tilemajor && (tile != 16 || f32io || N % 320 || (R.x2 && !R.a_blocked) || split_k < 1 || !operands_fit))
+        FMC_FAIL(FMC_E_SHAPE, "linear_bf16: a tile-major weight (tile 18) needs bf16, N %% 320 == 0, no two-source operand, no stream-K, operands < 2 GiB");
+    GemmParams P{};
+    linear_params(P, R);
+    if (int rc = set_split_k(P, split_k, R.workspace, R.workspace_bytes, R.epilogue == 0, R.who)) return rc;
+    if (R.epilogue == 0) launch_gemm<0, 0>(P, tile, (hipStream_t)R.stream); else launch_gemm<0, 1>(P, tile, (hipStream_t)R.stream);
     FMC_CHECK_LAUNCH("fmc_linear_bf16");
     return 0;
 }
 
-extern "C" int fmc_linear_bf16(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                               int N, int K, int64_t ldx, int64_t ldres, int64_t ldo, float alpha, int epilogue, int tile,
-                               int split_k, void* workspace, int64_t workspace_bytes, const void* x2, int64_t ldx2,
-                               int k_split, const void* residual2, void* stream) {
-    return linear_impl(x, w, bias, residual, out, M, N, K, ldx, ldres, ldo, alpha, epilogue, tile, split_k, workspace,
-                       workspace_bytes, x2, ldx2, k_split, residual2, stream, 0);
+// The feed-forward's second GEMM at any row count: gemm160p_kernel<..., PARTIAL = 1> (see its header).  x: ceil(M / 160) WHOLE tiles [K' / 32][160][32] (K' = K, or
+// k_split with x2); the pad rows of the last tile may hold anything.  Everything else as the whole-tile forms: N % 320 == 0, at least as many tiles as CUs, plain
+// epilogue, bf16.  The argument checks are a block of their own (the entry's name, one combined shape message); parameters, LDS, grid and launch are the whole-tile forms'.
+int ff_partial_impl(LinearReq R) {
+    if (!R.x || !R.w || !R.out) FMC_FAIL(FMC_E_NULL, "%s: NULL tensor", R.who);
+    const int64_t M = R.M;
+    const int N = R.N, K = R.K, k_split = R.k_split, ka = R.x2 ? k_split : K;                   // ka: columns of the tile-major segment
+    // (inherited, not derived: also launches of exactly one round, as every form that reads a tile-major A)
+    if (M <= 0 || N <= 0 || K <= 0 || K % BK_MAX || !g160_persistent_shape(M, N, Tiles::AtLeastCus, Rows::Ceil) || (R.residual && R.ldres % 8) ||
+        (R.x2 && (k_split <= 0 || k_split >= K || k_split % BK_MAX || R.ldx2 % 8 || R.ldx2 < K - k_split || !a_rows_fit(M, R.ldx2, K - k_split))) ||
+        blocked_bytes(M, ka, Rows::Ceil) >= GIB2 || !weight_fits(N, K))
+        FMC_FAIL(FMC_E_SHAPE, "%s: need N %% 320 == 0, K %% 64 == 0, ceil(M / 160) * (N / 320) >= CUs, operands below 2 GiB (M=%lld N=%d K=%d k_split=%d)", R.who,
+                 (long long)M, N, K, k_split);
+    const void* ptrs[] = {R.x, R.w, R.out, R.x2, R.residual, R.bias};         // (a NULL optional operand counts as aligned)
+    for (const void* q : ptrs) if (!fmc_aligned16(q)) FMC_FAIL(FMC_E_ALIGN, "%s: tensors must be 16-byte aligned", R.who);
+    R.a_blocked = 1; R.ldx = ka; R.ldo = N;
+    GemmParams P{};
+    linear_params(P, R);
+    P.a_bytes = blocked_bytes(M, ka, Rows::Ceil);             // the padded allocation: the last tile's blocks are read whole
+    if (int rc = set_split_k(P, 1, nullptr, 0, true, R.who)) return rc;
+    g160_tile_order(P, true);
+    launch_gemm160p<0>(P, (hipStream_t)R.stream, true);
+    FMC_CHECK_LAUNCH(R.who);
+    return 0;
 }
 
-extern "C" int fmc_linear_bf16_gn(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                                  int N, int K, int64_t ldx, int64_t ldres, int64_t ldo, float alpha, const void* residual2,
-                                  float* gn_partials, int gn_hw, int w_tilemajor, void* stream) {
-    if (!gn_partials) FMC_FAIL(FMC_E_NULL, "linear_bf16_gn: NULL gn_partials");
-    return linear_impl(x, w, bias, residual, out, M, N, K, ldx, ldres, ldo, alpha, 0, 16, 1, nullptr, 0, nullptr, 0, 0, residual2, stream, 0,
-                       gn_partials, gn_hw, nullptr, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, nullptr, nullptr, nullptr, 0, 0, w_tilemajor);
-}
+struct ConvReq {                                              // what an entry point asks of the 3x3 convolution, as LinearReq
+    const void *x = nullptr, *w = nullptr, *bias = nullptr, *temb = nullptr, *residual = nullptr;
+    void *out = nullptr, *workspace = nullptr, *gn_partials = nullptr, *stream = nullptr;
+    int64_t temb_row_stride = 0, workspace_bytes = 0;
+    int n_img = 0, H = 0, W = 0, Cin = 0, Cout = 0, temb_img_div = 1, upsample2x = 0, tile = 16, split_k = 1, f32io = 0, w_tilemajor = 0;
+};
 
-extern "C" int fmc_linear_bf16_ln(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                                  int N, int K, int64_t ldx, int64_t ldres, int64_t ldo, float alpha, const void* residual2,
-                                  void* ln_out, const float* ln_gamma, const float* ln_beta, float ln_eps, const float* ln_pe,
-                                  int ln_pe_inner, int ln_pe_frames, float* ln_stats, int w_tilemajor, void* stream) {
-    if (!ln_out && !ln_stats) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: NULL ln_out and ln_stats");
-    if (ln_out && (!ln_gamma || !ln_beta)) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: NULL gamma / beta");
-    return linear_impl(x, w, bias, residual, out, M, N, K, ldx, ldres, ldo, alpha, 0, 16, 1, nullptr, 0, nullptr, 0, 0, residual2, stream, 0,
-                       nullptr, 0, ln_out, ln_gamma, ln_beta, ln_eps, ln_pe, ln_pe_inner, ln_pe_frames, ln_stats, nullptr, nullptr, nullptr, 0, 0, w_tilemajor);
-}
-
-extern "C" int fmc_linear_bf16_lnc(const void* x, const void* w_gamma, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldo, int epilogue,
-                                   const float* ln_stats, const float* ln_c, const float* ln_bias, int w_tilemajor, void* stream) {
-    if (!ln_stats || !ln_c || !ln_bias) FMC_FAIL(FMC_E_NULL, "linear_bf16_lnc: NULL ln_stats / ln_c / ln_bias");
-    return linear_impl(x, w_gamma, nullptr, nullptr, out, M, N, K, ldx, 0, ldo, 1.f, epilogue, 16, 1, nullptr, 0, nullptr, 0, 0, nullptr, stream, 0,
-                       nullptr, 0, nullptr, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, ln_stats, ln_c, ln_bias, 0, 0, w_tilemajor);
-}
-
-extern "C" int fmc_linear_bf16_ffblk(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
-                                     int64_t ldres, float alpha, int epilogue, int x_blocked, int out_blocked, const float* ln_stats,
-                                     const float* ln_c, const float* ln_bias, int w_tilemajor, void* stream) {
-    if (!x_blocked && !out_blocked) FMC_FAIL(FMC_E_SHAPE, "linear_bf16_ffblk: neither operand is tile-major (use fmc_linear_bf16)");
-    const int n_out = epilogue == 1 ? N / 2 : N;
-    return linear_impl(x, w, bias, residual, out, M, N, K, K, ldres, n_out, alpha, epilogue, 16, 1, nullptr, 0, nullptr, 0, 0, nullptr, stream, 0,
-                       nullptr, 0, nullptr, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, ln_stats, ln_c, ln_bias, x_blocked, out_blocked, w_tilemajor);
-}
-
-extern "C" int fmc_linear_bf16_imgw(const void* x, const void* w_img, const float* bias_img, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldo,
-                                    int img_rows, float* ln_stats, float ln_eps, int w_tilemajor, void* stream) {
-    if (!bias_img) FMC_FAIL(FMC_E_NULL, "linear_bf16_imgw: NULL bias_img");
-    return linear_impl(x, w_img, nullptr, nullptr, out, M, N, K, ldx, 0, ldo, 1.f, 0, 16, 1, nullptr, 0, nullptr, 0, 0, nullptr, stream, 0,
-                       nullptr, 0, nullptr, nullptr, nullptr, ln_eps, nullptr, 1, 1, ln_stats, nullptr, nullptr, nullptr, 0, 0, w_tilemajor, bias_img, img_rows);
-}
-
-extern "C" int fmc_linear_bf16_fftail(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                                      int N, int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor, void* stream) {
-    if (!x2) FMC_FAIL(FMC_E_NULL, "linear_bf16_fftail: NULL x2 (use fmc_linear_bf16_ffblk)");
-    return linear_impl(x_blocked, w, bias, residual, out, M, N, K, k_split, ldres, N, 1.f, 0, 16, 1, nullptr, 0, x2, ldx2, k_split, nullptr, stream, 0,
-                       gn_partials, gn_hw, nullptr, nullptr, nullptr, 0.f, nullptr, 1, 1, nullptr, nullptr, nullptr, nullptr, 1, 0, w_tilemajor);
-}
-
-extern "C" int fmc_linear_x3_f32(const void* x3, const void* w3, const float* bias, const float* residual, float* out, int64_t M,
-                                 int N, int K3, int64_t ldx, int64_t ldres, int64_t ldo, float alpha, int epilogue, int tile,
-                                 int split_k, void* workspace, int64_t workspace_bytes, const float* residual2, void* stream) {
-    if (K3 % 3 || (K3 / 3) % 8) FMC_FAIL(FMC_E_SHAPE, "linear_x3_f32: K3 = 3 K of the split operands (K3=%d)", K3);
-    return linear_impl(x3, w3, bias, residual, out, M, N, K3, ldx, ldres, ldo, alpha, epilogue, tile, split_k, workspace,
-                       workspace_bytes, nullptr, 0, 0, residual2, stream, 1);
-}
-
-static int conv3x3_impl(const void* x, const void* w, const void* bias, const void* temb, const void* residual,
-                        void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                        int temb_img_div, int upsample2x, int tile, int split_k,
-                        void* workspace, int64_t workspace_bytes, void* stream, int f32io, void* gn_partials = nullptr, int w_tilemajor = 0) {
-    if (!x || !w || !out) FMC_FAIL(FMC_E_NULL, "conv3x3_bf16: NULL tensor");
-    if (tile == 18) { tile = 16; w_tilemajor = 1; }           // tile 18 = tile 16 on a filter pre-packed tile-major (fmc_hip.h)
+int conv3x3_impl(ConvReq R) {
+    if (!R.x || !R.w || !R.out) FMC_FAIL(FMC_E_NULL, "conv3x3_bf16: NULL tensor");
+    if (R.tile == 18) { R.tile = 16; R.w_tilemajor = 1; }     // tile 18 = tile 16 on a filter pre-packed tile-major (fmc_hip.h)
+    const int n_img = R.n_img, H = R.H, W = R.W, Cin = R.Cin, Cout = R.Cout, tile = R.tile, split_k = R.split_k, f32io = R.f32io, ups = R.upsample2x;
     if (n_img <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK_MAX || Cout % 8)
         FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: need Cin%%64==0 and Cout%%8==0 (Cin=%d Cout=%d)", Cin, Cout);
-    if (!fmc_aligned16(x) || !fmc_aligned16(w) || !fmc_aligned16(out) || (residual && !fmc_aligned16(residual)) ||
-        (temb && !fmc_aligned16(temb)) || (bias && !fmc_aligned16(bias)))
+    if (!fmc_aligned16(R.x) || !fmc_aligned16(R.w) || !fmc_aligned16(R.out) || (R.residual && !fmc_aligned16(R.residual)) || (R.temb && !fmc_aligned16(R.temb)) ||
+        (R.bias && !fmc_aligned16(R.bias)))
         FMC_FAIL(FMC_E_ALIGN, "conv3x3_bf16: tensors must be 16-byte aligned");
-    GemmParams P{};
-    P.a = (const bf16_t*)x; P.w = (const bf16_t*)w; P.bias = (const bf16_t*)bias; P.temb = (const bf16_t*)temb;
-    P.res = (const bf16_t*)residual; P.res2 = nullptr; P.out = (bf16_t*)out;
-    P.M = (int64_t)n_img * H * W; P.N = Cout; P.K = 9 * Cin; P.lda = Cin; P.ldres = Cout; P.ldo = Cout;
-    P.a2 = nullptr; P.lda2 = 0; P.ksplit = 0;
-    P.img_h = H; P.img_w = W; P.cin = Cin; P.hw = H * W; P.alpha = 1.f;
-    if (temb && (temb_img_div < 1 || temb_row_stride % (f32io ? 4 : 8))) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: temb_img_div >= 1, temb_row_stride %% 8 == 0");
-    P.f32io = f32io;
-    if (gn_partials && (f32io || tile != 16 || split_k != 1 || (H * W) % 160 || Cout % 320 ||
-                        (int64_t)n_img * H * W * Cin * 2 * (upsample2x == 2 ? 4 : 1) >= ((int64_t)1 << 31) || (int64_t)Cout * 9 * Cin * 2 >= ((int64_t)1 << 31)))
+    if (R.temb && (R.temb_img_div < 1 || R.temb_row_stride % (f32io ? 4 : 8))) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: temb_img_div >= 1, temb_row_stride %% 8 == 0");
+    // the input tensor as the kernel addresses it (the 2x2-read form spans four times the pixels) and the filter, below 2 GiB
+    const bool operands_fit = (int64_t)n_img * H * W * Cin * 2 * (ups == 2 ? 4 : 1) < GIB2 && weight_fits(Cout, 9 * (int64_t)Cin);
+    if (R.gn_partials && (f32io || tile != 16 || split_k != 1 || (H * W) % 160 || Cout % 320 || !operands_fit))
         FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: GroupNorm partials come out of tile 16's plain bf16 epilogue only (Cout %% 320 == 0, H W %% 160 == 0)");
-    P.gn_part = (float*)gn_partials; P.gn_hw = H * W;
     if (f32io && split_k < 0) FMC_FAIL(FMC_E_SHAPE, "conv3x3_x3_f32: no stream-K in fp32-storage mode");
-    P.temb_ld = temb_row_stride; P.temb_div = temb_img_div < 1 ? 1 : temb_img_div;
-    if (upsample2x < 0 || upsample2x > 2) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: resample mode %d", upsample2x);
-    if (upsample2x == 1 && ((H | W) & 1)) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: upsample2x needs even H, W (the OUTPUT size)");
-    P.ups = upsample2x;
+    if (ups < 0 || ups > 2) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: resample mode %d", ups);
+    if (ups == 1 && ((H | W) & 1)) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: upsample2x needs even H, W (the OUTPUT size)");
     if (tile < 0 || tile > GEMM_TILE_MAX) FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: tile %d", tile);
-    P.w_blocked = 0;
-    if (w_tilemajor) {                                        // the filter is packed in the kernel's (chunk, tap, half) sub-tile order
-        if (tile != 16 || f32io || Cout % 320 || Cin % 64 || split_k < 1 || (int64_t)Cout * 9 * Cin * 2 >= ((int64_t)1 << 31) ||
-            (int64_t)n_img * H * W * Cin * 2 * (upsample2x == 2 ? 4 : 1) >= ((int64_t)1 << 31))
-            FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: tile 18 (tile-major filter) needs bf16, Cout %% 320 == 0, Cin %% 64 == 0, no stream-K, operands < 2 GiB");
-        P.w_blocked = 1;
-    }
-    if (int rc = set_split_k(P, split_k, workspace, workspace_bytes, true, "conv3x3_bf16")) return rc;
-    launch_gemm<1, 0>(P, tile, (hipStream_t)stream);
+    // a tile-major filter: packed in the kernel's (chunk, tap, half) sub-tile order
+    if (R.w_tilemajor && (tile != 16 || f32io || Cout % 320 || Cin % 64 || split_k < 1 || !operands_fit))
+        FMC_FAIL(FMC_E_SHAPE, "conv3x3_bf16: tile 18 (tile-major filter) needs bf16, Cout %% 320 == 0, Cin %% 64 == 0, no stream-K, operands < 2 GiB");
+    GemmParams P{};
+    P.a = (const bf16_t*)R.x; P.w = (const bf16_t*)R.w; P.bias = (const bf16_t*)R.bias; P.temb = (const bf16_t*)R.temb; P.res = (const bf16_t*)R.residual;
+    P.out = (bf16_t*)R.out; P.M = (int64_t)n_img * H * W; P.N = Cout; P.K = 9 * Cin; P.lda = Cin; P.ldres = Cout; P.ldo = Cout;
+    P.img_h = H; P.img_w = W; P.cin = Cin; P.hw = H * W; P.alpha = 1.f; P.f32io = f32io; P.gn_part = (float*)R.gn_partials; P.gn_hw = H * W;
+    P.temb_ld = R.temb_row_stride; P.temb_div = R.temb_img_div < 1 ? 1 : R.temb_img_div; P.ups = ups; P.w_blocked = R.w_tilemajor != 0;
+    if (int rc = set_split_k(P, split_k, R.workspace, R.workspace_bytes, true, "conv3x3_bf16")) return rc;
+    launch_gemm<1, 0>(P, tile, (hipStream_t)R.stream);
     FMC_CHECK_LAUNCH("fmc_conv3x3_bf16");
     return 0;
 }
 
-extern "C" int fmc_conv3x3_bf16(const void* x, const void* w, const void* bias, const void* temb, const void* residual,
-                                void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                                int temb_img_div, int upsample2x, int tile, int split_k,
-                                void* workspace, int64_t workspace_bytes, void* stream) {
-    return conv3x3_impl(x, w, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, tile,
-                        split_k, workspace, workspace_bytes, stream, 0);
+}  // namespace
+
+extern "C" int fmc_linear_bf16(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldres,
+                               int64_t ldo, float alpha, int epilogue, int tile, int split_k, void* workspace, int64_t workspace_bytes, const void* x2, int64_t ldx2,
+                               int k_split, const void* residual2, void* stream) {
+    return linear_impl({.x = x, .x2 = x2, .w = w, .bias = bias, .residual = residual, .residual2 = residual2, .out = out, .workspace = workspace, .stream = stream, .M = M,
+                        .ldx = ldx, .ldx2 = ldx2, .ldres = ldres, .ldo = ldo, .workspace_bytes = workspace_bytes, .N = N, .K = K, .k_split = k_split, .epilogue = epilogue,
+                        .tile = tile, .split_k = split_k, .alpha = alpha});
 }
 
-extern "C" int fmc_conv3x3_bf16_gn(const void* x, const void* w, const void* bias, const void* temb, const void* residual,
-                                   void* out, int n_img, int H, int W, int Cin, int Cout, int64_t temb_row_stride,
-                                   int temb_img_div, int upsample2x, float* gn_partials, int w_tilemajor, void* stream) {
+extern "C" int fmc_linear_bf16_gn(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldres,
+                                  int64_t ldo, float alpha, const void* residual2, float* gn_partials, int gn_hw, int w_tilemajor, void* stream) {
+    if (!gn_partials) FMC_FAIL(FMC_E_NULL, "linear_bf16_gn: NULL gn_partials");
+    return linear_impl({.x = x, .w = w, .bias = bias, .residual = residual, .residual2 = residual2, .out = out, .stream = stream, .gn_partials = gn_partials, .M = M,
+                        .ldx = ldx, .ldres = ldres, .ldo = ldo, .N = N, .K = K, .gn_hw = gn_hw, .w_tilemajor = w_tilemajor, .alpha = alpha});
+}
+
+extern "C" int fmc_linear_bf16_ln(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldres,
+                                  int64_t ldo, float alpha, const void* residual2, void* ln_out, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                                  const float* ln_pe, int ln_pe_inner, int ln_pe_frames, float* ln_stats, int w_tilemajor, void* stream) {
+    if (!ln_out && !ln_stats) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: NULL ln_out and ln_stats");
+    if (ln_out && (!ln_gamma || !ln_beta)) FMC_FAIL(FMC_E_NULL, "linear_bf16_ln: NULL gamma / beta");
+    return linear_impl({.x = x, .w = w, .bias = bias, .residual = residual, .residual2 = residual2, .out = out, .stream = stream, .ln_out = ln_out, .ln_stats = ln_stats,
+                        .ln_gamma = ln_gamma, .ln_beta = ln_beta, .ln_pe = ln_pe, .M = M, .ldx = ldx, .ldres = ldres, .ldo = ldo, .N = N, .K = K,
+                        .ln_pe_inner = ln_pe_inner, .ln_pe_frames = ln_pe_frames, .w_tilemajor = w_tilemajor, .alpha = alpha, .ln_eps = ln_eps});
+}
+
+extern "C" int fmc_linear_bf16_lnc(const void* x, const void* w_gamma, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldo, int epilogue, const float* ln_stats,
+                                   const float* ln_c, const float* ln_bias, int w_tilemajor, void* stream) {
+    if (!ln_stats || !ln_c || !ln_bias) FMC_FAIL(FMC_E_NULL, "linear_bf16_lnc: NULL ln_stats / ln_c / ln_bias");
+    return linear_impl({.x = x, .w = w_gamma, .out = out, .stream = stream, .lnc_stats = ln_stats, .lnc_c = ln_c, .lnc_bias = ln_bias, .M = M, .ldx = ldx, .ldo = ldo,
+                        .N = N, .K = K, .epilogue = epilogue, .w_tilemajor = w_tilemajor});
+}
+
+extern "C" int fmc_linear_bf16_ffblk(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K, int64_t ldres, float alpha,
+                                     int epilogue, int x_blocked, int out_blocked, const float* ln_stats, const float* ln_c, const float* ln_bias, int w_tilemajor,
+                                     void* stream) {
+    if (!x_blocked && !out_blocked) FMC_FAIL(FMC_E_SHAPE, "linear_bf16_ffblk: neither operand is tile-major (use fmc_linear_bf16)");
+    return linear_impl({.x = x, .w = w, .bias = bias, .residual = residual, .out = out, .stream = stream, .lnc_stats = ln_stats, .lnc_c = ln_c, .lnc_bias = ln_bias,
+                        .M = M, .ldx = K, .ldres = ldres, .ldo = epilogue == 1 ? N / 2 : N, .N = N, .K = K, .epilogue = epilogue, .a_blocked = x_blocked,
+                        .out_blocked = out_blocked, .w_tilemajor = w_tilemajor, .alpha = alpha});
+}
+
+extern "C" int fmc_linear_bf16_imgw(const void* x, const void* w_img, const float* bias_img, void* out, int64_t M, int N, int K, int64_t ldx, int64_t ldo, int img_rows,
+                                    float* ln_stats, float ln_eps, int w_tilemajor, void* stream) {
+    if (!bias_img) FMC_FAIL(FMC_E_NULL, "linear_bf16_imgw: NULL bias_img");
+    return linear_impl({.x = x, .w = w_img, .out = out, .stream = stream, .ln_stats = ln_stats, .bias_img = bias_img, .M = M, .ldx = ldx, .ldo = ldo, .N = N, .K = K,
+                        .w_tilemajor = w_tilemajor, .img_rows = img_rows, .ln_eps = ln_eps});
+}
+
+extern "C" int fmc_linear_bf16_fftail(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
+                                      int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor, void* stream) {
+    if (!x2) FMC_FAIL(FMC_E_NULL, "linear_bf16_fftail: NULL x2 (use fmc_linear_bf16_ffblk)");
+    return linear_impl({.x = x_blocked, .x2 = x2, .w = w, .bias = bias, .residual = residual, .out = out, .stream = stream, .gn_partials = gn_partials, .M = M,
+                        .ldx = k_split, .ldx2 = ldx2, .ldres = ldres, .ldo = N, .N = N, .K = K, .k_split = k_split, .gn_hw = gn_hw, .a_blocked = 1,
+                        .w_tilemajor = w_tilemajor});
+}
+
+extern "C" int fmc_linear_x3_f32(const void* x3, const void* w3, const float* bias, const float* residual, float* out, int64_t M, int N, int K3, int64_t ldx,
+                                 int64_t ldres, int64_t ldo, float alpha, int epilogue, int tile, int split_k, void* workspace, int64_t workspace_bytes,
+                                 const float* residual2, void* stream) {
+    if (K3 % 3 || (K3 / 3) % 8) FMC_FAIL(FMC_E_SHAPE, "linear_x3_f32: K3 = 3 K of the split operands (K3=%d)", K3);
+    return linear_impl({.x = x3, .w = w3, .bias = bias, .residual = residual, .residual2 = residual2, .out = out, .workspace = workspace, .stream = stream, .M = M,
+                        .ldx = ldx, .ldres = ldres, .ldo = ldo, .workspace_bytes = workspace_bytes, .N = N, .K = K3, .epilogue = epilogue, .tile = tile,
+                        .split_k = split_k, .f32io = 1, .alpha = alpha});
+}
+
+extern "C" int fmc_linear_bf16_ffblk_partial(const void* x_blocked, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
+                                             int64_t ldres, float alpha, int w_tilemajor, void* stream) {
+    return ff_partial_impl({.who = "linear_bf16_ffblk_partial", .x = x_blocked, .w = w, .bias = bias, .residual = residual, .out = out, .stream = stream, .M = M,
+                            .ldres = ldres, .N = N, .K = K, .w_tilemajor = w_tilemajor, .alpha = alpha});
+}
+
+extern "C" int fmc_linear_bf16_fftail_partial(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N,
+                                              int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor, void* stream) {
+    if (!x2) FMC_FAIL(FMC_E_NULL, "linear_bf16_fftail_partial: NULL x2 (use fmc_linear_bf16_ffblk_partial)");
+    if (gn_partials || gn_hw) FMC_FAIL(FMC_E_SHAPE, "linear_bf16_fftail_partial: no GroupNorm partials with a partly filled last tile");
+    return ff_partial_impl({.who = "linear_bf16_fftail_partial", .x = x_blocked, .x2 = x2, .w = w, .bias = bias, .residual = residual, .out = out, .stream = stream,
+                            .M = M, .ldx2 = ldx2, .ldres = ldres, .N = N, .K = K, .k_split = k_split, .w_tilemajor = w_tilemajor});
+}
+
+extern "C" int fmc_conv3x3_bf16(const void* x, const void* w, const void* bias, const void* temb, const void* residual, void* out, int n_img, int H, int W, int Cin,
+                                int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x, int tile, int split_k, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+    return conv3x3_impl({.x = x, .w = w, .bias = bias, .temb = temb, .residual = residual, .out = out, .workspace = workspace, .stream = stream,
+                         .temb_row_stride = temb_row_stride, .workspace_bytes = workspace_bytes, .n_img = n_img, .H = H, .W = W, .Cin = Cin, .Cout = Cout,
+                         .temb_img_div = temb_img_div, .upsample2x = upsample2x, .tile = tile, .split_k = split_k});
+}
+
+extern "C" int fmc_conv3x3_bf16_gn(const void* x, const void* w, const void* bias, const void* temb, const void* residual, void* out, int n_img, int H, int W, int Cin,
+                                   int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x, float* gn_partials, int w_tilemajor, void* stream) {
     if (!gn_partials) FMC_FAIL(FMC_E_NULL, "conv3x3_bf16_gn: NULL gn_partials");
-    return conv3x3_impl(x, w, bias, temb, residual, out, n_img, H, W, Cin, Cout, temb_row_stride, temb_img_div, upsample2x, 16, 1,
-                        nullptr, 0, stream, 0, gn_partials, w_tilemajor);
+    return conv3x3_impl({.x = x, .w = w, .bias = bias, .temb = temb, .residual = residual, .out = out, .gn_partials = gn_partials, .stream = stream,
+                         .temb_row_stride = temb_row_stride, .n_img = n_img, .H = H, .W = W, .Cin = Cin, .Cout = Cout, .temb_img_div = temb_img_div,
+                         .upsample2x = upsample2x, .w_tilemajor = w_tilemajor});
 }
 
-extern "C" int fmc_conv3x3_x3_f32(const void* x3, const void* w3, const float* bias, const float* temb, const float* residual,
-                                  float* out, int n_img, int H, int W, int Cin3, int Cout, int64_t temb_row_stride,
-                                  int temb_img_div, int upsample2x, int tile, int split_k,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int fmc_conv3x3_x3_f32(const void* x3, const void* w3, const float* bias, const float* temb, const float* residual, float* out, int n_img, int H, int W,
+                                  int Cin3, int Cout, int64_t temb_row_stride, int temb_img_div, int upsample2x, int tile, int split_k, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
     if (Cin3 % 3) FMC_FAIL(FMC_E_SHAPE, "conv3x3_x3_f32: Cin3 = 3 Cin of the split operands (Cin3=%d)", Cin3);
-    return conv3x3_impl(x3, w3, bias, temb, residual, out, n_img, H, W, Cin3, Cout, temb_row_stride, temb_img_div, upsample2x, tile,
-                        split_k, workspace, workspace_bytes, stream, 1);
+    return conv3x3_impl({.x = x3, .w = w3, .bias = bias, .temb = temb, .residual = residual, .out = out, .workspace = workspace, .stream = stream,
+                         .temb_row_stride = temb_row_stride, .workspace_bytes = workspace_bytes, .n_img = n_img, .H = H, .W = W, .Cin = Cin3, .Cout = Cout,
+                         .temb_img_div = temb_img_div, .upsample2x = upsample2x, .tile = tile, .split_k = split_k, .f32io = 1});
 }
 
 // ---- fp32 -> split-bf16 x3 operand (see fmc_hip.h) ---------------------------------------------------------------------------
@@ -3253,8 +3302,8 @@ extern "C" int fmc_split_bf16x3(const float* src, void* dst, int64_t rows, int C
     return 0;
 }
 
-extern "C" int fmc_linear_fp8_qkv(const void* x, const void* w, void* out_fp8, int64_t M, int N, int K, int64_t ldx,
-                                  const void* inv_scales, void* amax_bits, void* stream) {
+extern "C" int fmc_linear_fp8_qkv(const void* x, const void* w, void* out_fp8, int64_t M, int N, int K, int64_t ldx, const void* inv_scales, void* amax_bits,
+                                  void* stream) {
     if (!x || !w || !out_fp8 || !inv_scales) FMC_FAIL(FMC_E_NULL, "linear_fp8_qkv: NULL tensor");
     if (M <= 0 || N <= 0 || K <= 0 || K % BK_MAX || N % 192 || ldx % 8)
         FMC_FAIL(FMC_E_SHAPE, "linear_fp8_qkv: need K%%64==0, N = 3*C with C%%64==0, ldx%%8==0 (M=%lld N=%d K=%d)", (long long)M, N, K);
@@ -3268,55 +3317,4 @@ extern "C" int fmc_linear_fp8_qkv(const void* x, const void* w, void* out_fp8, i
     launch_gemm8<0, 2, 4>(P, (hipStream_t)stream);
     FMC_CHECK_LAUNCH("fmc_linear_fp8_qkv");
     return 0;
-}
-
-// ---- the feed-forward's second GEMM at any row count: gemm160p_kernel<..., PARTIAL = 1> (see its header) ----------------------------------------------
-// x_blocked: ceil(M / 160) WHOLE tiles [K' / 32][160][32] (K' = K, or k_split with x2); the pad rows of the last tile may hold anything.  Everything else as
-// the whole-tile forms: N % 320 == 0, at least as many tiles as CUs, plain epilogue, bf16.
-static int ff_partial_impl(const char* who, const void* xb, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N,
-                           int K, int k_split, int64_t ldx2, int64_t ldres, float alpha, int w_tilemajor, void* stream) {
-    if (!xb || !w || !out) FMC_FAIL(FMC_E_NULL, "%s: NULL tensor", who);
-    const int cus = fmc_cu_count() & ~7;
-    const int64_t tiles_m = (M + 159) / 160, Mp = tiles_m * 160;
-    const int ka = x2 ? k_split : K;                          // columns of the tile-major segment
-    if (M <= 0 || N <= 0 || K <= 0 || N % 320 || K % BK_MAX || cus < 8 || tiles_m * (N / 320) < cus || g160_persist() == 0 || (residual && ldres % 8) ||
-        (x2 && (k_split <= 0 || k_split >= K || k_split % BK_MAX || ldx2 % 8 || ldx2 < K - k_split || ((M - 1) * ldx2 + (K - k_split)) * 2 >= ((int64_t)1 << 31))) ||
-        Mp * (int64_t)ka * 2 >= ((int64_t)1 << 31) || (int64_t)N * K * 2 >= ((int64_t)1 << 31))
-        FMC_FAIL(FMC_E_SHAPE, "%s: need N %% 320 == 0, K %% 64 == 0, ceil(M / 160) * (N / 320) >= CUs, operands below 2 GiB (M=%lld N=%d K=%d k_split=%d)", who,
-                 (long long)M, N, K, k_split);
-    if (!fmc_aligned16(xb) || !fmc_aligned16(w) || !fmc_aligned16(out) || (x2 && !fmc_aligned16(x2)) || (residual && !fmc_aligned16(residual)) ||
-        (bias && !fmc_aligned16(bias)))
-        FMC_FAIL(FMC_E_ALIGN, "%s: tensors must be 16-byte aligned", who);
-    GemmParams P{};
-    P.a = (const bf16_t*)xb; P.w = (const bf16_t*)w; P.bias = (const bf16_t*)bias; P.res = (const bf16_t*)residual; P.out = (bf16_t*)out;
-    P.M = M; P.N = N; P.K = K; P.lda = ka; P.ldres = ldres; P.ldo = N; P.hw = 1; P.alpha = alpha; P.temb_div = 1;
-    P.ln_pe_inner = 1; P.ln_pe_frames = 1;
-    P.a2 = (const bf16_t*)x2; P.lda2 = ldx2; P.ksplit = x2 ? k_split : 0;
-    P.a_blocked = 1; P.w_blocked = w_tilemajor != 0;
-    P.a_bytes = Mp * (int64_t)ka * 2;                         // the padded allocation: the last tile's blocks are read whole
-    if (int rc = set_split_k(P, 1, nullptr, 0, true, who)) return rc;
-    P.tiles_m = (int)tiles_m;
-    P.tiles_n = N / 320;
-    P.tap_outer = 0;
-    P.group_m = xcd_group_m(P, true, 32.0, 320, 160);
-    constexpr size_t ldsp = (size_t)3 * (160 + 320) * 32 * sizeof(bf16_t) + 1024 + (size_t)80 * 328 * 2 + 5120;     // launch_gemm160's, plain epilogue
-    const dim3 grid((unsigned)cus), block(512);
-    hipStream_t st = (hipStream_t)stream;
-    if (x2) fmc_launch<gemm160p_kernel<0, 5, 0, 0, 1, 0, 1>>(grid, block, ldsp, st, P);
-    else fmc_launch<gemm160p_kernel<0, 5, 0, 0, 0, 0, 1>>(grid, block, ldsp, st, P);
-    FMC_CHECK_LAUNCH(who);
-    return 0;
-}
-
-extern "C" int fmc_linear_bf16_ffblk_partial(const void* x_blocked, const void* w, const void* bias, const void* residual, void* out, int64_t M, int N, int K,
-                                             int64_t ldres, float alpha, int w_tilemajor, void* stream) {
-    return ff_partial_impl("linear_bf16_ffblk_partial", x_blocked, nullptr, w, bias, residual, out, M, N, K, 0, 0, ldres, alpha, w_tilemajor, stream);
-}
-
-extern "C" int fmc_linear_bf16_fftail_partial(const void* x_blocked, const void* x2, const void* w, const void* bias, const void* residual, void* out, int64_t M,
-                                              int N, int K, int k_split, int64_t ldx2, int64_t ldres, float* gn_partials, int gn_hw, int w_tilemajor,
-                                              void* stream) {
-    if (!x2) FMC_FAIL(FMC_E_NULL, "linear_bf16_fftail_partial: NULL x2 (use fmc_linear_bf16_ffblk_partial)");
-    if (gn_partials || gn_hw) FMC_FAIL(FMC_E_SHAPE, "linear_bf16_fftail_partial: no GroupNorm partials with a partly filled last tile");
-    return ff_partial_impl("linear_bf16_fftail_partial", x_blocked, x2, w, bias, residual, out, M, N, K, k_split, ldx2, ldres, 1.f, w_tilemajor, stream);
 }

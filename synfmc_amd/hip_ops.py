@@ -1306,6 +1306,22 @@ def _tile_form(kind: str, C: int, any_rows: bool) -> TileForm:
     return TileForm(_tile_units(C, kind), any_rows)
 
 
+def _g160_persistent(M: int, N: int, device, at_least: bool, any_rows: bool = False) -> bool:
+    """Tile 16's persistent form takes (M, N) on this device (csrc/gemm_conv.hip: `g160_persistent_shape`): `FMC_G160_PERSIST` not 0 (read per call), N a
+    multiple of 320, M of 160 (`any_rows`: any M, the last tile partly filled), and strictly more 160 x 320 tiles than CUs -- `at_least`: as many
+    suffice.  Which of the two a form asks is inherited, not derived: each call site says so."""
+    form = TileForm(_TILE_UNITS["ff"], any_rows)
+    if os.environ.get("FMC_G160_PERSIST", "1") == "0" or N % 320 or not form.takes(M):
+        return False
+    tiles = form.tiles(M) * (N // 320)
+    return tiles >= _cus(device) if at_least else tiles > _cus(device)
+
+
+def _below_2gib(numel: int) -> bool:
+    """`numel` bf16 elements stay below 2 GiB: the kernels' 32-bit operand offsets."""
+    return numel * 2 < (1 << 31)
+
+
 def _entry(whole: str, partial: bool):
     """(name, function) in C of a launch entry point: `whole` or its partial-tile twin (`..._partial_bf16`, `fmc_linear_bf16_<form>_partial`)."""
     name = whole if not partial else (whole[:-5] + "_partial_bf16" if whole.endswith("_bf16") else whole + "_partial")
@@ -1493,13 +1509,11 @@ def _geglu_blocked_ok(h: torch.Tensor, w2: torch.Tensor, residual, any_rows: boo
     C = h.shape[-1]
     M = h.numel() // C
     N2, Cff = w2.shape
-    form = _tile_form("ff", C, any_rows)
-    # inherited, not derived: Cff % 32 on whole tiles, Cff % 64 and the weight's own 2 GiB bound on partly filled ones.  (The intermediate's bound is the
-    # padded count in both: on whole tiles that IS M * Cff)
-    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and form.takes(M) and N2 % 320 == 0 and Cff % (64 if any_rows else 32) == 0
-            and form.tiles(M) * (N2 // 320) > _cus(h.device) and ff_blocked_numel(M, Cff) * 2 < (1 << 31) and (not any_rows or N2 * Cff * 2 < (1 << 31))
-            and w2.dtype == torch.bfloat16 and w2.is_contiguous()
-            and (residual is None or (residual.is_contiguous() and residual.dtype == h.dtype)) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+    # inherited, not derived: Cff % 32 on whole tiles, Cff % 64 and the weight's own 2 GiB bound on partly filled ones; strictly more tiles than CUs.  (The
+    # intermediate's bound is the padded count in both: on whole tiles that IS M * Cff)
+    return (GEGLU_DIRECT_BLOCKED and FF_BLOCKED and C == 320 and Cff % (64 if any_rows else 32) == 0 and _g160_persistent(M, N2, h.device, False, any_rows)
+            and _below_2gib(ff_blocked_numel(M, Cff)) and (not any_rows or _below_2gib(N2 * Cff)) and w2.dtype == torch.bfloat16 and w2.is_contiguous()
+            and (residual is None or (residual.is_contiguous() and residual.dtype == h.dtype)))
 
 
 def geglu_direct_blocked_partial_ok(h: torch.Tensor, w2: torch.Tensor, residual) -> bool:
@@ -1510,14 +1524,12 @@ def geglu_direct_blocked_partial_ok(h: torch.Tensor, w2: torch.Tensor, residual)
 def _ff_tail_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor], any_rows: bool) -> bool:
     C = h.shape[-1]
     M = h.numel() // C
-    form = _tile_form("ff", C, any_rows)
-    # inherited, not derived: `>=` against the CU count where the blocked pair asks `>`; the folded weight's own 2 GiB bound on partly filled tiles only
+    # inherited, not derived: as many tiles as CUs suffice where the blocked pair asks more; the folded weight's own 2 GiB bound on partly filled tiles only
     return (FF_TAIL and not torch.is_grad_enabled() and h.dtype == torch.bfloat16 and h.is_contiguous() and wp.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16
-            and wp.ndim == 2 and wp.shape[1] == w2.shape[0] == C and wp.shape[0] % 320 == 0 and C % 64 == 0 and w2.shape[1] % 64 == 0
-            and form.takes(M) and form.tiles(M) * (wp.shape[0] // 320) >= _cus(h.device) and ff_blocked_numel(M, max(w2.shape[1], C)) * 2 < (1 << 31)
-            and (not any_rows or wp.shape[0] * (w2.shape[1] + C) * 2 < (1 << 31))
-            and tail_residual is not None and tail_residual.dtype == h.dtype and tail_residual.is_contiguous()
-            and tail_residual.numel() == M * wp.shape[0] and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+            and wp.ndim == 2 and wp.shape[1] == w2.shape[0] == C and C % 64 == 0 and w2.shape[1] % 64 == 0
+            and _g160_persistent(M, wp.shape[0], h.device, True, any_rows) and _below_2gib(ff_blocked_numel(M, max(w2.shape[1], C)))
+            and (not any_rows or _below_2gib(wp.shape[0] * (w2.shape[1] + C)))
+            and tail_residual is not None and tail_residual.dtype == h.dtype and tail_residual.is_contiguous() and tail_residual.numel() == M * wp.shape[0])
 
 
 def ff_tail_partial_ok(h: torch.Tensor, w2: torch.Tensor, wp: torch.Tensor, tail_residual: Optional[torch.Tensor]) -> bool:
@@ -1570,6 +1582,29 @@ def _rows2d(t: torch.Tensor):
         return t.numel() // C, C
     assert t.ndim == 2 and t.stride(1) == 1, "strided operands must be 2-D [M, C] views"
     return t.shape[0], t.stride(0)
+
+
+# ---- what the token-GEMM wrappers below share: the residuals' stride with its assertions, the packed weight, the log line and the call --------------------------
+def _ldres(out: torch.Tensor, residual, residual2=None) -> int:
+    """Row stride of the residual(s) of `out` (0 without one): they have the output's shape, and the second one the first one's stride."""
+    ldres = 0
+    if residual is not None:
+        assert residual.shape == out.shape
+        ldres = _rows2d(residual)[1]
+    if residual2 is not None:
+        assert residual is not None and residual2.shape == out.shape and _rows2d(residual2)[1] == ldres
+    return ldres
+
+
+def _packed(weight: torch.Tensor):
+    """(the weight as tile 16 is to read it, the entry points' `w_tilemajor` flag): packed tile-major unless `W_TILEMAJOR` is off."""
+    return (_w_tilemajor(weight), 1) if W_TILEMAJOR else (weight, 0)
+
+
+def _own_linear(entry: str, form: str, M: int, N: int, Kd: int, n_res: int, *args) -> None:
+    """The `own_linear` log line of a launch and the call of `entry` with `args` + the stream."""
+    _log_call("own_linear", (M, N, Kd, form, n_res), 2.0 * M * N * Kd)
+    _lib.check(getattr(_lib.load(), entry)(*args, _stream()), entry)
 
 
 VENDOR_DIRECT = os.environ.get("FMC_VENDOR_DIRECT", "1") != "0"      # A/B switch: the vendor arm through fmc_vendor_linear_bf16 (bias + residual in the GEMM)
@@ -1707,15 +1742,9 @@ def linear4_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     assert weight.is_contiguous() and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
     M, ldx = _rows2d(x)
     out = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
-    ldres = 0
-    if residual is not None:
-        assert residual.shape == out.shape
-        _, ldres = _rows2d(residual)
-    if residual2 is not None:
-        assert residual is not None and residual2.shape == out.shape and _rows2d(residual2)[1] == ldres
-    _log_call("own_linear", (M, N, Kd, "g4", (residual is not None) + (residual2 is not None)), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear4_bf16(x.data_ptr(), weight.data_ptr(), _p(bias), _p(residual), _p(residual2), out.data_ptr(), M, N, Kd, ldx, ldres,
-                                            N, float(alpha), _stream()), "fmc_linear4_bf16")
+    ldres = _ldres(out, residual, residual2)
+    _own_linear("fmc_linear4_bf16", "g4", M, N, Kd, (residual is not None) + (residual2 is not None),
+                x.data_ptr(), weight.data_ptr(), _p(bias), _p(residual), _p(residual2), out.data_ptr(), M, N, Kd, ldx, ldres, N, float(alpha))
     return out
 
 
@@ -1732,7 +1761,7 @@ def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     N, Kd = weight.shape
     if tile == 18:
         M0 = x.numel() // x.shape[-1]
-        if x2 is not None or N % 320 or split_k < 1 or M0 * max(Kd, N) * 2 >= (1 << 31) or N * Kd * 2 >= (1 << 31):
+        if x2 is not None or N % 320 or split_k < 1 or not _below_2gib(M0 * max(Kd, N)) or not _below_2gib(N * Kd):
             tile = 16                                   # (not a case tile 16 takes on a packed weight: row-major, with tile 16's own fall-backs)
         else:
             weight = _w_tilemajor(weight)
@@ -1749,18 +1778,11 @@ def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     else:
         assert out.dtype == x.dtype and out.shape[-1] == n_out and _rows2d(out)[0] == M and tile != 18
         ldo = _rows2d(out)[1]
-    ldres = 0
-    if residual is not None:
-        assert residual.shape == out.shape
-        _, ldres = _rows2d(residual)
-    if residual2 is not None:
-        assert residual is not None and residual2.shape == out.shape and _rows2d(residual2)[1] == ldres
+    ldres = _ldres(out, residual, residual2)
     ws, ws_bytes = _splitk_workspace(x.device, split_k, M, N)
-    _log_call("own_linear", (M, N, Kd, "geglu" if geglu else f"t{tile}", (residual is not None) + (residual2 is not None)), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16(x.data_ptr(), weight.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N,
-                                           Kd, ldx, ldres, ldo, float(alpha), int(geglu), int(tile), int(split_k),
-                                           ws, ws_bytes, _p(x2), ldx2, k_split, _p(residual2), _stream()),
-               "fmc_linear_bf16")
+    _own_linear("fmc_linear_bf16", "geglu" if geglu else f"t{tile}", M, N, Kd, (residual is not None) + (residual2 is not None),
+                x.data_ptr(), weight.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, ldx, ldres, ldo, float(alpha), int(geglu), int(tile),
+                int(split_k), ws, ws_bytes, _p(x2), ldx2, k_split, _p(residual2))
     return out
 
 
@@ -1834,12 +1856,13 @@ def ln_emit_ok(x: torch.Tensor, weight: torch.Tensor, residual, residual2, ln: L
     N, Kd = weight.shape
     M = x.numel() // x.shape[-1]
     return (LN_EPILOGUE and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-            and x.is_contiguous() and weight.is_contiguous() and N == 320 and Kd % 64 == 0 and M % 160 == 0 and M // 160 > _cus(x.device)
+            and x.is_contiguous() and weight.is_contiguous() and N == 320 and Kd % 64 == 0
+            and _g160_persistent(M, N, x.device, at_least=False)                       # (inherited, not derived: N == 320 -- whole rows in a tile; more tiles than CUs)
             and ln.gamma.numel() == 320 and ln.gamma.dtype == torch.float32 and ln.beta.dtype == torch.float32
             and (ln.pe is None or (ln.pe.dtype == torch.float32 and ln.pe.is_contiguous() and ln.pe.shape[-1] == 320 and ln.pe_inner % 160 == 0
                                    and ln.pe.shape[0] >= ln.pe_frames))
             and (residual is None or (residual.is_contiguous() and residual.dtype == x.dtype))
-            and (residual2 is None or residual2.is_contiguous()) and M * max(Kd, 320) * 2 < (1 << 31) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+            and (residual2 is None or residual2.is_contiguous()) and _below_2gib(M * max(Kd, 320)))
 
 
 def carry_ln(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
@@ -1900,8 +1923,8 @@ def lnc_ok(x: torch.Tensor, weight: torch.Tensor) -> bool:
     N, Kd = weight.shape
     M = x.numel() // x.shape[-1]
     return (LN_EPILOGUE and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-            and x.is_contiguous() and N % 320 == 0 and Kd % 64 == 0 and M % 160 == 0 and (M // 160) * (N // 320) > _cus(x.device)
-            and M * max(Kd, 320) * 2 < (1 << 31) and N * Kd * 2 < (1 << 31) and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+            and x.is_contiguous() and Kd % 64 == 0 and _g160_persistent(M, N, x.device, at_least=False)      # (inherited, not derived: more tiles than CUs)
+            and _below_2gib(M * max(Kd, 320)) and _below_2gib(N * Kd))
 
 
 def linear_lnc(x: torch.Tensor, weight: torch.Tensor, bias, pend, geglu: bool = False) -> torch.Tensor:
@@ -1914,10 +1937,9 @@ def linear_lnc(x: torch.Tensor, weight: torch.Tensor, bias, pend, geglu: bool = 
     n_out = N // 2 if geglu else N
     out = torch.empty(*x.shape[:-1], n_out, dtype=x.dtype, device=x.device)
     ln_epilogue_calls["consumed"] += 1
-    wt = _w_tilemajor(wg) if W_TILEMAJOR else wg
-    _log_call("own_linear", (M, N, Kd, "lnc-geglu" if geglu else "lnc", 0), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_lnc(x.data_ptr(), wt.data_ptr(), out.data_ptr(), M, N, Kd, ldx, n_out, int(geglu), stats.data_ptr(),
-                                               c.data_ptr(), b.data_ptr(), int(W_TILEMAJOR), _stream()), "fmc_linear_bf16_lnc")
+    wt, tilemajor = _packed(wg)
+    _own_linear("fmc_linear_bf16_lnc", "lnc-geglu" if geglu else "lnc", M, N, Kd, 0,
+                x.data_ptr(), wt.data_ptr(), out.data_ptr(), M, N, Kd, ldx, n_out, int(geglu), stats.data_ptr(), c.data_ptr(), b.data_ptr(), tilemajor)
     return out
 
 
@@ -1934,12 +1956,10 @@ def linear_ln(x: torch.Tensor, weight: torch.Tensor, bias, residual, alpha: floa
         ln_out = None
     else:
         stats, ln_out = None, torch.empty_like(out)
-    wt = _w_tilemajor(weight) if W_TILEMAJOR else weight
-    _log_call("own_linear", (M, N, Kd, "ln", (residual is not None) + (residual2 is not None)), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_ln(x.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, ldx, ldres, N,
-                                              float(alpha), _p(residual2), _p(ln_out), ln.gamma.data_ptr(), ln.beta.data_ptr(), float(ln.eps),
-                                              _p(ln.pe), int(ln.pe_inner), int(ln.pe_frames), _p(stats), int(W_TILEMAJOR), _stream()),
-               "fmc_linear_bf16_ln")
+    wt, tilemajor = _packed(weight)
+    _own_linear("fmc_linear_bf16_ln", "ln", M, N, Kd, (residual is not None) + (residual2 is not None),
+                x.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, ldx, ldres, N, float(alpha), _p(residual2), _p(ln_out),
+                ln.gamma.data_ptr(), ln.beta.data_ptr(), float(ln.eps), _p(ln.pe), int(ln.pe_inner), int(ln.pe_frames), _p(stats), tilemajor)
     out._fmc_ln = (stats, ln.key, True) if ln.stats_only else (ln_out, ln.key, False)
     return out
 
@@ -1957,9 +1977,8 @@ def gn_fold_ok(x: torch.Tensor, gn_tag, groups: int, weight: torch.Tensor, ln: O
     M = n_img * hw
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and weight.dtype == torch.bfloat16 and weight.is_contiguous() and weight.shape[1] == C
             and groups == 32 and gn_tag[1] == C and gn_tag[0].shape[0] == n_img and gn_tag[0].shape[1] <= 64 and gn_tag[0].shape[2] == groups
-            and hw % 160 == 0 and C % 64 == 0 and N % 320 == 0 and (M // 160) * (N // 320) >= _cus(x.device) and n_img * N * C * 2 <= GN_FOLD_MAX_BYTES
-            and M * max(C, N) * 2 < (1 << 31) and (ln is None or (LN_EPILOGUE and ln.stats_only and N == 320))
-            and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+            and hw % 160 == 0 and C % 64 == 0 and _g160_persistent(M, N, x.device, at_least=True)      # (inherited, not derived: as many tiles as CUs suffice)
+            and n_img * N * C * 2 <= GN_FOLD_MAX_BYTES and _below_2gib(M * max(C, N)) and (ln is None or (LN_EPILOGUE and ln.stats_only and N == 320)))
 
 
 def linear_gnfold(x: torch.Tensor, gn_tag, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, weight: torch.Tensor, bias,
@@ -1984,9 +2003,8 @@ def linear_gnfold(x: torch.Tensor, gn_tag, gamma: torch.Tensor, beta: torch.Tens
     if ln is not None:
         stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
         ln_epilogue_calls["emitted"] += 1
-    _log_call("own_linear", (M, N, C, "gn-fold", 0), 2.0 * M * N * C)
-    _lib.check(lib.fmc_linear_bf16_imgw(x.data_ptr(), w_img.data_ptr(), b_img.data_ptr(), out.data_ptr(), M, N, C, C, N, hw, _p(stats),
-                                        float(ln.eps) if ln is not None else 0.0, int(W_TILEMAJOR), _stream()), "fmc_linear_bf16_imgw")
+    _own_linear("fmc_linear_bf16_imgw", "gn-fold", M, N, C, 0, x.data_ptr(), w_img.data_ptr(), b_img.data_ptr(), out.data_ptr(), M, N, C, C, N, hw, _p(stats),
+                float(ln.eps) if ln is not None else 0.0, int(W_TILEMAJOR))           # (the fold kernel above has written w_img in that layout)
     if ln is not None:
         out._fmc_ln = (stats, ln.key, True)
     return out
@@ -2004,9 +2022,8 @@ def ff_blocked_ok(x: torch.Tensor, w1_il160: Optional[torch.Tensor], w2: torch.T
     M = x.numel() // x.shape[-1]
     return (x.is_cuda and x.dtype == torch.bfloat16 and w1_il160.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16 and x.is_contiguous()
             and w1_il160.is_contiguous() and w2.is_contiguous() and N1 == 2 * Cff and Cff % 160 == 0 and N2 % 320 == 0 and Kd % 64 == 0
-            and M % 160 == 0 and M >= 16384 and (M // 160) * (N1 // 320) > _cus(x.device) and M * Cff * 2 < (1 << 31)
-            and (residual is None or (residual.is_contiguous() and residual.dtype == x.dtype))
-            and os.environ.get("FMC_G160_PERSIST", "1") != "0")
+            and M >= 16384 and _g160_persistent(M, N1, x.device, at_least=False)          # (inherited, not derived: the GEGLU that writes tile-major asks more tiles than CUs)
+            and _below_2gib(M * Cff) and (residual is None or (residual.is_contiguous() and residual.dtype == x.dtype)))
 
 
 def geglu_linear_blocked(x: torch.Tensor, weight_il160: torch.Tensor, bias_il160) -> torch.Tensor:
@@ -2018,17 +2035,15 @@ def geglu_linear_blocked(x: torch.Tensor, weight_il160: torch.Tensor, bias_il160
     out = torch.empty(*x.shape[:-1], N // 2, dtype=x.dtype, device=x.device)
     if pend is not None:
         stats, gamma, beta, _ = pend
-        wg, c, b = _ln_folded_weight(weight_il160, bias_il160, gamma, beta)
-        _dev(x, wg, c, b, stats)
+        w, c, b = _ln_folded_weight(weight_il160, bias_il160, gamma, beta)
+        _dev(x, w, c, b, stats)
         ln_epilogue_calls["consumed"] += 1
-        wt = _w_tilemajor(wg) if W_TILEMAJOR else wg
-        args = (wt.data_ptr(), None, None, out.data_ptr(), M, N, Kd, 0, 1.0, 1, 0, 1, stats.data_ptr(), c.data_ptr(), b.data_ptr(), int(W_TILEMAJOR))
+        bias, lnc = None, (stats.data_ptr(), c.data_ptr(), b.data_ptr())
     else:
         _dev(x, weight_il160, bias_il160)
-        wt = _w_tilemajor(weight_il160) if W_TILEMAJOR else weight_il160
-        args = (wt.data_ptr(), _p(bias_il160), None, out.data_ptr(), M, N, Kd, 0, 1.0, 1, 0, 1, None, None, None, int(W_TILEMAJOR))
-    _log_call("own_linear", (M, N, Kd, "geglu-blocked", 0), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_ffblk(x.data_ptr(), *args, _stream()), "fmc_linear_bf16_ffblk")
+        w, bias, lnc = weight_il160, _p(bias_il160), (None, None, None)
+    wt, tilemajor = _packed(w)
+    _own_linear("fmc_linear_bf16_ffblk", "geglu-blocked", M, N, Kd, 0, x.data_ptr(), wt.data_ptr(), bias, None, out.data_ptr(), M, N, Kd, 0, 1.0, 1, 0, 1, *lnc, tilemajor)
     return out
 
 
@@ -2045,13 +2060,12 @@ def linear_from_blocked(xb: torch.Tensor, weight: torch.Tensor, bias, residual, 
     if out is None:
         out = torch.empty(*xb.shape[:-1], N, dtype=xb.dtype, device=xb.device)
     assert out.is_contiguous() and out.numel() == M * N and out.dtype == xb.dtype
-    wt = _w_tilemajor(weight) if W_TILEMAJOR else weight
+    wt, tilemajor = _packed(weight)
     assert not partial_tiles or _blocked_storage_ok(xb, M, Kd), "linear_from_blocked: the tile-major operand does not own its padded storage"
-    _log_call("own_linear", (M, N, Kd, "from-blocked-partial" if partial_tiles else "from-blocked", int(residual is not None)), 2.0 * M * N * Kd)
-    name, fn = _entry("fmc_linear_bf16_ffblk", partial_tiles)
     # (the whole-tile entry point is the general blocked GEMM: no GEGLU, no LayerNorm epilogue -- the arguments the partial one does not have)
-    _lib.check(fn(xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, 0 if residual is None else N, float(alpha),
-                  *(() if partial_tiles else (0, 1, 0, None, None, None)), int(W_TILEMAJOR), _stream()), name)
+    _own_linear(_entry("fmc_linear_bf16_ffblk", partial_tiles)[0], "from-blocked-partial" if partial_tiles else "from-blocked", M, N, Kd, int(residual is not None),
+                xb.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, 0 if residual is None else N, float(alpha),
+                *(() if partial_tiles else (0, 1, 0, None, None, None)), tilemajor)
     return out
 
 
@@ -2094,11 +2108,10 @@ def ff_tail(mid_blocked: torch.Tensor, h: torch.Tensor, w_cat: torch.Tensor, b_c
     if gn_hw and not partial_tiles and gn_emit_ok(M, N, Kd, gn_hw, h.dtype):
         part = torch.empty(M // gn_hw, gn_hw // 160, 32, 2, dtype=torch.float32, device=h.device)
         gn_epilogue_calls["emitted"] += 1
-    wt = _w_tilemajor(w_cat) if W_TILEMAJOR else w_cat
-    _log_call("own_linear", (M, N, Kd, "ff-tail-partial" if partial_tiles else "ff-tail", 1), 2.0 * M * N * Kd)
-    name, fn = _entry("fmc_linear_bf16_fftail", partial_tiles)
-    _lib.check(fn(mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(), out.data_ptr(), M, N, Kd, Kd - C,
-                  C, N, _p(part), int(gn_hw if part is not None else 0), int(W_TILEMAJOR), _stream()), name)
+    wt, tilemajor = _packed(w_cat)
+    _own_linear(_entry("fmc_linear_bf16_fftail", partial_tiles)[0], "ff-tail-partial" if partial_tiles else "ff-tail", M, N, Kd, 1,
+                mid_blocked.data_ptr(), h.data_ptr(), wt.data_ptr(), _p(b_cat), tail_residual.data_ptr(), out.data_ptr(), M, N, Kd, Kd - C, C, N, _p(part),
+                int(gn_hw if part is not None else 0), tilemajor)
     if part is not None:
         out._fmc_gn = (part, N)
     return out
@@ -2113,10 +2126,9 @@ def linear_gn(x: torch.Tensor, weight: torch.Tensor, bias, residual, alpha: floa
     part = torch.empty(M // hw, hw // 160, 32, 2, dtype=torch.float32, device=x.device)
     ldres = 0 if residual is None else _rows2d(residual)[1]
     gn_epilogue_calls["emitted"] += 1
-    wt = _w_tilemajor(weight) if W_TILEMAJOR else weight
-    _log_call("own_linear", (M, N, Kd, "gn", (residual is not None) + (residual2 is not None)), 2.0 * M * N * Kd)
-    _lib.check(_lib.load().fmc_linear_bf16_gn(x.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, ldx, ldres, N,
-                                              float(alpha), _p(residual2), part.data_ptr(), int(hw), int(W_TILEMAJOR), _stream()), "fmc_linear_bf16_gn")
+    wt, tilemajor = _packed(weight)
+    _own_linear("fmc_linear_bf16_gn", "gn", M, N, Kd, (residual is not None) + (residual2 is not None),
+                x.data_ptr(), wt.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, N, Kd, ldx, ldres, N, float(alpha), _p(residual2), part.data_ptr(), int(hw), tilemajor)
     out._fmc_gn = (part, N)
     return out
 

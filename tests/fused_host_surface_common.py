@@ -14,7 +14,7 @@ import itertools
 import torch
 
 from tests import fake_kernels
-from tests.halo_host_surface_common import _OnDevice, _Table, rle, unrle  # noqa: F401  (rle / unrle: re-exported to the test)
+from tests.halo_host_surface_common import _OnDevice, _Table, rle, same_table, unrle  # noqa: F401  (rle / same_table / unrle: re-exported to the test)
 
 BF16, F32 = torch.bfloat16, torch.float32
 HWS = list(range(1, 171))

@@ -129,52 +129,52 @@ def workspace_bytes(c, cus):
 
 def expected_kernel(c, cus=DEVICE_CUS):
     """(kernel, form) the C ABI runs for `c` on a device of `cus` compute units, every A/B switch at its default and the workspace of `workspace_bytes`:
-    `linear_impl` (gemm_conv.hip:2993-3085), `launch_gemm` (:2905-2959) and the launchers it calls, restated line by line."""
+    `linear_impl`, `launch_gemm` and the launchers it calls (csrc/gemm_conv.hip), restated line by line."""
     M, N, K = c.shape
     g8 = cus & ~7
     if c.entry == "linear4_bf16":
         return "gemm4_kernel", "plain grid"                                                                    # gemm4.hip:198-215: one kernel
     if c.entry == "linear_fp8_qkv":
-        return "gemm8_kernel<EPI 2, PF 4>", "plain grid"                                                       # :3268 (split_k 1, no stream-K: :3265)
+        return "gemm8_kernel<EPI 2, PF 4>", "plain grid"                                                       # fmc_linear_fp8_qkv (split_k 1, no stream-K)
     if c.entry in ("linear_bf16_ffblk_partial", "linear_bf16_fftail_partial"):
-        assert N % 320 == 0 and -(-M // 160) * (N // 320) >= g8 >= 8                                           # ff_partial_impl, :3282
-        return ("gemm160p_kernel<0, 5, 0, 0, 1, 0, 1>" if c.k_split else "gemm160p_kernel<0, 5, 0, 0, 0, 0, 1>"), "persistent, partial"    # :3305-3306
+        assert N % 320 == 0 and -(-M // 160) * (N // 320) >= g8 >= 8                                           # ff_partial_impl
+        return ("gemm160p_kernel<0, 5, 0, 0, 1, 0, 1>" if c.k_split else "gemm160p_kernel<0, 5, 0, 0, 0, 0, 1>"), "persistent, partial"    # launch_gemm160p, forms 7 | 8
     f32 = c.entry == "linear_x3_f32"
-    tile = 16 if c.tile == 18 else c.tile                                                                      # :3002
+    tile = 16 if c.tile == 18 else c.tile                                                                      # linear_impl
     a_blocked = "x_blocked" in c.form or c.entry == "linear_bf16_fftail"
     a2, res2, epi = c.k_split > 0, "2" in c.extras, int(c.geglu)
-    split = c.split_k if c.split_k > 1 else 1                                                                  # set_split_k, :2961-2989
+    split = c.split_k if c.split_k > 1 else 1                                                                  # set_split_k
     sk, hybrid = c.split_k < 0, c.split_k == -2
     lock = 1 if c.split_k == -3 else (-c.split_k - 16 if c.split_k <= -16 else 0)
-    gemm8_ok = split == 1 and (not a2 or a_blocked)                                                            # :2897 (every operand here is below 2 GiB)
+    gemm8_ok = split == 1 and (not a2 or a_blocked)                                                            # gemm8_ok (every operand here is below 2 GiB)
     g = tile
     assert 1 <= g <= 22, "the table names its tiles (tile 0 = the library's choice is not a launch form)"
-    if g == 17:                                                                                                # :2915-2920
-        if epi == 1 and gemm8_ok and N % 320 == 0 and M % 256 == 0 and not sk and not a2 and not f32 and g8 >= 8 and (M // 256) * (N // 320) > g8:    # :2880
-            return "gemm160p_kernel<1, 8>", "persistent 256 x 320"                                             # launch_gemm256p, :2889
+    if g == 17:                                                                                                # launch_gemm
+        if epi == 1 and gemm8_ok and N % 320 == 0 and M % 256 == 0 and not sk and not a2 and not f32 and g8 >= 8 and (M // 256) * (N // 320) > g8:    # gemm256p_ok
+            return "gemm160p_kernel<1, 8>", "persistent 256 x 320"                                             # launch_gemm256p
         g = 16
-    if g == 16:                                                                                                # :2921-2928
-        if (not a2 or a_blocked) and N % 320 == 0 and not sk:                                                  # gemm8_ok with split_k set aside, gemm160_ok :2827
+    if g == 16:                                                                                                # launch_gemm
+        if (not a2 or a_blocked) and N % 320 == 0 and not sk:                                                  # gemm8_ok with split_k set aside, gemm160_ok
             tiles = -(-M // 160) * (N // 320)
             if split > 1:
                 assert epi == 0
-                return "gemm160_kernel<0, 0>", "split-K + splitk_reduce_kernel"                                # :2838-2845
+                return "gemm160_kernel<0, 0>", "split-K + splitk_reduce_kernel"                                # launch_gemm160
             imgw = c.entry == "linear_bf16_imgw"
-            if not f32 and M % 160 == 0 and g8 >= 8 and (tiles >= g8 if (a_blocked or imgw) else tiles > g8):  # :2852
-                e0 = epi == 0                                                                                  # :2859
+            if not f32 and M % 160 == 0 and g8 >= 8 and (tiles >= g8 if (a_blocked or imgw) else tiles > g8):  # launch_gemm160, g160_persistent_shape
+                e0 = epi == 0                                                                                  # launch_gemm160p
                 form = ((5 if "ln_stats" in c.form else 4) if e0 and imgw else 6 if e0 and a2 else 1 if "lnc" in c.form else 2 if e0 and "ln_out" in c.form
                         else 3 if e0 and "ln_stats" in c.form else 0)
-                args = {0: "", 1: ", 0, 1", 2: ", 1", 3: ", 2", 4: ", 0, 0, 0, 1", 5: ", 2, 0, 0, 1", 6: ", 0, 0, 1"}[form]                             # :2861-2868
+                args = {0: "", 1: ", 0, 1", 2: ", 1", 3: ", 2", 4: ", 0, 0, 0, 1", 5: ", 2, 0, 0, 1", 6: ", 0, 0, 1"}[form]                             # launch_gemm160p
                 return f"gemm160p_kernel<{epi}, 5{args}>", "persistent"
-            return f"gemm160_kernel<0, {epi}>", "plain grid"                                                   # :2874
+            return f"gemm160_kernel<0, {epi}>", "plain grid"                                                   # launch_gemm160
         g = 13
-    if g in (13, 14) and not gemm8_ok:                                                                         # :2929
+    if g in (13, 14) and not gemm8_ok:                                                                         # launch_gemm
         g = 3
-    if g == 15:                                                                                                # :2930-2935, gemm_k320_ok :2801-2805
+    if g == 15:                                                                                                # launch_gemm, gemm_k320_ok :2801-2805
         if epi == 0 and not f32 and K == 320 and N % 320 == 0 and M % 64 == 0 and not a2 and not res2 and split == 1 and not sk:
             return "gemm_k320_kernel<2, 2, " + ("true>" if "r" in c.extras else "false>"), "persistent"       # gemm_k320_cfg default, :2821
         g = 5
-    if epi == 0 and 19 <= g <= 22 and (split != 1 or res2 or sk or f32):                                       # :2937
+    if epi == 0 and 19 <= g <= 22 and (split != 1 or res2 or sk or f32):                                       # launch_gemm
         g = 1
     if g in (13, 14):                                                                                          # launch_gemm8, :2530-2607
         name = f"gemm8_kernel<EPI {epi}, PF {4 if g == 13 else 5}>"
@@ -349,6 +349,21 @@ def table(cus=DEVICE_CUS):
     for st in (True, False):
         out.append(_c("gnfold-imgw" + ("-ln-stats" if st else ""), "linear_bf16_imgw", 16, (4 * 160 * (g8 // 4 + (1 if st else 0)), 320, 64), "",
                       form="ln_stats w_tilemajor" if st else "", want=("gemm160p_kernel<0, 5, " + ("2, 0, 0, 1>" if st else "0, 0, 0, 1>"), "persistent")))
+    # -- the same entry points at exactly the smallest tile count each accepts, N = 320 (the accepted side of `g160_persistent_shape`'s two comparisons): CUs
+    #    tiles where a launch of exactly one round is taken (a tile-major A, per-image weights, the partial forms: ceil), CUs + 1 where more tiles than CUs
+    #    are asked.  Above: ln-* and lnc-plain (CUs + 1), ffblk-x-blocked-alpha, fftail-plain and gnfold-imgw (CUs).  fmc_linear_bf16_gn has no smallest
+    #    count (the plain grid takes the rest); its images of two tiles put the persistent case at CUs + 2
+    P1 = "gemm160p_kernel<1, 5"
+    out.append(_c("lnc-geglu-min", "linear_bf16_lnc", 16, (160 * (g8 + 1), 320, 64), "", geglu=True, form="lnc w_tilemajor", want=(P1 + ", 0, 1>", "persistent")))
+    out.append(_c("ffblk-out-blocked-min", "linear_bf16_ffblk", 16, (160 * (g8 + 1), 320, 64), "b", geglu=True, form="out_blocked w_tilemajor", want=(P1 + ">", "persistent")))
+    out.append(_c("ffblk-out-blocked-lnc-min", "linear_bf16_ffblk", 16, (160 * (g8 + 1), 320, 128), "", geglu=True, form="out_blocked lnc w_tilemajor",
+                  want=(P1 + ", 0, 1>", "persistent")))
+    out.append(_c("ffblk-partial-min", "linear_bf16_ffblk_partial", 16, (160 * (g8 - 1) + 1, 320, 64), "bar", form="x_blocked w_tilemajor"))
+    out.append(_c("fftail-gn-min", "linear_bf16_fftail", 16, (160 * g8, 320, 320), "br", k_split=256, form="gn_partials w_tilemajor",
+                  want=("gemm160p_kernel<0, 5, 0, 0, 1>", "persistent")))
+    out.append(_c("fftail-partial-min", "linear_bf16_fftail_partial", 16, (160 * (g8 - 1) + 81, 320, 192), "br", k_split=128, form="w_tilemajor"))
+    out.append(_c("gnfold-imgw-ln-stats-min", "linear_bf16_imgw", 16, (4 * 160 * (g8 // 4), 320, 64), "", form="ln_stats w_tilemajor",
+                  want=("gemm160p_kernel<0, 5, 2, 0, 0, 1>", "persistent")))
     # -- gemm4.hip: 160 x 160 tiles, 0 - 3 extras
     for n, ex in enumerate(("", "b", "bar", "bar2")):
         out.append(_c(f"linear4-extras{n}", "linear4_bf16", 0, (161, 200, 128) if n % 2 else (321, 168, 64), ex))

@@ -4,6 +4,7 @@ the (return code, message) of failing calls to the launch and pack entry points,
 Nothing here launches: the failing calls are refused by their argument checks (pointers are made-up integers), the routes run on recording
 stand-ins with storage-less tensors."""
 import itertools
+import json
 
 import torch
 
@@ -27,6 +28,18 @@ def rle(seq):
 
 def unrle(runs):
     return [v for v, k in zip(runs[::2], runs[1::2]) for _ in range(k)]
+
+
+def same_table(got, want, what, expand):
+    """Equal tables, naming the first element that differs where they are not (`expand`: (table, value) -> the flat list a value stands for)."""
+    got = json.loads(json.dumps(got))
+    assert [r[:-1] for r in got["rows"]] == [r[:-1] for r in want["rows"]], f"{what}: the rows themselves differ"
+    for g, w in zip(got["rows"], want["rows"]):
+        a, b = expand(got, got["values"][g[-1]]), expand(want, want["values"][w[-1]])
+        if a != b:
+            at = next(i for i, (x, y) in enumerate(zip(a, b)) if x != y)
+            raise AssertionError(f"{what} {g[:-1]}: element {at} is {a[at]}, recorded {b[at]}")
+    assert got == want, what
 
 
 class _Table:

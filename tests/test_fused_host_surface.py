@@ -8,7 +8,6 @@ import os
 import pytest
 
 from tests import fused_host_surface_common as S
-from tests.test_halo_host_surface import _same_table
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fused_host_surface.json")
 
@@ -26,16 +25,16 @@ def K():
 
 
 def test_predicates_and_counts(K, golden, monkeypatch):
-    _same_table(S.predicates(K, monkeypatch), golden["predicates"], "predicates (by index in `names`; element = index into HWS / MS)", lambda data, v: S.unrle(v))
+    S.same_table(S.predicates(K, monkeypatch), golden["predicates"], "predicates (by index in `names`; element = index into HWS / MS)", lambda data, v: S.unrle(v))
 
 
 def test_refused_calls_keep_code_and_message(K, golden):
     want = golden["errors"]
     assert [[want["names"][r[0]], r[1]] for r in want["rows"]] == [list(c[:2]) for c in S.error_calls()]
     assert all(rc in S.REFUSALS for rc, _ in want["values"])                 # (recorded: every row fails before the launch)
-    _same_table(S.errors(K._lib.load()), want, "refused calls (entry point by index in `names`)", lambda data, v: v)
+    S.same_table(S.errors(K._lib.load()), want, "refused calls (entry point by index in `names`)", lambda data, v: v)
 
 
 def test_routes(K, golden, monkeypatch):
     launches = lambda data, runs: [data["launches"][i] for i in S.unrle(runs)]
-    _same_table(S.routes(K, monkeypatch), golden["routes"], "routes (switch set by index in `switches`; element = size and call in order)", launches)
+    S.same_table(S.routes(K, monkeypatch), golden["routes"], "routes (switch set by index in `switches`; element = size and call in order)", launches)

@@ -35,7 +35,7 @@ BF16, F32, U8 = torch.bfloat16, torch.float32, torch.uint8
 # Tile 16 / 17 / 18 (gemm_conv.hip: gemm160p_kernel): 160-row (17: 256-row) x 320-column tiles; the persistent form requests the NEXT tile's operands
 # under the epilogue, so a workgroup's reach past its last tile is one whole tile: 320 rows of A cover both tile heights, and one `[160][32]`-blocked
 # tile column of a tile-major intermediate is 160 x 32 = 5120 elements, less than 320 rows of any width used here (>= 128).
-P_BAND = 320                          # rows of A, residuals, out, ln_out, tile-major intermediates (gemm_conv.hip:3002-3011: tile 16's persistent form only)
+P_BAND = 320                          # rows of A, residuals, out, ln_out, tile-major intermediates (gemm_conv.hip, `linear_impl`: tile 16's persistent form only)
 P_BAND_W = 320                        # rows of W and of its tile-major copy: one 320-column block (hip_ops._w_tilemajor)
 STAT_BAND = 320                       # rows of ln_stats [M][2]: one tile of rows each side
 PART_BAND = 8                         # rows of 64 floats around gn_partials: >= the tiles of one image in these cases, as the existing file's rule
@@ -163,7 +163,7 @@ def test_linear_bf16_geglu_k_lockstep(K):
 
 
 # =====================================================================================================================================
-# The tile-16-only entry points.  Operand names and checks (gemm_conv.hip:2962-3054, `linear_impl`).
+# The tile-16-only entry points.  Operand names and checks (gemm_conv.hip, `linear_impl`).
 # =====================================================================================================================================
 def _w16(g, w, tm, name="w"):
     return g.inp(_tilemajor(w) if tm else w, P_BAND_W, 0, name)
@@ -652,7 +652,7 @@ def test_conv3x3_bf16_8phase_hybrid_and_k_lockstep(K, tile, split_k, upsample):
 
 
 # =====================================================================================================================================
-# fmc_linear_fp8_qkv (gemm_conv.hip:3225-3240: the 8-phase 256 x 256 kernel with an e4m3 epilogue) and fmc_fp8_scales_roll
+# fmc_linear_fp8_qkv (gemm_conv.hip: the 8-phase 256 x 256 kernel with an e4m3 epilogue) and fmc_fp8_scales_roll
 # =====================================================================================================================================
 FP8_TOP = 16.0                         # |acc * inv_scale| <= 16 = byte 0x58: no output byte can equal the sentinel 0x5A (= 20.0), so "every byte written" holds
 

@@ -23,29 +23,17 @@ def K():
     return hip_ops
 
 
-def _same_table(got, want, what, expand):
-    """Equal tables, naming the first element that differs where they are not (`expand`: (table, value) -> the flat list a value stands for)."""
-    got = json.loads(json.dumps(got))
-    assert [r[:-1] for r in got["rows"]] == [r[:-1] for r in want["rows"]], f"{what}: the rows themselves differ"
-    for g, w in zip(got["rows"], want["rows"]):
-        a, b = expand(got, got["values"][g[-1]]), expand(want, want["values"][w[-1]])
-        if a != b:
-            at = next(i for i, (x, y) in enumerate(zip(a, b)) if x != y)
-            raise AssertionError(f"{what} {g[:-1]}: element {at} is {a[at]}, recorded {b[at]}")
-    assert got == want, what
-
-
 def test_predicates_and_counts(K, golden):
-    _same_table(S.predicates(K._lib.load()), golden["predicates"], "predicates (by index in `names`; element = (H - 1) * 70 + W - 1)", S.expand_plane)
+    S.same_table(S.predicates(K._lib.load()), golden["predicates"], "predicates (by index in `names`; element = (H - 1) * 70 + W - 1)", S.expand_plane)
 
 
 def test_refused_calls_keep_code_and_message(K, golden):
     want = golden["errors"]
     assert [[want["names"][r[0]], r[1]] for r in want["rows"]] == [list(c[:2]) for c in S.error_calls()]
     assert all(rc in S.REFUSALS for rc, _ in want["values"])                 # (recorded: every row fails before the launch)
-    _same_table(S.errors(K._lib.load()), want, "refused calls (entry point by index in `names`)", lambda data, v: v)
+    S.same_table(S.errors(K._lib.load()), want, "refused calls (entry point by index in `names`)", lambda data, v: v)
 
 
 def test_routes(K, golden, monkeypatch):
     launches = lambda data, runs: [data["launches"][i] for i in S.unrle(runs)]
-    _same_table(S.routes(K, monkeypatch), golden["routes"], "routes (switch set by index in `switches`; element = (size, channels) in order)", launches)
+    S.same_table(S.routes(K, monkeypatch), golden["routes"], "routes (switch set by index in `switches`; element = (size, channels) in order)", launches)
