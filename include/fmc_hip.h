@@ -201,6 +201,26 @@ int fmc_sampler_step(const void* eps_uc, const float* x, const void* noise, cons
                      const float* hist2, float* x_out, float* m_out, void* x_in, int64_t n, int has_uncond, int n_hist,
                      int in_reps, fmc_sampler_coef coef, int dtype, int in_dtype, void* stream);
 
+/* Sliding windows ("multidiff", pipeline_animation_cm_om.py:687-720): the average of the windows' guided predictions and the step
+ * of fmc_sampler_step, one pass over the full latents x [BC, Ftot, hw] fp32, Ftot = (W - 1) stride + F.  Window w covers frames
+ * [w stride, w stride + F); the windows that cover frame f are w_lo = max(0, ceil((f - F + 1) / stride)) .. w_hi = min(W - 1,
+ * floor(f / stride)), cnt = w_hi - w_lo + 1 of them.  Per element (bc, f, s), fp32:
+ *     e_w = has_uncond ? eu_w + g (ec_w - eu_w) : e0_w        at window w's own frame f - w stride
+ *     e   = (sum over w = w_lo .. w_hi, ascending, of e_w) / cnt
+ *     m, x' as in fmc_sampler_step from (x, e, hist, noise);   x_out = x', m_out = m
+ *     x_in[r][w][bc][f - w stride][s] = (in_dtype)(in_scale x')   for every covering window w and r < in_reps
+ *   eps, x_in : one buffer each; element (r, w, bc, f_local, s) sits at base + r stride_r + w stride_w + (bc F + f_local) hw + s
+ *               (strides in elements; r = 0 unconditional, 1 conditional for eps with has_uncond, else only r = 0 is read)
+ *   noise (dtype), hist0..2, m_out (fp32) : [BC, Ftot, hw] like x;  x_out may alias x, m_out any hist[j]; x_in aliases nothing
+ * Refused (FMC_E_SHAPE): stride < 1 or > F, W < 1, F < 1, in_reps > 2, n_hist > 3, 2^31 or more rows or work items (element
+ * offsets are 64-bit).  Pointers need the alignment of their element only.  Windows that do not overlap (stride == F, or
+ * W = 1) are fmc_sampler_step on every contiguous (bc, window) block of F hw elements: its kernel is launched per block (W = 1: once
+ * on all BC F hw elements), and gives each block the plain step's bits. */
+int fmc_window_step(const void* eps, int64_t eps_stride_r, int64_t eps_stride_w, const float* x, const void* noise,
+                    const float* hist0, const float* hist1, const float* hist2, float* x_out, float* m_out, void* x_in,
+                    int64_t in_stride_r, int64_t in_stride_w, int BC, int F, int stride, int W, int hw, int has_uncond,
+                    int n_hist, int in_reps, fmc_sampler_coef coef, int dtype, int in_dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogue:  out = alpha * (x @ w^T + bias) + residual      (epilogue 0)
  *                                      out = (x @ wa^T + ba) * gelu_erf(x @ wg^T + bg)  (epilogue 1, GEGLU)

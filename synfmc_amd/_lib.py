@@ -52,6 +52,8 @@ SIGNATURES = {
                                   c_void_p]),
     "fmc_sampler_step_elems_per_trip": (c_int64, []),
     "fmc_sampler_step": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_int, c_int, SamplerCoef, c_int, c_int, c_void_p]),
+    "fmc_window_step": (c_int, [c_void_p, c_int64, c_int64] + [c_void_p] * 8 + [c_int64, c_int64] + [c_int] * 8 +
+                                [SamplerCoef, c_int, c_int, c_void_p]),
     "fmc_linear_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64,
                                 c_int64, c_int64, c_float, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                 c_void_p, c_void_p]),

@@ -931,6 +931,55 @@ def sampler_step(eps: torch.Tensor, x: torch.Tensor, *, guidance: float = 1.0, h
     return x_out
 
 
+def _window_view(t: torch.Tensor, what: str):
+    """`[R, W, B, C, F, ...]` with the trailing `[B, C, F, ...]` block dense -> (stride_r, stride_w) in elements."""
+    assert t.ndim >= 6, f"{what}: [R, W, B, C, F, ...]"
+    assert t[0, 0].is_contiguous(), f"{what}: every [B, C, F, ...] block has to be dense"
+    return int(t.stride(0)), int(t.stride(1))
+
+
+def window_step(eps: torch.Tensor, x: torch.Tensor, *, overlap: int, guidance: float = 1.0, m_x: float = 0.0, m_e: float = 0.0,
+                m_clamp: float = 0.0, c_x: float = 1.0, c_e: float = 0.0, c_m: float = 0.0, c_n: float = 0.0, c_h=(), hist=(),
+                noise: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None, m_out: Optional[torch.Tensor] = None,
+                x_in: Optional[torch.Tensor] = None, in_scale: float = 1.0) -> torch.Tensor:
+    """Sliding windows: the average of the windows' guided predictions + one sampler step (`fmc_window_step`; the formula is in
+    include/fmc_hip.h).  eps `[R, W, B, C, F, ...]` with R = 2 (uncond, cond) or 1, x fp32 latents `[B, C, Ftot, ...]` with
+    `Ftot = W (F - overlap) + overlap`; `hist`, `noise`, `m_out` like x.  eps and `x_in` `[R', W, B, C, F, ...]` (R' = 1 or 2) may be
+    any view whose `[B, C, F, ...]` blocks are dense: `[W, R, B, ...]` storage is `t.transpose(0, 1)`.  `x_in` receives
+    `in_scale * x'` at every covering window's own frame.  Returns `x_out` (a new tensor when not given)."""
+    _dev(eps, x, noise, x_out, m_out, x_in, *hist)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.ndim >= 4
+    R, W, B, C, F = (int(v) for v in eps.shape[:5])
+    e_sr, e_sw = _window_view(eps, "eps")
+    stride = F - int(overlap)
+    hw = int(math.prod(x.shape[3:]))
+    assert R in (1, 2) and tuple(x.shape[:2]) == (B, C) and tuple(eps.shape[5:]) == tuple(x.shape[3:])
+    if stride < 1 or overlap < 0:
+        raise ValueError(f"window_step: overlap {overlap} of windows of {F} frames")
+    assert x.shape[2] == (W - 1) * stride + F, f"window_step: {W} windows of {F} frames overlapping by {overlap} cover " \
+                                               f"{(W - 1) * stride + F} frames, the latents hold {x.shape[2]}"
+    n = x.numel()
+    assert len(hist) == len(c_h) <= 3 and all(h.dtype == torch.float32 and h.is_contiguous() and h.numel() == n for h in hist)
+    assert noise is None or (noise.dtype == eps.dtype and noise.is_contiguous() and noise.numel() == n)
+    assert m_out is None or (m_out.dtype == torch.float32 and m_out.is_contiguous() and m_out.numel() == n)
+    if x_out is None:
+        x_out = torch.empty_like(x)
+    assert x_out.dtype == torch.float32 and x_out.is_contiguous() and x_out.numel() == n
+    in_reps, i_sr, i_sw = 0, 0, 0
+    if x_in is not None:
+        assert tuple(x_in.shape[1:]) == tuple(eps.shape[1:]) and x_in.shape[0] in (1, 2)
+        in_reps = int(x_in.shape[0])
+        i_sr, i_sw = _window_view(x_in, "x_in")
+    coef = _lib.SamplerCoef(float(guidance), float(m_x), float(m_e), float(m_clamp), float(c_x), float(c_e), float(c_m), float(c_n),
+                            (ctypes.c_float * 3)(*[float(c) for c in c_h]), float(in_scale))
+    hp = [h.data_ptr() for h in hist] + [None] * (3 - len(hist))
+    _log_call("window_step", (n, W, F, int(overlap), R, len(hist), noise is not None, in_reps), 0.0)
+    _lib.check(_lib.load().fmc_window_step(eps.data_ptr(), e_sr, e_sw, x.data_ptr(), _p(noise), hp[0], hp[1], hp[2], x_out.data_ptr(),
+                                           _p(m_out), _p(x_in), i_sr, i_sw, B * C, F, stride, W, hw, int(R == 2), len(hist), in_reps, coef,
+                                           _dt(eps), _dt(x_in) if x_in is not None else _dt(eps), _stream()), "fmc_window_step")
+    return x_out
+
+
 # --------------------------------------------------------------------------------------------
 # bf16 MFMA GEMM / implicit 3x3 conv with fused epilogues
 # --------------------------------------------------------------------------------------------

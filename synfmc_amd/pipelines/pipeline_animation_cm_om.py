@@ -21,6 +21,11 @@ What changes under the hood (one denoising step = one U-Net forward at CFG batch
 
 `AnimationPipeline` (:40-440) is the plain text-to-video loop of the LoRA-only configuration (BASELINE configs[1]):
 base U-Net, no pose encoder, sliding-window "multidiff" blending included.
+
+Sliding windows (`multidiff_total_steps > 1`) run under camera and object control too: the reference stops at an assert (:690)
+because it never slices `traj_features`; here the windows go through the U-Net as batch entries with per-window text, camera and
+OMC features gathered once per clip, and `fmc_window_step` averages the guided predictions over the overlaps, steps the full
+latents and writes every window's next model input (`_window_loop`; `window_batch` caps the windows per U-Net call).
 """
 from __future__ import annotations
 
@@ -139,6 +144,10 @@ class _GraphedUNet:
         return self.out
 
 
+_CLIP_PRODUCTS = ("_pose_term_cache", "_qkv_fold_cache", "_text_kv")      # what the modules keep per clip, one entry each
+_LEGACY_WINDOWS = object()             # `AnimationPipeline(window_batch=...)` not given: the torch-op window loop and its bits
+
+
 def _weights_version(module) -> int:
     """Fingerprint of everything a captured graph of `module` reads by address or was specialised on: identity, storage and version of
     every parameter and buffer (`p.data = ...`, `load_state_dict(assign=True)`, in-place updates), the attention-processor classes, and
@@ -229,6 +238,7 @@ class AnimationPipeline:
     def _prologue(self, prompt, height, width, callback_steps, latents, num_videos_per_prompt, guidance_scale,
                   negative_prompt, prompt_embeds, device, eta):
         unet = self.unet
+        self._slot_products = {}                    # (the eager window chunks' per-clip products: `_runner`)
         if hasattr(unet, "invalidate_text_conditioning"):
             unet.invalidate_text_conditioning()     # a new clip: no text k | v of the previous prompt survives (they are re-made once below / by the runner)
         height = height or unet.config.sample_size * self.vae_scale_factor
@@ -252,15 +262,21 @@ class AnimationPipeline:
         text = prompt_embeds.to(device=device, dtype=unet.dtype)
         return height, width, do_cfg, batch_size, text
 
-    def _runner(self, x_shape, text, pose_feats, traj, use_graph, t_float: bool = False):
+    def _runner(self, x_shape, text, pose_feats, traj, use_graph, t_float: bool = False, slot=None):
         """The U-Net step as a callable `(x, t) -> eps`: a cached HIP graph (refilled with this clip's conditioning) or eager.
-        `t_float`: the timestep table has a fractional entry, which has to reach the U-Net untruncated."""
+        `t_float`: the timestep table has a fractional entry, which has to reach the U-Net untruncated.  `slot`: the chunk of windows
+        this runner serves when a clip's windows go through the U-Net in several calls, each with conditioning of its own: a graph of
+        its own per slot, and on the eager path the modules' per-clip products (pose terms, folded q | k | v terms, the text's k | v)
+        of the slot's first call are put back before every later one, so that they are computed once per clip and slot."""
         unet = self.unet
         shared = bool(getattr(self, "_cfg_shared", False)) and getattr(unet, "_accepts_cfg_shared_input", False)   # (a foreign U-Net never sees the keyword)
         skw = {"cfg_shared_input": True} if shared else {}
         if not use_graph:
-            if hasattr(unet, "prepare_text_conditioning") and not torch.is_grad_enabled():
+            if slot is None and hasattr(unet, "prepare_text_conditioning") and not torch.is_grad_enabled():
                 unet.prepare_text_conditioning(text)     # once per clip, before the loop (SURVEY section 8 f2) -- not inside step 1
+            # (a slot's text k | v are made by its first call and kept with its other per-clip products: preparing every slot here would
+            # only overwrite the modules' one entry slot after slot)
+            kept = None if slot is None else self._slot_products.setdefault(slot, {})
             def eager(x, t):
                 kw = {}
                 if pose_feats is not None:
@@ -268,12 +284,18 @@ class AnimationPipeline:
                     if traj is not None or getattr(unet, "_pass_traj_none", False):    # (UNet3DConditionModelPoseCond takes no traj_features)
                         kw["traj_features"] = traj
                 tt = torch.tensor(float(t), dtype=torch.float32, device=x.device) if t_float else torch.tensor(int(t), device=x.device)
-                return unet(x, tt, encoder_hidden_states=text, **skw, **kw).sample
+                for m, entries in (kept or {}).items():
+                    m.__dict__.update(entries)
+                out = unet(x, tt, encoder_hidden_states=text, **skw, **kw).sample
+                if kept is not None and not kept:
+                    kept.update({m: {k: m.__dict__[k] for k in _CLIP_PRODUCTS if m.__dict__.get(k) is not None} for m in unet.modules()
+                                 if any(m.__dict__.get(k) is not None for k in _CLIP_PRODUCTS)})
+                return out
             return eager
         from .. import hip_ops as K
         # (`hip_ops.PARTIAL_TILES` and `hip_ops.FP8_FF` decide launches that a captured graph replays: a graph captured under another setting is not this step's)
         key = (tuple(x_shape), tuple(text.shape), unet.dtype, pose_feats is not None, traj is not None,
-               shared, bool(t_float), bool(K.PARTIAL_TILES), bool(K.FP8_FF), _weights_version(unet))
+               shared, bool(t_float), bool(K.PARTIAL_TILES), bool(K.FP8_FF), slot, _weights_version(unet))
         r = self._runners.get(key)
         if r is None:
             for k in [k for k in self._runners if k[:-1] == key[:-1]]:      # same shapes, stale weights: drop the graph
@@ -303,6 +325,62 @@ class AnimationPipeline:
             x_in = None                                     # sliding windows: the inputs are slices, made per window
         return True, t_float, dict(eta=eta, generator=generator), x_in
 
+    def _window_loop(self, latents, single, overlap, windows, text, pose_w, traj_w, window_batch, use_graph, timesteps, guidance_scale,
+                     do_cfg, eta, generator, omcm_min_step, callback, callback_steps):
+        """Sliding windows on `fmc_window_step`.  The windows go through the U-Net as batch entries `[R][W_chunk][B]` (R: uncond,
+        cond), `window_batch` of them per call (None: all); text, camera (`pose_w`: per window, per level `[B, c, F, h, w]`, or None)
+        and OMC features (`traj_w`, likewise) are gathered per chunk ONCE per clip, and every chunk has a runner of its own, so that
+        its pose terms, folded q | k | v terms and text k | v are made once per clip.  The kernel averages the guided predictions
+        over the overlaps, steps the full latents and writes every window's next model input (reference :687-720)."""
+        unet, sch = self.unet, self.scheduler
+        if not hasattr(sch, "step_windows"):
+            raise NotImplementedError(f"{type(sch).__name__} has no step_windows")
+        if window_batch is not None and (not isinstance(window_batch, int) or window_batch < 1):
+            raise ValueError(f"window_batch {window_batch!r}: None (all windows in one U-Net call) or a positive int")
+        B, R, W = latents.shape[0], 2 if do_cfg else 1, windows
+        stride = single - overlap
+        per = W if window_batch is None else min(window_batch, W)
+        chunks = [(k, min(k + per, W)) for k in range(0, W, per)]
+        blk = (B, latents.shape[1], single) + tuple(latents.shape[3:])
+        # one buffer for every window's model input and one for the predictions, addressed by (stride_r, stride_w): [R][W][B] storage is
+        # one U-Net batch; with one window per call [W][R][B] storage makes every call's batch dense
+        per_window = per == 1 and W > 1
+        def buffer():
+            store = torch.empty(((W, R) if per_window else (R, W)) + blk, dtype=unet.dtype, device=latents.device)
+            return store.transpose(0, 1) if per_window else store
+        x_in = buffer()
+        eps = buffer() if len(chunks) > 1 else None
+        first = sch.scale_model_input(latents, timesteps[0])
+        for w in range(W):
+            x_in[:, w] = first[:, :, w * stride:w * stride + single]
+        t_float = any(not float(t).is_integer() for t in timesteps)
+        uses_traj = [traj_w is not None and not (omcm_min_step > 0 and t < omcm_min_step) for t in timesteps]      # reference :682-685
+        cl3d = lambda v: v.contiguous(memory_format=torch.channels_last_3d)
+        runs = {}
+        for ci, (k0, k1) in enumerate(chunks):              # every runner of the clip before its first step
+            n = k1 - k0
+            text_c = text.reshape((R, 1, B) + tuple(text.shape[1:])).expand((R, n, B) + tuple(text.shape[1:])) \
+                .reshape((R * n * B,) + tuple(text.shape[1:])).contiguous()
+            pose_c = traj_c = None
+            if pose_w is not None:
+                pose_c = [cl3d(torch.cat([torch.cat([pose_w[w][lv] for w in range(k0, k1)])] * R)) for lv in range(len(pose_w[0]))]
+            if traj_w is not None:
+                traj_c = [cl3d(torch.cat([traj_w[w][lv] for w in range(k0, k1)]).to(unet.dtype)) for lv in range(len(traj_w[0]))]
+            for key in sorted(set(uses_traj)):
+                runs[ci, key] = self._runner((R * n * B,) + blk[1:], text_c, pose_c, traj_c if key else None, use_graph, t_float,
+                                             slot=ci if len(chunks) > 1 else None)
+        for i, t in enumerate(timesteps):
+            for ci, (k0, k1) in enumerate(chunks):
+                out = runs[ci, uses_traj[i]](x_in[:, k0:k1].reshape((R * (k1 - k0) * B,) + blk[1:]), t)
+                if eps is not None:
+                    eps[:, k0:k1].copy_(out.reshape((R, k1 - k0) + blk))
+            e = eps if eps is not None else out.contiguous().view((R, W) + blk)
+            latents = sch.step_windows(e, t, latents, guidance_scale, overlap, eta=eta, generator=generator, x_in=x_in)
+            if callback is not None and i % callback_steps == 0:
+                callback(i, t, latents)
+        self._slot_products = {}                            # (the chunks' per-clip tensors are not kept beyond the clip)
+        return latents
+
     def _finish(self, latents, output_type, return_dict):
         if output_type == "latent":
             video = latents
@@ -322,7 +400,9 @@ class AnimationPipeline:
                  latents: Optional[torch.Tensor] = None, output_type: Optional[str] = "tensor",
                  return_dict: bool = True, callback: Optional[Callable] = None, callback_steps: Optional[int] = 1,
                  multidiff_total_steps: int = 1, multidiff_overlaps: int = 12, prompt_embeds=None,
-                 use_graph: bool = True, **kwargs):
+                 use_graph: bool = True, window_batch=_LEGACY_WINDOWS, **kwargs):
+        """`window_batch` (None: all windows in one U-Net call, or an int: at most that many per call) moves the sliding windows onto
+        `fmc_window_step` (`_window_loop`); not given, the windows run one after another on torch ops, with the bits they always had."""
         unet = self.unet
         device = next(unet.parameters()).device
         height, width, do_cfg, batch_size, text = self._prologue(
@@ -334,6 +414,12 @@ class AnimationPipeline:
         video_length = multidiff_total_steps * (video_length - multidiff_overlaps) + multidiff_overlaps       # :369
         latents = self.prepare_latents(batch_size * num_videos_per_prompt, unet.in_channels, video_length, height,
                                        width, text.dtype, device, generator, latents).contiguous()
+        if multidiff_total_steps > 1 and window_batch is not _LEGACY_WINDOWS:
+            if not 0 <= multidiff_overlaps < single:
+                raise ValueError(f"multidiff_overlaps {multidiff_overlaps}: windows of {single} frames overlap by 0 .. {single - 1}")
+            latents = self._window_loop(latents, single, multidiff_overlaps, multidiff_total_steps, text, None, None, window_batch,
+                                        use_graph, timesteps, guidance_scale, do_cfg, eta, generator, 0, callback, callback_steps)
+            return self._finish(latents, output_type, return_dict)
         x_shape = (latents.shape[0] * (2 if do_cfg else 1), latents.shape[1], single) + tuple(latents.shape[3:])
         fused, t_float, step_kw, x_in = self._sampler_path(eta, generator, timesteps, x_shape, latents, do_cfg)
         run = self._runner(x_shape, text, None, None, use_graph, t_float)
@@ -373,6 +459,58 @@ class CameraObjCtrlPipeline(AnimationPipeline):
         super().__init__(vae, text_encoder, tokenizer, unet, scheduler)
         self.pose_encoder = pose_encoder
 
+    def _frame_limit(self):
+        """Frames the Camera Encoder can see at once: the length of its temporal positional table (None: it has none)."""
+        from ..models.motion_module import PositionalEncoding
+        mods = self.pose_encoder.modules() if hasattr(self.pose_encoder, "modules") else []
+        sizes = [int(m.pe.shape[1]) for m in mods if isinstance(m, PositionalEncoding)]
+        return min(sizes) if sizes else None
+
+    def _window_conditioning(self, pose_embedding, traj_features, single, overlap, windows, batch):
+        """Camera and OMC features per window: `(pose_w, traj_w)`, each a list over the windows of per-level `[B, c, F, h, w]`
+        tensors (`traj_w` None without OMC features).  Tensor forms cover all `Ftot` frames and are sliced (reference :700); list
+        forms hold one entry per window (reference :646-653)."""
+        stride = single - overlap
+        total = (windows - 1) * stride + single
+        cut = lambda levels: [[x[:, :, w * stride:w * stride + single] for x in levels] for w in range(windows)]
+        if isinstance(pose_embedding, (list, tuple)):
+            for pe in pose_embedding:
+                if pe.ndim != 5 or pe.shape[2] != single:
+                    raise ValueError(f"every pose embedding of the list is [B, 6, {single}, H, W]: got {tuple(pe.shape)}")
+            bs = pose_embedding[0].shape[0]
+            pose_w = [features_to_video(self.pose_encoder(pe), bs) for pe in pose_embedding]
+        else:
+            if pose_embedding.ndim != 5 or pose_embedding.shape[2] != total:
+                raise ValueError(f"pose_embedding covers {tuple(pose_embedding.shape)}: {windows} windows of {single} frames overlapping "
+                                 f"by {overlap} need [B, 6, {total}, H, W] (or a list of one embedding per window)")
+            limit = self._frame_limit()
+            if limit is not None and total > limit:
+                raise ValueError(f"pose_embedding as one tensor is encoded in one pass over {total} frames, and the Camera Encoder's "
+                                 f"positional table holds {limit}: pass a list of one embedding per window")
+            bs = pose_embedding.shape[0]
+            pose_w = cut(features_to_video(self.pose_encoder(pose_embedding), bs))
+        traj_w = None
+        if traj_features is not None:
+            if isinstance(traj_features[0], (list, tuple)):
+                if len(traj_features) != windows:
+                    raise ValueError(f"traj_features lists {len(traj_features)} windows, multidiff_total_steps is {windows}")
+                traj_w = [list(levels) for levels in traj_features]
+                frames = {int(x.shape[2]) for levels in traj_w for x in levels}
+                if frames != {single}:
+                    raise ValueError(f"every window's traj_features cover {single} frames: got {sorted(frames)}")
+            else:
+                frames = {int(x.shape[2]) for x in traj_features}
+                if frames != {total}:
+                    raise ValueError(f"traj_features cover {sorted(frames)} frames: {windows} windows of {single} frames overlapping by "
+                                     f"{overlap} need {total} (or a list of one per-level list per window)")
+                traj_w = cut(list(traj_features))
+            if any(x.shape[0] != batch for levels in traj_w for x in levels):
+                raise ValueError(f"OMC features do not cover the {batch} clips of the latents")
+        if bs != batch:
+            raise ValueError(f"camera features cover {bs} clips but the latents hold {batch} "
+                             "(num_videos_per_prompt > 1 needs the conditioning repeated by the caller)")
+        return pose_w, traj_w
+
     # ---- the denoising loop (the metric's unit) ------------------------------------------------------
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None], pose_embedding: torch.Tensor, video_length: Optional[int],
@@ -382,18 +520,41 @@ class CameraObjCtrlPipeline(AnimationPipeline):
                  latents: Optional[torch.Tensor] = None, output_type: Optional[str] = "tensor",
                  return_dict: bool = True, callback: Optional[Callable] = None, callback_steps: Optional[int] = 1,
                  multidiff_total_steps: int = 1, multidiff_overlaps: int = 12, prompt_embeds=None,
-                 use_graph: bool = True, pose_embedding_unshuffled: bool = False, **kwargs):
-        assert multidiff_total_steps == 1                                    # reference :690
+                 use_graph: bool = True, pose_embedding_unshuffled: bool = False, window_batch: Optional[int] = None, **kwargs):
+        """`multidiff_total_steps > 1`: sliding windows of `video_length` frames overlapping by `multidiff_overlaps` (the reference
+        stops at an assert, :690, because it never slices `traj_features`; its slicing of the camera features, :646-653 and :697-701,
+        and its average, :715-717, are what runs here).  `pose_embedding`: a 5-d tensor over all frames, encoded once and sliced per
+        window, or a list of one tensor per window, each encoded on its own.  `traj_features`: per-level tensors over all frames, or a
+        list of one per-level list per window.  `window_batch`: windows per U-Net call (None: all)."""
         unet = self.unet
-        device = pose_embedding.device
+        windows = int(multidiff_total_steps)
+        pose_list = isinstance(pose_embedding, (list, tuple))
+        if windows > 1:
+            if not 0 <= multidiff_overlaps < video_length:
+                raise ValueError(f"multidiff_overlaps {multidiff_overlaps}: windows of {video_length} frames overlap by 0 .. {video_length - 1}")
+            if pose_embedding_unshuffled:
+                raise ValueError("pose_embedding_unshuffled takes one window (multidiff_total_steps=1)")
+            if pose_list and len(pose_embedding) != windows:
+                raise ValueError(f"pose_embedding lists {len(pose_embedding)} windows, multidiff_total_steps is {windows}")
+        elif pose_list:
+            raise ValueError("a list of pose embeddings is one per window: it needs multidiff_total_steps > 1")
+        device = (pose_embedding[0] if pose_list else pose_embedding).device
         height, width, do_cfg, batch_size, text = self._prologue(
             prompt, height, width, callback_steps, latents, num_videos_per_prompt, guidance_scale, negative_prompt,
             prompt_embeds, device, eta)
 
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         timesteps = self.scheduler._timesteps_host
+        single = video_length
+        video_length = windows * (single - multidiff_overlaps) + multidiff_overlaps if windows > 1 else single      # :369
         latents = self.prepare_latents(batch_size * num_videos_per_prompt, unet.in_channels, video_length, height,
                                        width, text.dtype, device, generator, latents).contiguous()
+        if windows > 1:
+            pose_w, traj_w = self._window_conditioning(pose_embedding, traj_features, single, multidiff_overlaps, windows, latents.shape[0])
+            latents = self._window_loop(latents, single, multidiff_overlaps, windows, text, pose_w, traj_w, window_batch, use_graph,
+                                        timesteps, guidance_scale, do_cfg, eta, generator, kwargs.get("omcm_min_step", 0), callback,
+                                        callback_steps)
+            return self._finish(latents, output_type, return_dict)
 
         # camera features: once per clip (reference :657-669)
         if pose_embedding_unshuffled:

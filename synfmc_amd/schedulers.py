@@ -7,7 +7,8 @@ Host side: the beta schedule, the timestep and sigma tables and the coefficients
 tables diffusers keeps).  Device side: `step_cfg` runs the classifier-free-guidance combine and the update as ONE launch on fp32
 latents -- `fmc_cfg_ddim_step` for the configuration the FMC configs use (DDIM, eta = 0, epsilon, no clipping, leading spacing),
 `fmc_sampler_step` for everything else: every update here is `x' = c_x x + c_e e + c_m m + sum c_h[j] hist[j] + c_n noise` with
-`m = clamp(m_x x + m_e e)` the x0 prediction, and the kernel also writes the next step's model input.
+`m = clamp(m_x x + m_e e)` the x0 prediction, and the kernel also writes the next step's model input.  `step_windows` is the same step
+for sliding windows: one prediction per window, averaged where windows overlap, on `fmc_window_step` with the same coefficients.
 
 The timestep and sigma tables follow diffusers 0.24.0 as read, not as run: no copy of the library was at hand."""
 from __future__ import annotations
@@ -168,6 +169,17 @@ class DDIMScheduler:
             noise = variance_noise.to(eps.dtype).contiguous() if variance_noise is not None else _draw_noise(latents, eps, generator)
         return K.sampler_step(eps, latents, guidance=guidance_scale, has_uncond=has_uncond, noise=noise, x_in=x_in, **c)
 
+    def step_windows(self, eps: torch.Tensor, timestep: int, latents: torch.Tensor, guidance_scale: float, overlap: int,
+                     eta: float = 0.0, generator=None, x_in=None, use_clipped_model_output: bool = False, variance_noise=None) -> torch.Tensor:
+        """Sliding windows: eps `[R, W, B, C, F, ...]` (R = 2: uncond, cond), one prediction per window of F frames overlapping by
+        `overlap`; latents fp32 `[B, C, Ftot, ...]`.  The blend and the step are one `fmc_window_step` launch (the plain
+        configuration included); `x_in` `[R', W, B, C, F, ...]` receives every window's next model input."""
+        c = self._coefs(int(timestep), float(eta), use_clipped_model_output)
+        noise = None
+        if eta > 0.0:
+            noise = variance_noise.to(eps.dtype).contiguous() if variance_noise is not None else _draw_noise(latents, eps, generator)
+        return K.window_step(eps, latents, overlap=overlap, guidance=guidance_scale, noise=noise, x_in=x_in, **c)
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, generator=None,
              variance_noise=None, **kwargs):
         x = sample.float().contiguous()
@@ -316,6 +328,20 @@ class EulerDiscreteScheduler(_SigmaScheduler):
         self._step_index = i + 1
         return out
 
+    def step_windows(self, eps, timestep, latents, guidance_scale, overlap, eta: float = 0.0, generator=None, x_in=None,
+                     noise=None) -> torch.Tensor:
+        """As `DDIMScheduler.step_windows`; the windows' predictions were made on `scale_model_input` of their frames."""
+        i = self._index_for(timestep)
+        c = self._coefs(i)
+        if self._stochastic:
+            noise = noise.to(eps.dtype).contiguous() if noise is not None else _draw_noise(latents, eps, generator)
+        else:
+            noise = None
+        out = K.window_step(eps, latents, overlap=overlap, guidance=guidance_scale, noise=noise, x_in=x_in,
+                            in_scale=self.next_input_scale(), **c)
+        self._step_index = i + 1
+        return out
+
 
 class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
     """diffusers 0.24.0 `EulerAncestralDiscreteScheduler`: the Euler step to `sigma_down`, plus `sigma_up` of fresh noise."""
@@ -429,8 +455,16 @@ class DPMSolverMultistepScheduler(_SigmaScheduler):
 
     def step_cfg(self, eps, timestep, latents, guidance_scale, has_uncond, eta: float = 0.0, generator=None, x_in=None) -> torch.Tensor:
         """As `DDIMScheduler.step_cfg`.  `eta` and `generator` are accepted and ignored (a deterministic solver)."""
+        return self._multistep(eps.contiguous(), timestep, latents, x_in,
+                               lambda e, **kw: K.sampler_step(e, latents, guidance=guidance_scale, has_uncond=has_uncond, **kw))
+
+    def step_windows(self, eps, timestep, latents, guidance_scale, overlap, eta: float = 0.0, generator=None, x_in=None) -> torch.Tensor:
+        """As `DDIMScheduler.step_windows`; the history holds x0 predictions of the full latents' shape."""
+        return self._multistep(eps, timestep, latents, x_in,
+                               lambda e, **kw: K.window_step(e, latents, overlap=overlap, guidance=guidance_scale, **kw))
+
+    def _multistep(self, eps, timestep, latents, x_in, launch) -> torch.Tensor:
         i = self._index_for(timestep)
-        eps = eps.contiguous()
         order_max = self.config.solver_order
         if i == 0 or len(self._hist) != order_max or self._hist[0].shape != latents.shape or self._hist[0].device != latents.device:
             self._hist = [torch.empty_like(latents) for _ in range(order_max)]       # (first step after set_timesteps)
@@ -438,7 +472,7 @@ class DPMSolverMultistepScheduler(_SigmaScheduler):
         c = self._coefs(i, order)
         hist = [self._hist[(i - 1 - j) % order_max] for j in range(order - 1)]
         m_out = self._hist[i % order_max] if order_max > 1 else None           # over the oldest slot; order 1 keeps no history
-        out = K.sampler_step(eps, latents, guidance=guidance_scale, has_uncond=has_uncond, hist=hist, m_out=m_out, x_in=x_in, **c)
+        out = launch(eps, hist=hist, m_out=m_out, x_in=x_in, **c)
         if self._lower_order_nums < order_max:
             self._lower_order_nums += 1
         self._step_index = i + 1
