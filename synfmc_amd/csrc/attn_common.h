@@ -2,6 +2,8 @@
 // Storage type T = bf16_t: one MFMA per product; T = float: split-bf16 x3 (hi*hi + hi*lo + lo*hi), the parity mode.
 #pragma once
 #include "common.h"
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -73,4 +75,48 @@ template <> __device__ __forceinline__ void store4<float>(float* p, float a, flo
 }
 
 // NKS: number of 16-wide k-steps of the QK^T reduction (D padded to 16*NKS); NDT = ceil(NKS/2)
+}  // namespace
+
+// ---- host side, shared by spatial_attn.hip, spatial_attn_bwd.hip, temporal_attn.hip and attn_generic.hip ----------------------------------------
+namespace {
+
+// The argument checks of an attention entry point, in the one order all of them keep: required pointers, storage type, the entry's own shape check
+// (`shape`: 0, or the FMC_FAIL it made), strides, 16-byte alignment.  The first failure sets "<prefix>: <text>" and is the return value.
+struct AttnStrides {
+    std::initializer_list<int64_t> values;
+    int multiple;
+    const char* text;
+};
+struct AttnArgs {
+    const char* prefix;
+    std::initializer_list<const void*> required;
+    const char* null_text;
+    bool typed;                                          // false: an entry point without a dtype argument
+    int dtype;
+    std::initializer_list<AttnStrides> strides;
+    std::initializer_list<const void*> aligned;          // a NULL among them is an optional tensor left out; empty: the entry checks no alignment
+};
+template <class Shape>
+int fmc_attn_check(const AttnArgs& a, Shape&& shape) {
+    for (const void* p : a.required)
+        if (!p) FMC_FAIL(FMC_E_NULL, "%s: %s", a.prefix, a.null_text);
+    if (a.typed && a.dtype != FMC_BF16 && a.dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "%s: dtype %d", a.prefix, a.dtype);
+    if (const int rc = shape()) return rc;
+    for (const AttnStrides& s : a.strides)
+        for (int64_t v : s.values)
+            if (v % s.multiple) FMC_FAIL(FMC_E_ALIGN, "%s: %s", a.prefix, s.text);
+    for (const void* p : a.aligned)
+        if (p && !fmc_aligned16(p)) FMC_FAIL(FMC_E_ALIGN, "%s: tensors must be 16-byte aligned", a.prefix);
+    return 0;
+}
+
+// `go(std::integral_constant<int, n>{})` for the one N that equals n; false when none does (the caller's refusal)
+template <int... N, class Go>
+bool fmc_pick(int n, Go&& go) {
+    return ((n == N && (go(std::integral_constant<int, N>{}), true)) || ...);
+}
+// the 16-wide k-steps of a head width among the built ones, for the spatial forward and backward kernels
+template <class Go>
+bool fmc_pick_nks(int D, Go&& go) { return fmc_pick<1, 2, 3, 4, 5, 6, 8, 10>((D + 15) / 16, go); }
+
 }  // namespace

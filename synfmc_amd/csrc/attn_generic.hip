@@ -14,7 +14,7 @@
 //   v_mfma_f32_16x16x16_bf16, so P^T feeds O^T[d x 16 queries] += V^T P^T from registers (the scheme of temporal_attn.hip); online softmax in the exp2
 //   domain, row statistics replicated over the four lanes of a query.
 // fp32 storage: every product as split-bf16 x3 (hi hi + hi lo + lo hi, fp32 accumulate), like the other attention kernels.
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -237,18 +237,6 @@ int ag_launch(const AGParams& P, hipStream_t st) {
     return 0;
 }
 
-template <typename T>
-int ag_dispatch(const AGParams& P, int D, hipStream_t st) {
-    switch (D / 32) {
-        case 1: return ag_launch<T, 1>(P, st);
-        case 2: return ag_launch<T, 2>(P, st);
-        case 4: return ag_launch<T, 4>(P, st);
-        case 8: return ag_launch<T, 8>(P, st);
-        case 16: return ag_launch<T, 16>(P, st);
-        default: FMC_FAIL(FMC_E_SHAPE, "attention_fwd: head width %d (supported: 32, 64, 128, 256, 512)", D);
-    }
-}
-
 }  // namespace
 
 extern "C" int fmc_attention_supported(int D) { return D == 32 || D == 64 || D == 128 || D == 256 || D == 512; }
@@ -256,22 +244,23 @@ extern "C" int fmc_attention_supported(int D) { return D == 32 || D == 64 || D =
 extern "C" int fmc_attention_fwd(const void* q, const void* k, const void* v, void* o, const unsigned char* key_keep, int B, int H, int Sq, int Skv, int D,
                                  int64_t q_batch_stride, int64_t q_row_stride, int64_t kv_batch_stride, int64_t kv_row_stride, int64_t o_batch_stride,
                                  int64_t o_row_stride, float scale, int causal, int dtype, void* stream) {
-    if (!q || !k || !v || !o) FMC_FAIL(FMC_E_NULL, "attention_fwd: NULL tensor");
-    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "attention_fwd: dtype %d", dtype);
-    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || !fmc_attention_supported(D) || (int64_t)B * H > 65535)
-        FMC_FAIL(FMC_E_SHAPE, "attention_fwd: B=%d H=%d Sq=%d Skv=%d D=%d (D in {32, 64, 128, 256, 512}, B*H <= 65535)", B, H, Sq, Skv, D);
-    const int64_t strides[] = {q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "attention_fwd: strides must be multiples of 8 elements");
-    if (!fmc_aligned16(q) || !fmc_aligned16(k) || !fmc_aligned16(v) || !fmc_aligned16(o)) FMC_FAIL(FMC_E_ALIGN, "attention_fwd: tensors must be 16-byte aligned");
+    const int rc = fmc_attn_check({"attention_fwd", {q, k, v, o}, "NULL tensor", true, dtype,
+                                   {{{q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride}, 8, "strides must be multiples of 8 elements"}},
+                                   {q, k, v, o}}, [&]() -> int {
+        if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || !fmc_attention_supported(D) || (int64_t)B * H > 65535)
+            FMC_FAIL(FMC_E_SHAPE, "attention_fwd: B=%d H=%d Sq=%d Skv=%d D=%d (D in {32, 64, 128, 256, 512}, B*H <= 65535)", B, H, Sq, Skv, D);
+        return 0;
+    });
+    if (rc) return rc;
     AGParams P;
     P.q = q; P.k = k; P.v = v; P.o = o; P.key_keep = key_keep;
     P.B = B; P.H = H; P.Sq = Sq; P.Skv = Skv;
     P.qbs = q_batch_stride; P.qrs = q_row_stride; P.kbs = kv_batch_stride; P.krs = kv_row_stride; P.obs = o_batch_stride; P.ors = o_row_stride;
     P.scale_log2 = scale * 1.4426950408889634f;
     P.causal = causal != 0;
-    const int rc = dtype == FMC_BF16 ? ag_dispatch<bf16_t>(P, D, (hipStream_t)stream) : ag_dispatch<float>(P, D, (hipStream_t)stream);
-    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!fmc_pick<1, 2, 4, 8, 16>(D / 32, [&](auto nks) { dtype == FMC_BF16 ? ag_launch<bf16_t, nks()>(P, st) : ag_launch<float, nks()>(P, st); }))
+        FMC_FAIL(FMC_E_SHAPE, "attention_fwd: head width %d (supported: 32, 64, 128, 256, 512)", D);
     FMC_CHECK_LAUNCH("fmc_attention_fwd");
     return 0;
 }

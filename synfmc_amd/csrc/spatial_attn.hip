@@ -1059,21 +1059,21 @@ __global__ __launch_bounds__(512, 1) void xattn40_kernel(const SAParams P, const
     }
 }
 
-inline int sa_xattn_env() {           // FMC_SA_XATTN=0: the block-by-block kernel for the text cross-attention too (A/B)
-    static const int v = fmc_env_int("FMC_SA_XATTN", 1);
-    return v;
-}
-inline bool xattn40_ok(const SAParams& P) {
-    return P.D == 40 && P.H == 8 && P.Skv <= 96 && P.Skv >= 1 && P.Sq % 32 == 0 && P.B % P.kv_batch_div == 0 && sa_xattn_env() != 0;
-}
-inline void launch_xattn40(const SAParams& P, hipStream_t st) {
-    const int nkvb = P.B / P.kv_batch_div, nq32 = P.Sq / 32, units = P.kv_batch_div * nq32;
-    int per = fmc_cu_count() / nkvb;                     // (per device; with the one in fmc_launch, two hipGetDevice per call)
-    if (per < 1) per = 1;
-    if (per > units) per = units;
-    const size_t lds = (size_t)8 * 96 * XA_VP * 2;
-    fmc_launch<xattn40_kernel>(dim3((unsigned)(per * nkvb)), dim3(512), lds, st, P, nq32, units, nkvb);
-}
+// The A/B switches of this unit (FMC_SA_*), read once per process by the first call that asks for one; every reader goes through sa_switches().
+struct SASwitches {
+    const int xattn = fmc_env_int("FMC_SA_XATTN", 1);                // 0: the block-by-block kernel for the text cross-attention too (A/B)
+    const int big80 = fmc_env_int("FMC_SA_BIG80", 1);                // 0: the tiled kernel at the 20x32 level too (A/B)
+    const int big80_waves = fmc_env_int("FMC_SA_BIG80_WAVES", 10);   // 10 | 8 | 5 waves per workgroup of sa_big80 (anything else: 10)
+    const int small = fmc_env_int("FMC_SA_SMALL", 1);                // 0: the tiled kernel at the inner levels too (A/B)
+    const int pipe = fmc_env_int("FMC_SA_PIPE", 1);                  // 0: the block-by-block kernel at d = 40 too (A/B); 4: persistent workgroups
+    const int prefetch = fmc_env_int("FMC_SA_PREFETCH", -1);         // 0 / 1 overrides the default policy (experiments only)
+    const int nq = fmc_env_int("FMC_SA_NQ", 2);                      // 1 | 2 query blocks per wave for d <= 48 (default 2)
+    const int vr = fmc_env_int("FMC_SA_VR", 1);                      // 0: V transposed while staging instead of by the transpose read (A/B)
+    const int mk = fmc_env_int("FMC_SA_MK", 1);                      // 0: softmax reference through the accumulator instead of the QK^T reduction
+    const int xcd = fmc_env_int("FMC_SA_XCD", -1);                   // 0: plain workgroup order, 1: (batch, head) per XCD (A/B)
+};
+inline const SASwitches& sa_switches() { static const SASwitches s; return s; }
+
 
 // =====================================================================================================================
 // Whole-K/V kernel for the inner levels (bf16, D = 160, S_kv <= 160): the self-attention of the 10x16 and 5x8 feature
@@ -1394,13 +1394,23 @@ __global__ __launch_bounds__(640, 1) void sa_big80_kernel_w10(const SAParams P) 
 __global__ __launch_bounds__(512, 1) void sa_big80_kernel_w8(const SAParams P) { sa_big80_body<8>(P); }
 __global__ __launch_bounds__(320, 3) void sa_big80_kernel_w5(const SAParams P) { sa_big80_body<5>(P); }
 
-inline bool sa_big80_ok(const SAParams& P) {     // FMC_SA_BIG80=0: the tiled kernel at the 20x32 level too (A/B)
-    static const bool on = fmc_env_int("FMC_SA_BIG80", 1) != 0;
-    return on && P.D == 80 && P.Skv % 32 == 0 && P.Skv >= 256 && P.Sq >= 160;
+// ---- host side.  The special kernels first, in the order fmc_spatial_attn_fwd asks them (bf16 only); then the tiled kernel's ladder ----------------
+inline bool xattn40_ok(const SAParams& P) {
+    return P.D == 40 && P.H == 8 && P.Skv <= 96 && P.Skv >= 1 && P.Sq % 32 == 0 && P.B % P.kv_batch_div == 0 && sa_switches().xattn != 0;
 }
+inline void launch_xattn40(const SAParams& P, hipStream_t st) {
+    const int nkvb = P.B / P.kv_batch_div, nq32 = P.Sq / 32, units = P.kv_batch_div * nq32;
+    int per = fmc_cu_count() / nkvb;                     // (per device; with the one in fmc_launch, two hipGetDevice per call)
+    if (per < 1) per = 1;
+    if (per > units) per = units;
+    const size_t lds = (size_t)8 * 96 * XA_VP * 2;
+    fmc_launch<xattn40_kernel>(dim3((unsigned)(per * nkvb)), dim3(512), lds, st, P, nq32, units, nkvb);
+}
+
+inline bool sa_big80_ok(const SAParams& P) { return sa_switches().big80 != 0 && P.D == 80 && P.Skv % 32 == 0 && P.Skv >= 256 && P.Sq >= 160; }
 inline void launch_sa_big80(const SAParams& Pin, hipStream_t st) {
     SAParams P = Pin;
-    static const int nw = [] { const int v = fmc_env_int("FMC_SA_BIG80_WAVES", 10); return v == 8 || v == 5 ? v : 10; }();
+    const int w = sa_switches().big80_waves, nw = w == 8 || w == 5 ? w : 10;
     P.nqblk = (P.Sq + 32 * nw - 1) / (32 * nw);
     if (P.xcd_remap != 2) P.xcd_remap = 0;
     const size_t lds = (size_t)(nw == 5 ? 160 : 320) * (5 * 16 + 8 + sa_vr_pitch<3>()) * 2;
@@ -1409,10 +1419,7 @@ inline void launch_sa_big80(const SAParams& Pin, hipStream_t st) {
     else fmc_launch<sa_big80_kernel_w10>(dim3((unsigned)(P.B * P.H * P.nqblk)), dim3(640), lds, st, P);
 }
 
-inline bool sa_small_ok(const SAParams& P) {     // FMC_SA_SMALL=0: the tiled kernel at the inner levels too (A/B)
-    static const bool on = fmc_env_int("FMC_SA_SMALL", 1) != 0;
-    return on && P.D == 160 && P.Skv <= 160;
-}
+inline bool sa_small_ok(const SAParams& P) { return sa_switches().small != 0 && P.D == 160 && P.Skv <= 160; }
 template <int NB>
 void launch_sa_small_nb(const SAParams& P, hipStream_t st) {
     const size_t lds = (size_t)NB * 32 * (10 * 16 + 8 + sa_vr_pitch<5>()) * 2;
@@ -1425,13 +1432,9 @@ inline void launch_sa_small(const SAParams& Pin, hipStream_t st) {
     else launch_sa_small_nb<5>(P, st);
 }
 
-inline int sa_pipe_env() {            // FMC_SA_PIPE=0: the block-by-block kernel at d = 40 too (A/B); 4: persistent workgroups
-    static const int v = fmc_env_int("FMC_SA_PIPE", 1);
-    return v;
-}
 inline bool sa40_ok(const SAParams& P) {
     return P.D == 40 && P.Skv % SA_BK == 0 && P.Skv >= 2 * SA_BK && P.Sq % 256 == 0 && P.krs * 2 * (int64_t)P.Skv < (1ll << 31) &&
-           sa_pipe_env() != 0;
+           sa_switches().pipe != 0;
 }
 inline void launch_sa40(const SAParams& Pin, hipStream_t st) {
     SAParams P = Pin;
@@ -1441,7 +1444,7 @@ inline void launch_sa40(const SAParams& Pin, hipStream_t st) {
     // 53..78 us, the XCDs' clocks 1.48..1.61 GHz); FMC_SA_PIPE=4 runs 2 persistent workgroups per CU over a static item
     // list instead -- measured 4 % slower for that reason.
     int grid = nitems;
-    if (sa_pipe_env() == 4) {
+    if (sa_switches().pipe == 4) {
         const int resident = 2 * fmc_cu_count();
         if (nitems > resident) grid = resident;
     }
@@ -1458,79 +1461,32 @@ void launch_sa_v(const SAParams& Pin, hipStream_t st) {
     fmc_launch<spatial_attn_kernel<T, NKS, SHORT_KV, PF, NQ, MK, VR>>(grid, block, lds, st, P);   // (gfx950 has 160 KiB of LDS per CU; above 64 KiB it is opt-in)
 }
 
-// FMC_SA_PREFETCH=0/1 overrides the default policy (experiments only)
-inline int sa_prefetch_env() {
-    static const int v = fmc_env_int("FMC_SA_PREFETCH", -1);
-    return v;
+// The tiled kernel's forms, for K/V of at most two tiles (SHORT_KV) and of more.  Prefetch: two tiles have a second one to fetch ahead only when the
+// keys reach into it, and only FMC_SA_PREFETCH=0 turns that off; longer K/V follow SA_PREFETCH_DEFAULT unless the switch says 0 or 1.
+template <typename T, int NKS, bool SHORT_KV>
+void launch_sa_forms(const SAParams& P, hipStream_t st) {
+    const SASwitches& sw = sa_switches();
+    const bool prefetch = SHORT_KV ? sw.prefetch != 0 && P.Skv > SA_BK : (sw.prefetch < 0 ? SA_PREFETCH_DEFAULT : sw.prefetch != 0);
+    if constexpr (sizeof(T) == 2 && NKS <= 6) {
+        if (prefetch) {
+            if constexpr (NKS <= 3) {
+                if (sw.nq == 2 && P.Sq >= 2 * SA_BQ) {
+                    if (sw.vr) {
+                        if (P.D % 16 == 8 && sw.mk) return launch_sa_v<T, NKS, SHORT_KV, true, 2, true, true>(P, st);
+                        return launch_sa_v<T, NKS, SHORT_KV, true, 2, false, true>(P, st);
+                    }
+                    return launch_sa_v<T, NKS, SHORT_KV, true, 2>(P, st);
+                }
+            }
+            return launch_sa_v<T, NKS, SHORT_KV, true>(P, st);
+        }
+    }
+    launch_sa_v<T, NKS, SHORT_KV, false>(P, st);
 }
-
-inline int sa_nq_env() {              // FMC_SA_NQ = 1 | 2 query blocks per wave for d <= 48 (default 2)
-    static const int v = fmc_env_int("FMC_SA_NQ", 2);
-    return v;
-}
-
-inline int sa_vr_env() {              // FMC_SA_VR=0: V transposed while staging instead of by the transpose read (A/B)
-    static const int v = fmc_env_int("FMC_SA_VR", 1);
-    return v;
-}
-
-inline int sa_mk_env() {              // FMC_SA_MK=0: softmax reference through the accumulator instead of the QK^T reduction
-    static const int v = fmc_env_int("FMC_SA_MK", 1);
-    return v;
-}
-
 template <typename T, int NKS>
 void launch_sa(const SAParams& P, hipStream_t st) {
-    if (P.Skv <= 2 * SA_BK) {
-        if constexpr (sizeof(T) == 2 && NKS <= 6) {
-            if (sa_prefetch_env() != 0 && P.Skv > SA_BK) {
-                if constexpr (NKS <= 3) {
-                    if (sa_nq_env() == 2 && P.Sq >= 2 * SA_BQ) {
-                        if (sa_vr_env()) {
-                            if (P.D % 16 == 8 && sa_mk_env()) return launch_sa_v<T, NKS, true, true, 2, true, true>(P, st);
-                            return launch_sa_v<T, NKS, true, true, 2, false, true>(P, st);
-                        }
-                        return launch_sa_v<T, NKS, true, true, 2>(P, st);
-                    }
-                }
-                return launch_sa_v<T, NKS, true, true>(P, st);
-            }
-        }
-        launch_sa_v<T, NKS, true, false>(P, st);
-    } else {
-        if constexpr (sizeof(T) == 2 && NKS <= 6) {
-            const int e = sa_prefetch_env();
-            if (e < 0 ? SA_PREFETCH_DEFAULT : e != 0) {
-                if constexpr (NKS <= 3) {
-                    if (sa_nq_env() == 2 && P.Sq >= 2 * SA_BQ) {
-                        if (sa_vr_env()) {
-                            if (P.D % 16 == 8 && sa_mk_env()) return launch_sa_v<T, NKS, false, true, 2, true, true>(P, st);
-                            return launch_sa_v<T, NKS, false, true, 2, false, true>(P, st);
-                        }
-                        return launch_sa_v<T, NKS, false, true, 2>(P, st);
-                    }
-                }
-                return launch_sa_v<T, NKS, false, true>(P, st);
-            }
-        }
-        launch_sa_v<T, NKS, false, false>(P, st);
-    }
-}
-
-template <typename T>
-int dispatch_sa(const SAParams& P, hipStream_t st) {
-    switch ((P.D + 15) / 16) {
-        case 1: launch_sa<T, 1>(P, st); break;
-        case 2: launch_sa<T, 2>(P, st); break;
-        case 3: launch_sa<T, 3>(P, st); break;
-        case 4: launch_sa<T, 4>(P, st); break;
-        case 5: launch_sa<T, 5>(P, st); break;
-        case 6: launch_sa<T, 6>(P, st); break;
-        case 8: launch_sa<T, 8>(P, st); break;
-        case 10: launch_sa<T, 10>(P, st); break;
-        default: FMC_FAIL(FMC_E_SHAPE, "spatial_attn: head dim %d not built (supported: <=96, 113..128, 145..160)", P.D);
-    }
-    return 0;
+    if (P.Skv <= 2 * SA_BK) launch_sa_forms<T, NKS, true>(P, st);
+    else launch_sa_forms<T, NKS, false>(P, st);
 }
 
 }  // namespace
@@ -1539,16 +1495,14 @@ extern "C" int fmc_spatial_attn_fwd(const void* q, const void* k, const void* v,
                                     int Sq, int Skv, int D, int64_t q_batch_stride, int64_t q_row_stride,
                                     int64_t kv_batch_stride, int64_t kv_row_stride, int64_t o_batch_stride,
                                     int64_t o_row_stride, int kv_batch_div, float scale, int dtype, void* stream) {
-    if (!q || !k || !v || !o) FMC_FAIL(FMC_E_NULL, "spatial_attn: NULL tensor");
-    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "spatial_attn: dtype %d", dtype);
-    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || D <= 0 || D % 8 || D > 160 || kv_batch_div <= 0)
-        FMC_FAIL(FMC_E_SHAPE, "spatial_attn: need D%%8==0, D<=160, positive sizes (B=%d H=%d Sq=%d Skv=%d D=%d)", B, H, Sq,
-                 Skv, D);
-    const int64_t strides[] = {q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "spatial_attn: strides must be multiples of 8 elements");
-    if (!fmc_aligned16(q) || !fmc_aligned16(k) || !fmc_aligned16(v) || !fmc_aligned16(o))
-        FMC_FAIL(FMC_E_ALIGN, "spatial_attn: tensors must be 16-byte aligned");
+    const int rc = fmc_attn_check({"spatial_attn", {q, k, v, o}, "NULL tensor", true, dtype,
+                                   {{{q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride}, 8, "strides must be multiples of 8 elements"}},
+                                   {q, k, v, o}}, [&]() -> int {
+        if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || D <= 0 || D % 8 || D > 160 || kv_batch_div <= 0)      // (not B % kv_batch_div, which the backward refuses: inherited)
+            FMC_FAIL(FMC_E_SHAPE, "spatial_attn: need D%%8==0, D<=160, positive sizes (B=%d H=%d Sq=%d Skv=%d D=%d)", B, H, Sq, Skv, D);
+        return 0;
+    });
+    if (rc) return rc;
     SAParams P;
     P.q = q; P.k = k; P.v = v; P.o = o; P.lse = lse;
     P.B = B; P.H = H; P.Sq = Sq; P.Skv = Skv; P.D = D;
@@ -1558,31 +1512,16 @@ extern "C" int fmc_spatial_attn_fwd(const void* q, const void* k, const void* v,
     P.scale_log2 = scale * LOG2E;
     P.nqblk = (Sq + SA_BQ - 1) / SA_BQ;
     P.xcd_remap = (B % 8 == 0) ? 2 : ((B * H) % 8 == 0) ? 1 : 0;
-    static const int want = fmc_env_int("FMC_SA_XCD", -1);   // A/B switch: 0 = plain order, 1 = (batch, head) per XCD
+    const int want = sa_switches().xcd;
     if (want == 0 || (want == 1 && (B * H) % 8 == 0)) P.xcd_remap = want;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FMC_BF16 && xattn40_ok(P)) {
-        launch_xattn40(P, st);
-        FMC_CHECK_LAUNCH("fmc_spatial_attn_fwd");
-        return 0;
-    }
-    if (dtype == FMC_BF16 && sa_big80_ok(P)) {
-        launch_sa_big80(P, st);
-        FMC_CHECK_LAUNCH("fmc_spatial_attn_fwd");
-        return 0;
-    }
-    if (dtype == FMC_BF16 && sa_small_ok(P)) {
-        launch_sa_small(P, st);
-        FMC_CHECK_LAUNCH("fmc_spatial_attn_fwd");
-        return 0;
-    }
-    if (dtype == FMC_BF16 && sa40_ok(P)) {
-        launch_sa40(P, st);
-        FMC_CHECK_LAUNCH("fmc_spatial_attn_fwd");
-        return 0;
-    }
-    int rc = (dtype == FMC_BF16) ? dispatch_sa<bf16_t>(P, st) : dispatch_sa<float>(P, st);
-    if (rc) return rc;
+    const bool bf16 = dtype == FMC_BF16;
+    if (bf16 && xattn40_ok(P)) launch_xattn40(P, st);
+    else if (bf16 && sa_big80_ok(P)) launch_sa_big80(P, st);
+    else if (bf16 && sa_small_ok(P)) launch_sa_small(P, st);
+    else if (bf16 && sa40_ok(P)) launch_sa40(P, st);
+    else if (!fmc_pick_nks(D, [&](auto nks) { bf16 ? launch_sa<bf16_t, nks()>(P, st) : launch_sa<float, nks()>(P, st); }))
+        FMC_FAIL(FMC_E_SHAPE, "spatial_attn: head dim %d not built (supported: <=96, 113..128, 145..160)", D);
     FMC_CHECK_LAUNCH("fmc_spatial_attn_fwd");
     return 0;
 }

@@ -356,22 +356,6 @@ void launch_bwd(SABwdParams P, hipStream_t st) {
     }
 }
 
-template <typename T>
-int dispatch_bwd(const SABwdParams& P, hipStream_t st) {
-    switch ((P.D + 15) / 16) {
-        case 1: launch_bwd<T, 1>(P, st); break;
-        case 2: launch_bwd<T, 2>(P, st); break;
-        case 3: launch_bwd<T, 3>(P, st); break;
-        case 4: launch_bwd<T, 4>(P, st); break;
-        case 5: launch_bwd<T, 5>(P, st); break;
-        case 6: launch_bwd<T, 6>(P, st); break;
-        case 8: launch_bwd<T, 8>(P, st); break;
-        case 10: launch_bwd<T, 10>(P, st); break;
-        default: FMC_FAIL(FMC_E_SHAPE, "spatial_attn_bwd: head dim %d not built", P.D);
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int fmc_spatial_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o,
@@ -381,18 +365,16 @@ extern "C" int fmc_spatial_attn_bwd(const void* q, const void* k, const void* v,
                                     int64_t o_row_stride, int64_t dq_batch_stride, int64_t dq_row_stride,
                                     int64_t dkv_batch_stride, int64_t dkv_row_stride, int kv_batch_div, float scale,
                                     int dtype, void* stream) {
-    if (!q || !k || !v || !o || !d_o || !lse || !dvec || !dq || (!dk != !dv))
-        FMC_FAIL(FMC_E_NULL, "spatial_attn_bwd: NULL tensor (dk and dv may be NULL together)");
-    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "spatial_attn_bwd: dtype %d", dtype);
-    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || D <= 0 || D % 8 || D > 160 || kv_batch_div <= 0 || B % kv_batch_div)
-        FMC_FAIL(FMC_E_SHAPE, "spatial_attn_bwd: bad shape (B=%d H=%d Sq=%d Skv=%d D=%d div=%d)", B, H, Sq, Skv, D, kv_batch_div);
-    const int64_t strides[] = {q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride,
-                               dq_batch_stride, dq_row_stride, dkv_batch_stride, dkv_row_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "spatial_attn_bwd: strides must be multiples of 8 elements");
-    const void* ptrs[] = {q, k, v, o, d_o, dq, dk, dv};
-    for (const void* p : ptrs)
-        if (p && !fmc_aligned16(p)) FMC_FAIL(FMC_E_ALIGN, "spatial_attn_bwd: tensors must be 16-byte aligned");
+    const void* const dkdv = (!dk != !dv) ? nullptr : q;          // one of the two alone reads as a missing tensor
+    const int rc = fmc_attn_check({"spatial_attn_bwd", {q, k, v, o, d_o, lse, dvec, dq, dkdv}, "NULL tensor (dk and dv may be NULL together)", true, dtype,
+                                   {{{q_batch_stride, q_row_stride, kv_batch_stride, kv_row_stride, o_batch_stride, o_row_stride, dq_batch_stride, dq_row_stride,
+                                      dkv_batch_stride, dkv_row_stride}, 8, "strides must be multiples of 8 elements"}},
+                                   {q, k, v, o, d_o, dq, dk, dv}}, [&]() -> int {
+        if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || D <= 0 || D % 8 || D > 160 || kv_batch_div <= 0 || B % kv_batch_div)
+            FMC_FAIL(FMC_E_SHAPE, "spatial_attn_bwd: bad shape (B=%d H=%d Sq=%d Skv=%d D=%d div=%d)", B, H, Sq, Skv, D, kv_batch_div);
+        return 0;
+    });
+    if (rc) return rc;
     SABwdParams P;
     P.q = q; P.k = k; P.v = v; P.o = o; P.d_o = d_o; P.lse = lse; P.dvec = dvec; P.dq = dq; P.dk = dk; P.dv = dv;
     P.B = B; P.H = H; P.Sq = Sq; P.Skv = Skv; P.D = D;
@@ -401,8 +383,8 @@ extern "C" int fmc_spatial_attn_bwd(const void* q, const void* k, const void* v,
     P.dkbs = dkv_batch_stride; P.dkrs = dkv_row_stride;
     P.kv_batch_div = kv_batch_div; P.scale = scale; P.scale_log2 = scale * LOG2E_B; P.nblk = 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc = dtype == FMC_BF16 ? dispatch_bwd<bf16_t>(P, st) : dispatch_bwd<float>(P, st);
-    if (rc) return rc;
+    if (!fmc_pick_nks(D, [&](auto nks) { dtype == FMC_BF16 ? launch_bwd<bf16_t, nks()>(P, st) : launch_bwd<float, nks()>(P, st); }))
+        FMC_FAIL(FMC_E_SHAPE, "spatial_attn_bwd: head dim %d not built", D);
     FMC_CHECK_LAUNCH("fmc_spatial_attn_bwd");
     return 0;
 }

@@ -23,7 +23,7 @@
 //   * FMC_F32 storage = split-bf16 x3 products (parity mode), like the spatial kernel.
 //
 // Algorithmic bytes per launch = 4 * n_clips*n_pix*F*H*D * e; flops = 4 * n_clips*n_pix*H*F*F*D.
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -769,75 +769,90 @@ void launch_ta_bwd_one_frame(const TABwdParams& P, hipStream_t st) {
     fmc_launch<temporal_attn_bwd_one_frame_kernel<T>>(dim3((unsigned)blocks), dim3(256), 0, st, P);
 }
 
-template <typename T, int FT, int NK32, bool PART>
-void launch_ta_bwd(const TABwdParams& P, hipStream_t st) {
-    const int CW = P.GH * P.D;
-    const size_t lds = sizeof(T) * 7 * (size_t)(FT * 16) * (CW + 8);
-    const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
-    dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    // (lds grows with GH * D: the eager warm-up before a graph capture has to cover the largest shape, as for the ring GEMMs)
-    fmc_launch<temporal_attn_bwd_kernel<T, FT, NK32, PART>>(grid, block, lds, st, P);
-}
+// ---- host side: every entry point below reads check, fill, group, dispatch ------------------------------------------------------------
+template <int V> using Int = std::integral_constant<int, V>;
 
-template <typename T, int FT, bool PART>
-int dispatch_ta_bwd_k(const TABwdParams& P, hipStream_t st) {
-    switch ((P.D + 31) / 32) {
-        case 1: launch_ta_bwd<T, FT, 1, PART>(P, st); break;
-        case 2: launch_ta_bwd<T, FT, 2, PART>(P, st); break;
-        case 3: launch_ta_bwd<T, FT, 3, PART>(P, st); break;
-        case 4: launch_ta_bwd<T, FT, 4, PART>(P, st); break;
-        case 5: launch_ta_bwd<T, FT, 5, PART>(P, st); break;
-        default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: head dim %d > 160", P.D);
-    }
-    return 0;
+// head group: the largest divisor GH of H whose GH * D channels are at most 320 (one 640-byte bf16 run per frame row) and pass `extra`
+template <class Extra>
+int ta_head_group(int H, int D, Extra&& extra) {
+    int gh = 1;
+    for (int g = 1; g <= H; ++g)
+        if (H % g == 0 && g * D <= 320 && extra(g * D)) gh = g;
+    return gh;
 }
+// the backward's seven LDS tiles of a head group `cw` channels wide: the frame count rounded up to whole 16-row tiles, pitch cw + 8
+inline size_t ta_bwd_lds(int F, int cw, size_t esz) { return 7 * (size_t)((F + 15) / 16 * 16) * (cw + 8) * esz; }
 
 // frame tiles and partial flag from the real frame count: F = 16 / 32 take the whole-tile kernels they always took
-template <typename T>
-int dispatch_ta_bwd(const TABwdParams& P, hipStream_t st) {
-    if (P.F == 1) { launch_ta_bwd_one_frame<T>(P, st); return 0; }
-    if (P.F == 16) return dispatch_ta_bwd_k<T, 1, false>(P, st);
-    if (P.F == 32) return dispatch_ta_bwd_k<T, 2, false>(P, st);
-    return P.F < 16 ? dispatch_ta_bwd_k<T, 1, true>(P, st) : dispatch_ta_bwd_k<T, 2, true>(P, st);
+template <class Go>
+void ta_tiles(int F, Go&& go) {
+    if (F == 16) go(Int<1>{}, std::false_type{});
+    else if (F == 32) go(Int<2>{}, std::false_type{});
+    else if (F < 16) go(Int<1>{}, std::true_type{});
+    else go(Int<2>{}, std::true_type{});
 }
+// the waves of a workgroup split the unit's heads
+inline int ta_waves(int GH) { return GH >= 4 ? 4 : (GH >= 2 ? 2 : 1); }
 
-template <typename T, int FT, int NK32, bool PART>
-void launch_ta(const TAParams& P, hipStream_t st) {
-    const int CW = P.GH * P.D;
-    const size_t lds = sizeof(T) * 3 * (size_t)(FT * 16) * (CW + 8);
-    dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH)));
-    auto go = [&](auto nw) {                                          // the waves of a workgroup split the unit's heads
-        constexpr int NW = decltype(nw)::value;
-        fmc_launch<temporal_attn_kernel<T, FT, NK32, NW, PART>>(grid, dim3(64 * NW), lds, st, P);
-    };
-    if (P.GH >= 4) go(std::integral_constant<int, 4>{});
-    else if (P.GH >= 2) go(std::integral_constant<int, 2>{});
-    else go(std::integral_constant<int, 1>{});
-}
-
-template <typename T, int FT, bool PART>
-int dispatch_ta_k(const TAParams& P, hipStream_t st) {
-    switch ((P.D + 31) / 32) {
-        case 1: launch_ta<T, FT, 1, PART>(P, st); break;
-        case 2: launch_ta<T, FT, 2, PART>(P, st); break;
-        case 3: launch_ta<T, FT, 3, PART>(P, st); break;
-        case 4: launch_ta<T, FT, 4, PART>(P, st); break;
-        case 5: launch_ta<T, FT, 5, PART>(P, st); break;
-        default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn: head dim %d > 160", P.D);
-    }
+// (FT, NK32, PART) of a launch as compile-time constants; `what`: the entry's name in the refusal of a head width without a kernel
+template <class Params, class Launch>
+int ta_dispatch(const Params& P, const char* what, Launch&& launch) {
+    bool built = false;
+    ta_tiles(P.F, [&](auto ft, auto part) { built = fmc_pick<1, 2, 3, 4, 5>((P.D + 31) / 32, [&](auto nk32) { launch(ft, nk32, part); }); });
+    if (!built) FMC_FAIL(FMC_E_SHAPE, "%s: head dim %d > 160", what, P.D);
     return 0;
 }
+template <class Params>
+dim3 ta_grid(const Params& P) { return dim3((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))); }
 
-template <typename T>
-int dispatch_ta(const TAParams& P, hipStream_t st) {
-    if (P.F < 1 || P.F > 32) FMC_FAIL(FMC_E_SHAPE, "temporal_attn: F must be in 1..32 (got %d)", P.F);
-    if (P.F == 16) return dispatch_ta_k<T, 1, false>(P, st);
-    if (P.F == 32) return dispatch_ta_k<T, 2, false>(P, st);
-    return P.F < 16 ? dispatch_ta_k<T, 1, true>(P, st) : dispatch_ta_k<T, 2, true>(P, st);
+// sizes, head group, the strides of the inputs and of the output (forward) or dO (backward), the scale
+struct TAStrides { int64_t c, f, p; };
+template <class Params>
+void ta_fill(Params& P, int n_clips, int n_pix, int F, int H, int D, int GH, TAStrides in, TAStrides out, float scale) {
+    P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D; P.GH = GH;
+    P.cs = in.c; P.fs = in.f; P.ps = in.p;
+    P.ocs = out.c; P.ofs = out.f; P.ops = out.p;
+    P.scale_log2 = scale * LOG2E;
 }
 
-// rows of the LDS tiles: the frame count rounded up to whole 16-row tiles
-inline int ta_tile_rows(int F) { return (F + 15) / 16 * 16; }
+template <typename T>
+int launch_ta(const TAParams& P, hipStream_t st) {
+    return ta_dispatch(P, "temporal_attn", [&](auto ft, auto nk32, auto part) {
+        const size_t lds = sizeof(T) * 3 * (size_t)(ft() * 16) * (P.GH * P.D + 8);
+        fmc_pick<4, 2, 1>(ta_waves(P.GH), [&](auto nw) {
+            fmc_launch<temporal_attn_kernel<T, ft(), nk32(), nw(), part()>>(ta_grid(P), dim3(64 * nw()), lds, st, P);
+        });
+    });
+}
+
+int launch_ta8(const TA8Params& P, hipStream_t st) {
+    return ta_dispatch(P, "temporal_attn_fp8", [&](auto ft, auto nk32, auto part) {
+        const int CW = P.GH * P.D;
+        const size_t lds = 3 * (size_t)(ft() * 16) * (CW + 16) + sizeof(bf16_t) * (size_t)(ft() * 16) * (CW + 8);
+        fmc_launch<temporal_attn_fp8_kernel<ft(), nk32(), part()>>(ta_grid(P), dim3(64 * ta_waves(P.GH)), lds, st, P);
+    });
+}
+
+// the fp8 entry runs the bf16 kernels (its dO and gradients are bf16): `what` names the entry in the refusals
+template <typename T>
+int launch_ta_bwd(const TABwdParams& P, const char* what, hipStream_t st) {
+    if (P.F == 1) { launch_ta_bwd_one_frame<T>(P, st); return 0; }
+    return ta_dispatch(P, what, [&](auto ft, auto nk32, auto part) {
+        // (lds grows with GH * D: the eager warm-up before a graph capture has to cover the largest shape, as for the ring GEMMs)
+        fmc_launch<temporal_attn_bwd_kernel<T, ft(), nk32(), part()>>(ta_grid(P), dim3(64 * ta_waves(P.GH)), ta_bwd_lds(ft() * 16, P.GH * P.D, sizeof(T)), st, P);
+    });
+}
+
+// the backward's head group (whose seven LDS tiles fit in ~150 KiB), its own strides and both scales on top of `ta_fill`
+int ta_bwd_fill(TABwdParams& P, const char* what, const char* in_this_dtype, int n_clips, int n_pix, int F, int H, int D, size_t esz, TAStrides in, TAStrides d_o,
+                TAStrides dq, float scale) {
+    const int gh = ta_head_group(H, D, [&](int cw) { return ta_bwd_lds(F, cw, esz) <= 150 * 1024; });
+    if (ta_bwd_lds(F, gh * D, esz) > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "%s: F=%d D=%d does not fit LDS%s", what, F, D, in_this_dtype);
+    ta_fill(P, n_clips, n_pix, F, H, D, gh, in, d_o, scale);
+    P.dcs = dq.c; P.dfs = dq.f; P.dps = dq.p;
+    P.scale = scale;
+    return 0;
+}
 
 }  // namespace
 
@@ -845,29 +860,20 @@ extern "C" int fmc_temporal_attn_fwd(const void* q, const void* k, const void* v
                                      int F, int H, int D, int64_t clip_stride, int64_t frame_stride,
                                      int64_t pix_stride, int64_t o_clip_stride, int64_t o_frame_stride,
                                      int64_t o_pix_stride, float scale, int dtype, void* stream) {
-    if (!q || !k || !v || !o) FMC_FAIL(FMC_E_NULL, "temporal_attn: NULL tensor");
-    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "temporal_attn: dtype %d", dtype);
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160)
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn: need D%%8==0, D<=160, positive sizes (clips=%d pix=%d H=%d D=%d)", n_clips,
-                 n_pix, H, D);
-    const int64_t strides[] = {clip_stride, frame_stride, pix_stride, o_clip_stride, o_frame_stride, o_pix_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "temporal_attn: strides must be multiples of 8 elements");
-    if (!fmc_aligned16(q) || !fmc_aligned16(k) || !fmc_aligned16(v) || !fmc_aligned16(o))
-        FMC_FAIL(FMC_E_ALIGN, "temporal_attn: tensors must be 16-byte aligned");
+    const TAStrides in{clip_stride, frame_stride, pix_stride}, out{o_clip_stride, o_frame_stride, o_pix_stride};
+    int rc = fmc_attn_check({"temporal_attn", {q, k, v, o}, "NULL tensor", true, dtype,
+                             {{{in.c, in.f, in.p, out.c, out.f, out.p}, 8, "strides must be multiples of 8 elements"}}, {q, k, v, o}}, [&]() -> int {
+        if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160)
+            FMC_FAIL(FMC_E_SHAPE, "temporal_attn: need D%%8==0, D<=160, positive sizes (clips=%d pix=%d H=%d D=%d)", n_clips, n_pix, H, D);
+        return 0;
+    });
+    if (rc) return rc;
     TAParams P;
     P.q = q; P.k = k; P.v = v; P.o = o;
-    P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
-    // head group: the largest divisor GH of H with GH*D <= 320 channels (one 640-byte bf16 run per frame row)
-    int gh = 1;
-    for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320) gh = g;
-    P.GH = gh;
-    P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;
-    P.ocs = o_clip_stride; P.ofs = o_frame_stride; P.ops = o_pix_stride;
-    P.scale_log2 = scale * LOG2E;
+    ta_fill(P, n_clips, n_pix, F, H, D, ta_head_group(H, D, [](int) { return true; }), in, out, scale);
+    if (F < 1 || F > 32) FMC_FAIL(FMC_E_SHAPE, "temporal_attn: F must be in 1..32 (got %d)", F);       // (after the other checks: inherited)
     hipStream_t st = (hipStream_t)stream;
-    int rc = (dtype == FMC_BF16) ? dispatch_ta<bf16_t>(P, st) : dispatch_ta<float>(P, st);
+    rc = (dtype == FMC_BF16) ? launch_ta<bf16_t>(P, st) : launch_ta<float>(P, st);
     if (rc) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_fwd");
     return 0;
@@ -879,95 +885,45 @@ extern "C" int fmc_temporal_attn_bwd(const void* q, const void* k, const void* v
                                      int64_t do_frame_stride, int64_t do_pix_stride, int64_t dq_clip_stride,
                                      int64_t dq_frame_stride, int64_t dq_pix_stride, float scale, int dtype,
                                      void* stream) {
-    if (!q || !k || !v || !d_o || !dq || !dk || !dv) FMC_FAIL(FMC_E_NULL, "temporal_attn_bwd: NULL tensor");
-    if (dtype != FMC_BF16 && dtype != FMC_F32) FMC_FAIL(FMC_E_DTYPE, "temporal_attn_bwd: dtype %d", dtype);
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
-    const int64_t strides[] = {clip_stride, frame_stride, pix_stride, do_clip_stride, do_frame_stride, do_pix_stride,
-                               dq_clip_stride, dq_frame_stride, dq_pix_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_bwd: strides must be multiples of 8 elements");
-    const void* ptrs[] = {q, k, v, d_o, dq, dk, dv};
-    for (const void* p : ptrs)
-        if (!fmc_aligned16(p)) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_bwd: tensors must be 16-byte aligned");
+    const TAStrides in{clip_stride, frame_stride, pix_stride}, g{do_clip_stride, do_frame_stride, do_pix_stride}, d{dq_clip_stride, dq_frame_stride, dq_pix_stride};
+    int rc = fmc_attn_check({"temporal_attn_bwd", {q, k, v, d_o, dq, dk, dv}, "NULL tensor", true, dtype,
+                             {{{in.c, in.f, in.p, g.c, g.f, g.p, d.c, d.f, d.p}, 8, "strides must be multiples of 8 elements"}}, {q, k, v, d_o, dq, dk, dv}}, [&]() -> int {
+        if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+            FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+        return 0;
+    });
+    if (rc) return rc;
     TABwdParams P;
     P.q = q; P.k = k; P.v = v; P.d_o = d_o; P.dq = dq; P.dk = dk; P.dv = dv;
-    P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
-    // head group: largest divisor of H whose 7 LDS tiles fit in ~150 KiB and whose rows are <= 320 channels
-    const size_t esz = dtype == FMC_BF16 ? 2 : 4, FR = (size_t)ta_tile_rows(F);
-    int gh = 1;
-    for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320 && 7 * FR * (g * D + 8) * esz <= 150 * 1024) gh = g;
-    if (7 * FR * (gh * D + 8) * esz > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_bwd: F=%d D=%d does not fit LDS in this dtype", F, D);
-    P.GH = gh;
-    P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;
-    P.ocs = do_clip_stride; P.ofs = do_frame_stride; P.ops = do_pix_stride;
-    P.dcs = dq_clip_stride; P.dfs = dq_frame_stride; P.dps = dq_pix_stride;
-    P.scale = scale; P.scale_log2 = scale * LOG2E;
     P.q8_scales = nullptr;
+    if ((rc = ta_bwd_fill(P, "temporal_attn_bwd", " in this dtype", n_clips, n_pix, F, H, D, dtype == FMC_BF16 ? 2 : 4, in, g, d, scale))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == FMC_BF16) rc = dispatch_ta_bwd<bf16_t>(P, st);
-    else rc = dispatch_ta_bwd<float>(P, st);
+    rc = dtype == FMC_BF16 ? launch_ta_bwd<bf16_t>(P, "temporal_attn_bwd", st) : launch_ta_bwd<float>(P, "temporal_attn_bwd", st);
     if (rc) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_bwd");
     return 0;
 }
 
-namespace {
-template <int FT, int NK32, bool PART>
-void launch_ta8(const TA8Params& P, hipStream_t st) {
-    const int CW = P.GH * P.D;
-    const size_t lds = 3 * (size_t)(FT * 16) * (CW + 16) + sizeof(bf16_t) * (size_t)(FT * 16) * (CW + 8);
-    const int waves = P.GH >= 4 ? 4 : (P.GH >= 2 ? 2 : 1);
-    dim3 grid((unsigned)((int64_t)P.n_clips * P.n_pix * (P.H / P.GH))), block(64 * waves);
-    fmc_launch<temporal_attn_fp8_kernel<FT, NK32, PART>>(grid, block, lds, st, P);
-}
-template <int FT, bool PART>
-int dispatch_ta8(const TA8Params& P, hipStream_t st) {
-    switch ((P.D + 31) / 32) {
-        case 1: launch_ta8<FT, 1, PART>(P, st); break;
-        case 2: launch_ta8<FT, 2, PART>(P, st); break;
-        case 3: launch_ta8<FT, 3, PART>(P, st); break;
-        case 4: launch_ta8<FT, 4, PART>(P, st); break;
-        case 5: launch_ta8<FT, 5, PART>(P, st); break;
-        default: FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: head dim %d > 160", P.D);
-    }
-    return 0;
-}
-}  // namespace
-
 extern "C" int fmc_temporal_attn_fp8_fwd(const void* q, const void* k, const void* v, void* o, const void* scales,
                                          int n_clips, int n_pix, int F, int H, int D, int64_t clip_stride,
                                          int64_t frame_stride, int64_t pix_stride, int64_t o_clip_stride,
                                          int64_t o_frame_stride, int64_t o_pix_stride, float scale, void* stream) {
-    if (!q || !k || !v || !o || !scales) FMC_FAIL(FMC_E_NULL, "temporal_attn_fp8: NULL tensor");
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
-    const int64_t strides[] = {clip_stride, frame_stride, pix_stride};
-    for (int64_t s : strides)
-        if (s % 16) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_fp8: q/k/v strides must be multiples of 16 bytes");
-    const int64_t ostrides[] = {o_clip_stride, o_frame_stride, o_pix_stride};
-    for (int64_t s : ostrides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_fp8: o strides must be multiples of 8 elements");
-    if (!fmc_aligned16(q) || !fmc_aligned16(k) || !fmc_aligned16(v) || !fmc_aligned16(o))
-        FMC_FAIL(FMC_E_ALIGN, "temporal_attn_fp8: tensors must be 16-byte aligned");
+    const TAStrides in{clip_stride, frame_stride, pix_stride}, out{o_clip_stride, o_frame_stride, o_pix_stride};
+    int rc = fmc_attn_check({"temporal_attn_fp8", {q, k, v, o, scales}, "NULL tensor", false, 0,
+                             {{{in.c, in.f, in.p}, 16, "q/k/v strides must be multiples of 16 bytes"}, {{out.c, out.f, out.p}, 8, "o strides must be multiples of 8 elements"}},
+                             {q, k, v, o}}, [&]() -> int {
+        if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+            FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+        return 0;
+    });
+    if (rc) return rc;
     TA8Params P;
     P.q = (const unsigned char*)q; P.k = (const unsigned char*)k; P.v = (const unsigned char*)v; P.o = (bf16_t*)o;
     P.scales = (const float*)scales;
-    P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
-    int gh = 1;                        // head group: GH*D channels <= 320 and a multiple of 16 bytes per staged row
-    for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320 && (g * D) % 16 == 0) gh = g;
+    const int gh = ta_head_group(H, D, [](int cw) { return cw % 16 == 0; });          // a multiple of 16 bytes per staged row
     if ((gh * D) % 16) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8: no head group with (GH*D) %% 16 == 0 (H=%d D=%d)", H, D);
-    P.GH = gh;
-    P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;
-    P.ocs = o_clip_stride; P.ofs = o_frame_stride; P.ops = o_pix_stride;
-    P.scale_log2 = scale * LOG2E;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = F == 16 ? dispatch_ta8<1, false>(P, st) : F == 32 ? dispatch_ta8<2, false>(P, st)
-                 : F < 16 ? dispatch_ta8<1, true>(P, st) : dispatch_ta8<2, true>(P, st);
-    if (rc) return rc;
+    ta_fill(P, n_clips, n_pix, F, H, D, gh, in, out, scale);
+    if ((rc = launch_ta8(P, (hipStream_t)stream))) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_fp8_fwd");
     return 0;
 }
@@ -978,30 +934,19 @@ extern "C" int fmc_temporal_attn_fp8_bwd(const void* q, const void* k, const voi
                                          int64_t do_clip_stride, int64_t do_frame_stride, int64_t do_pix_stride,
                                          int64_t dq_clip_stride, int64_t dq_frame_stride, int64_t dq_pix_stride, float scale,
                                          void* stream) {
-    if (!q || !k || !v || !scales || !d_o || !dq || !dk || !dv) FMC_FAIL(FMC_E_NULL, "temporal_attn_fp8_bwd: NULL tensor");
-    if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
-        FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
-    const int64_t strides[] = {clip_stride, frame_stride, pix_stride, do_clip_stride, do_frame_stride, do_pix_stride,
-                               dq_clip_stride, dq_frame_stride, dq_pix_stride};
-    for (int64_t s : strides)
-        if (s % 8) FMC_FAIL(FMC_E_ALIGN, "temporal_attn_fp8_bwd: strides must be multiples of 8");
+    const TAStrides in{clip_stride, frame_stride, pix_stride}, g{do_clip_stride, do_frame_stride, do_pix_stride}, d{dq_clip_stride, dq_frame_stride, dq_pix_stride};
+    int rc = fmc_attn_check({"temporal_attn_fp8_bwd", {q, k, v, scales, d_o, dq, dk, dv}, "NULL tensor", false, 0,
+                             {{{in.c, in.f, in.p, g.c, g.f, g.p, d.c, d.f, d.p}, 8, "strides must be multiples of 8"}}, {}}, [&]() -> int {     // (no alignment check: inherited)
+        if (n_clips <= 0 || n_pix <= 0 || H <= 0 || D <= 0 || D % 8 || D > 160 || F < 1 || F > 32)
+            FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: need F in 1..32, D%%8==0, D<=160 (F=%d H=%d D=%d)", F, H, D);
+        return 0;
+    });
+    if (rc) return rc;
     TABwdParams P;
     P.q = q; P.k = k; P.v = v; P.d_o = d_o; P.dq = dq; P.dk = dk; P.dv = dv;
-    P.n_clips = n_clips; P.n_pix = n_pix; P.F = F; P.H = H; P.D = D;
-    const size_t FR = (size_t)ta_tile_rows(F);
-    int gh = 1;
-    for (int g = 1; g <= H; ++g)
-        if (H % g == 0 && g * D <= 320 && 7 * FR * (g * D + 8) * 2 <= 150 * 1024) gh = g;
-    if (7 * FR * (gh * D + 8) * 2 > 160 * 1024) FMC_FAIL(FMC_E_SHAPE, "temporal_attn_fp8_bwd: F=%d D=%d does not fit LDS", F, D);
-    P.GH = gh;
-    P.cs = clip_stride; P.fs = frame_stride; P.ps = pix_stride;          // bytes = elements for the e4m3 inputs
-    P.ocs = do_clip_stride; P.ofs = do_frame_stride; P.ops = do_pix_stride;
-    P.dcs = dq_clip_stride; P.dfs = dq_frame_stride; P.dps = dq_pix_stride;
-    P.scale = scale; P.scale_log2 = scale * LOG2E;
     P.q8_scales = (const float*)scales;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = dispatch_ta_bwd<bf16_t>(P, st);
-    if (rc) return rc;
+    if ((rc = ta_bwd_fill(P, "temporal_attn_fp8_bwd", "", n_clips, n_pix, F, H, D, 2, in, g, d, scale))) return rc;      // (bytes = elements for the e4m3 inputs)
+    if ((rc = launch_ta_bwd<bf16_t>(P, "temporal_attn_fp8_bwd", (hipStream_t)stream))) return rc;
     FMC_CHECK_LAUNCH("fmc_temporal_attn_fp8_bwd");
     return 0;
 }

@@ -391,6 +391,31 @@ def _rows(t: torch.Tensor) -> Tuple[int, int]:
     return t.stride(0), t.stride(1)
 
 
+def _split3(qkv: torch.Tensor):
+    """The q | k | v slices of a fused `[.., 3C]` tensor."""
+    C = qkv.shape[-1] // 3
+    return qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+
+
+def _split2(kv: torch.Tensor):
+    """The k | v slices of a fused `[.., 2C]` tensor."""
+    C = kv.shape[-1] // 2
+    return kv[..., :C], kv[..., C:]
+
+
+def _spatial_bwd(q, k, v, o, lse, d_o, dq, dk, dv, kbs, div, heads, scale, unwritten=(0, 0)) -> None:
+    """`fmc_spatial_attn_bwd` into dq and dk / dv (both None: a frozen key/value side).  o and `d_o` are dense `[B, Sq, C]`; `kbs`: the batch stride K / V
+    are read with, `div`: the batch entries that share one of them; `unwritten`: the strides named for dk / dv when there is none (inherited: each
+    caller has its own pair, the kernels read neither)."""
+    B, Sq, C = q.shape
+    dvec = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device)
+    dkb, dkr = (dk.stride(0), dk.stride(1)) if dk is not None else unwritten
+    _lib.check(_lib.load().fmc_spatial_attn_bwd(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dvec.data_ptr(), dq.data_ptr(), _p(dk), _p(dv), B, heads, Sq,
+        k.shape[1], C // heads, q.stride(0), q.stride(1), kbs, k.stride(1), Sq * C, C, dq.stride(0), dq.stride(1), dkb, dkr, div, float(scale), _dt(q), _stream()),
+        "fmc_spatial_attn_bwd")
+
+
 class _SpatialAttention(torch.autograd.Function):
     """q `[B,S,C]`, kv-side tensors `[Bkv,Skv,C]` (strided slices allowed).  Grads come back as dense tensors."""
 
@@ -404,21 +429,12 @@ class _SpatialAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o):
         q, k, v, o, lse = ctx.saved_tensors
-        B, Sq, C = q.shape
-        Bkv, Skv, _ = k.shape
-        heads = ctx.heads
-        D = C // heads
-        d_o = d_o.contiguous()
-        dq = torch.empty(B, Sq, C, dtype=q.dtype, device=q.device)
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         need_kv = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        dk = torch.empty(Bkv, Skv, C, dtype=q.dtype, device=q.device) if need_kv else None
-        dv = torch.empty(Bkv, Skv, C, dtype=q.dtype, device=q.device) if need_kv else None
-        dvec = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device)
-        _lib.check(_lib.load().fmc_spatial_attn_bwd(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-            dq.data_ptr(), _p(dk), _p(dv), B, heads, Sq, Skv, D, q.stride(0), q.stride(1), k.stride(0),
-            k.stride(1), Sq * C, C, Sq * C, C, Skv * C, C, B // Bkv, float(ctx.scale), _dt(q), _stream()),
-            "fmc_spatial_attn_bwd")
+        dk = torch.empty(k.shape, dtype=q.dtype, device=q.device) if need_kv else None
+        dv = torch.empty(k.shape, dtype=q.dtype, device=q.device) if need_kv else None
+        _spatial_bwd(q, k, v, o, lse, d_o.contiguous(), dq, dk, dv, k.stride(0), q.shape[0] // k.shape[0], ctx.heads, ctx.scale,
+                     unwritten=(k.shape[1] * k.shape[2], k.shape[2]))
         return dq, dk, dv, None, None
 
 
@@ -484,9 +500,24 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
 
 
 def _tstrides(t):
+    """(clips, pixels, frames, clip stride, frame stride, pixel stride) of the native `[B, F, P, C]` layout or of `[N, F, C]` (one clip of N pixels)."""
     if t.ndim == 4:
         return t.shape[0], t.shape[2], t.shape[1], t.stride(0), t.stride(1), t.stride(2)
     return 1, t.shape[0], t.shape[1], 0, t.stride(1), t.stride(0)
+
+
+def _temporal_bwd(q, k, v, d_o, dqkv, heads, scale, scales=None) -> None:
+    """`fmc_temporal_attn_bwd` into the slices of the fused `[.., 3C]` gradient `dqkv`; with `scales` (the three fp8 scales of the forward) q, k, v are
+    e4m3 bytes and the call is `fmc_temporal_attn_fp8_bwd` (bf16 `d_o` and gradients)."""
+    dq, dk, dv = _split3(dqkv)
+    B, P, F, cs, fs, ps = _tstrides(q)
+    args = (d_o.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, P, F, heads, q.shape[-1] // heads, cs, fs, ps, *_tstrides(d_o)[3:], *_tstrides(dq)[3:],
+            float(scale))
+    L = _lib.load()
+    if scales is None:
+        _lib.check(L.fmc_temporal_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), *args, _dt(q), _stream()), "fmc_temporal_attn_bwd")
+    else:
+        _lib.check(L.fmc_temporal_attn_fp8_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), scales.data_ptr(), *args, _stream()), "fmc_temporal_attn_fp8_bwd")
 
 
 class _TemporalAttention(torch.autograd.Function):
@@ -499,18 +530,9 @@ class _TemporalAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o):
         q, k, v = ctx.saved_tensors
-        d_o = d_o.contiguous()
-        C = q.shape[-1]
-        dqkv = torch.empty(*q.shape[:-1], 3 * C, dtype=q.dtype, device=q.device)   # fused [.., 3C] gradient
-        dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        B, P, F, cs, fs, ps = _tstrides(q)
-        _, _, _, ocs, ofs, ops = _tstrides(d_o)
-        _, _, _, dcs, dfs, dps = _tstrides(dq)
-        _lib.check(_lib.load().fmc_temporal_attn_bwd(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), d_o.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, P,
-            F, ctx.heads, C // ctx.heads, cs, fs, ps, ocs, ofs, ops, dcs, dfs, dps, float(ctx.scale), _dt(q), _stream()),
-            "fmc_temporal_attn_bwd")
-        return dq, dk, dv, None, None
+        dqkv = torch.empty(*q.shape[:-1], 3 * q.shape[-1], dtype=q.dtype, device=q.device)   # fused [.., 3C] gradient
+        _temporal_bwd(q, k, v, d_o.contiguous(), dqkv, ctx.heads, ctx.scale)
+        return (*_split3(dqkv), None, None)
 
 
 class _SelfAttentionQKV(torch.autograd.Function):
@@ -520,8 +542,7 @@ class _SelfAttentionQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads, scale, temporal):
-        C = qkv.shape[-1] // 3
-        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        q, k, v = _split3(qkv)
         ctx.heads, ctx.scale, ctx.temporal = heads, scale, temporal
         if temporal:
             ctx.save_for_backward(qkv)
@@ -533,29 +554,14 @@ class _SelfAttentionQKV(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o):
         qkv = ctx.saved_tensors[0]
-        C = qkv.shape[-1] // 3
-        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        q, k, v = _split3(qkv)
         d_o = d_o.contiguous()
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        heads = ctx.heads
         if ctx.temporal:
-            B, P, F, cs, fs, ps = _tstrides(q)
-            _, _, _, ocs, ofs, ops = _tstrides(d_o)
-            _, _, _, dcs, dfs, dps = _tstrides(dq)
-            _lib.check(_lib.load().fmc_temporal_attn_bwd(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), d_o.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B,
-                P, F, heads, C // heads, cs, fs, ps, ocs, ofs, ops, dcs, dfs, dps, float(ctx.scale), _dt(q), _stream()),
-                "fmc_temporal_attn_bwd")
+            _temporal_bwd(q, k, v, d_o, dqkv, ctx.heads, ctx.scale)
         else:
             _, o, lse = ctx.saved_tensors
-            B, S, _ = q.shape
-            dvec = torch.empty(B, heads, S, dtype=torch.float32, device=q.device)
-            _lib.check(_lib.load().fmc_spatial_attn_bwd(
-                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-                dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, heads, S, S, C // heads, q.stride(0), q.stride(1),
-                k.stride(0), k.stride(1), S * C, C, dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), 1,
-                float(ctx.scale), _dt(q), _stream()), "fmc_spatial_attn_bwd")
+            _spatial_bwd(q, k, v, o, lse, d_o, *_split3(dqkv), k.stride(0), 1, ctx.heads, ctx.scale)
         return dqkv, None, None, None
 
 
@@ -564,8 +570,7 @@ class _CrossAttentionQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, heads, scale):
-        C = q.shape[-1]
-        o, lse = _spatial_attention_raw(q, kv[..., :C], kv[..., C:], heads, scale, True)
+        o, lse = _spatial_attention_raw(q, *_split2(kv), heads, scale, True)
         ctx.save_for_backward(q, kv, o, lse)
         ctx.heads, ctx.scale = heads, scale
         return o
@@ -573,30 +578,21 @@ class _CrossAttentionQKV(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o):
         q, kv, o, lse = ctx.saved_tensors
-        B, Sq, C = q.shape
-        Bkv, Skv, _ = kv.shape
-        k, v = kv[..., :C], kv[..., C:]
-        heads = ctx.heads
-        d_o = d_o.contiguous()
-        dq = torch.empty(B, Sq, C, dtype=q.dtype, device=q.device)
-        dvec = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device)
+        B, Bkv = q.shape[0], kv.shape[0]
+        k, v = _split2(kv)
+        dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         div, kbs = B // Bkv, k.stride(0)
         if not ctx.needs_input_grad[1]:
             # frozen to_k / to_v on a constant text embedding (every FMC training stage): no dK / dV kernel at all
-            dkv = dk = dv = None
+            dkv = None
         elif Bkv == 1 and div > 1:
             # one text for all frames: per-frame partial dK | dV (batch stride 0 on K / V keeps B x heads workgroups
             # busy instead of `heads`), summed over the frames afterwards
-            part = torch.empty(B, Skv, 2 * C, dtype=q.dtype, device=q.device)
-            dk, dv, div, kbs, dkv = part[..., :C], part[..., C:], 1, 0, part
+            dkv, div, kbs = torch.empty(B, *kv.shape[1:], dtype=q.dtype, device=q.device), 1, 0
         else:
             dkv = torch.empty(kv.shape, dtype=q.dtype, device=q.device)
-            dk, dv = dkv[..., :C], dkv[..., C:]
-        _lib.check(_lib.load().fmc_spatial_attn_bwd(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), dvec.data_ptr(),
-            dq.data_ptr(), _p(dk), _p(dv), B, heads, Sq, Skv, C // heads, q.stride(0), q.stride(1), kbs, k.stride(1),
-            Sq * C, C, Sq * C, C, dk.stride(0) if dk is not None else 0, dk.stride(1) if dk is not None else 2 * C, div,
-            float(ctx.scale), _dt(q), _stream()), "fmc_spatial_attn_bwd")
+        dk, dv = _split2(dkv) if dkv is not None else (None, None)
+        _spatial_bwd(q, k, v, o, lse, d_o.contiguous(), dq, dk, dv, kbs, div, ctx.heads, ctx.scale, unwritten=(0, kv.shape[2]))
         if dkv is not None and dkv.shape[0] != Bkv:
             dkv = dkv.sum(0, keepdim=True, dtype=torch.float32).to(q.dtype)
         return dq, dkv, None, None
@@ -604,19 +600,17 @@ class _CrossAttentionQKV(torch.autograd.Function):
 
 def self_attention_qkv(qkv: torch.Tensor, heads: int, scale: float, temporal: bool) -> torch.Tensor:
     """Attention on a fused `[.., 3C]` projection (q | k | v); differentiable with a single fused gradient."""
-    C = qkv.shape[-1] // 3
     if torch.is_grad_enabled() and qkv.requires_grad:
         return _SelfAttentionQKV.apply(qkv, heads, scale, temporal)
-    q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+    q, k, v = _split3(qkv)
     return _temporal_attention_raw(q, k, v, heads, scale) if temporal else _spatial_attention_raw(q, k, v, heads, scale)
 
 
 def cross_attention_q_kv(q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
     """Cross attention with a fused `[.., 2C]` (k | v) projection; differentiable with a fused dK | dV gradient."""
-    C = q.shape[-1]
     if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
         return _CrossAttentionQKV.apply(q, kv, heads, scale)
-    return _spatial_attention_raw(q, kv[..., :C], kv[..., C:], heads, scale)
+    return _spatial_attention_raw(q, *_split2(kv), heads, scale)
 
 
 def temporal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int,
@@ -639,20 +633,10 @@ def _temporal_attention_raw(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, h
     D = C // heads
     scale = D ** -0.5 if scale is None else scale
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-    if q.ndim == 4:
-        B, F, P, _ = q.shape
-        cs, fs, ps = q.stride(0), q.stride(1), q.stride(2)
-        ocs, ofs, ops = o.stride(0), o.stride(1), o.stride(2)
-    elif q.ndim == 3:
-        P, F, _ = q.shape
-        B = 1
-        cs, fs, ps = 0, q.stride(1), q.stride(0)
-        ocs, ofs, ops = 0, o.stride(1), o.stride(0)
-    else:
+    if q.ndim not in (3, 4):
         raise ValueError("temporal_attention expects [B, F, P, C] or [N, F, C]")
-    _lib.check(_lib.load().fmc_temporal_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, P, F, heads,
-                                                 D, cs, fs, ps, ocs, ofs, ops, float(scale), _dt(q), _stream()),
-               "fmc_temporal_attn_fwd")
+    _lib.check(_lib.load().fmc_temporal_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), *_tstrides(q)[:3], heads, D, *_tstrides(q)[3:],
+                                                 *_tstrides(o)[3:], float(scale), _dt(q), _stream()), "fmc_temporal_attn_fwd")
     return o
 
 
@@ -701,14 +685,11 @@ def linear_fp8_qkv(x: torch.Tensor, weight: torch.Tensor, scales: Fp8QKVScales) 
 
 
 def _temporal_fp8_raw(qkv8: torch.Tensor, scale_dev: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
-    C = qkv8.shape[-1] // 3
-    q, k, v = qkv8[..., :C], qkv8[..., C:2 * C], qkv8[..., 2 * C:]
+    q, k, v = _split3(qkv8)
+    C = q.shape[-1]
     o = torch.empty(*qkv8.shape[:-1], C, dtype=torch.bfloat16, device=qkv8.device)
-    B, P, F, cs, fs, ps = _tstrides(q)
-    _, _, _, ocs, ofs, ops = _tstrides(o)
-    _lib.check(_lib.load().fmc_temporal_attn_fp8_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                                                     scale_dev.data_ptr(), B, P, F, heads, C // heads, cs, fs, ps, ocs, ofs,
-                                                     ops, float(scale), _stream()), "fmc_temporal_attn_fp8_fwd")
+    _lib.check(_lib.load().fmc_temporal_attn_fp8_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), scale_dev.data_ptr(), *_tstrides(q)[:3], heads,
+                                                     C // heads, *_tstrides(q)[3:], *_tstrides(o)[3:], float(scale), _stream()), "fmc_temporal_attn_fp8_fwd")
     return o
 
 
@@ -729,18 +710,8 @@ class _TemporalAttentionFp8(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o):
         x, weight, qkv8, sc = ctx.saved_tensors
-        C = qkv8.shape[-1] // 3
-        q, k, v = qkv8[..., :C], qkv8[..., C:2 * C], qkv8[..., 2 * C:]
-        d_o = d_o.contiguous()
         dqkv = torch.empty(qkv8.shape, dtype=torch.bfloat16, device=qkv8.device)
-        dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        B, P, F, cs, fs, ps = _tstrides(q)
-        _, _, _, ocs, ofs, ops = _tstrides(d_o)
-        _, _, _, dcs, dfs, dps = _tstrides(dq)
-        _lib.check(_lib.load().fmc_temporal_attn_fp8_bwd(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), sc.data_ptr(), d_o.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-            dv.data_ptr(), B, P, F, ctx.heads, C // ctx.heads, cs, fs, ps, ocs, ofs, ops, dcs, dfs, dps, float(ctx.scale),
-            _stream()), "fmc_temporal_attn_fp8_bwd")
+        _temporal_bwd(*_split3(qkv8), d_o.contiguous(), dqkv, ctx.heads, ctx.scale, scales=sc)
         dx = None
         if ctx.needs_input_grad[0]:                  # frozen weight: own GEMM on the cached W^T; a training weight: plain matmul
             dx = torch.matmul(dqkv, weight) if weight.requires_grad else linear_backward_data(dqkv, weight)
@@ -755,9 +726,7 @@ def temporal_attention_fp8(x: torch.Tensor, weight: torch.Tensor, scales: Fp8QKV
     The first call on a fresh `scales` runs the bf16 path once to calibrate the maxima."""
     if not scales.calibrated:
         with torch.no_grad():
-            qkv = linear(x.detach(), weight.detach())
-            C = qkv.shape[-1] // 3
-            scales.calibrate(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:])
+            scales.calibrate(*_split3(linear(x.detach(), weight.detach())))
     scales.roll()
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
         return _TemporalAttentionFp8.apply(x, weight, scales, heads, scale)

@@ -17,7 +17,7 @@ Two instruments, every case gets both:
   family's rounding points.
 
 The reference takes the logits as `scale_log2 * q.k` in log2 units with the fp32 product `scale_log2 = scale * LOG2E` every entry point forms
-(spatial_attn.hip:1558, temporal_attn.hip:868, attn_generic.hip:271; within 2^-23 of scale * log2(e)), evaluated in float64 on the operands as stored."""
+(`fmc_spatial_attn_fwd`, `ta_fill` of temporal_attn.hip, `fmc_attention_fwd`; within 2^-23 of scale * log2(e)), evaluated in float64 on the operands as stored."""
 import functools
 import math
 import zlib
@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 F64 = torch.float64
-LOG2E32 = np.float32(1.4426950408889634)            # `constexpr float LOG2E` of spatial_attn.hip:36, temporal_attn.hip:30, attn_generic.hip:271
+LOG2E32 = np.float32(1.4426950408889634)            # `constexpr float LOG2E` of spatial_attn.hip:36, temporal_attn.hip:30, the literal in `fmc_attention_fwd`
 LN2 = math.log(2.0)
 SA_BQ, SA_BK, REF_LIMIT = 128, 64, 64.0             # spatial_attn.hip:33, :35, :62
 
@@ -38,30 +38,30 @@ Case = namedtuple("Case", "abi dtype B H Sq Skv D kvdiv layout kernel k2 spike c
 # dispatch restatement (csrc/spatial_attn.hip, csrc/temporal_attn.hip, csrc/attn_generic.hip)
 # =====================================================================================================================================================
 def xcd_remap(B, H):
-    """spatial_attn.hip:1560."""
+    """`P.xcd_remap` in `fmc_spatial_attn_fwd`."""
     return 2 if B % 8 == 0 else (1 if (B * H) % 8 == 0 else 0)
 
 
 def expected_kernel(dtype, B, H, Sq, Skv, D, kv_div):
     """The kernel `fmc_spatial_attn_fwd` launches with every A/B switch at its default."""
     bf = dtype == "bf16"
-    if bf and D == 40 and H == 8 and 1 <= Skv <= 96 and Sq % 32 == 0 and B % kv_div == 0:                       # xattn40_ok, :1066-1068 (first: :1564)
+    if bf and D == 40 and H == 8 and 1 <= Skv <= 96 and Sq % 32 == 0 and B % kv_div == 0:                       # xattn40_ok (asked first by fmc_spatial_attn_fwd)
         return "xattn40_kernel"
-    if bf and D == 80 and Skv % 32 == 0 and Skv >= 256 and Sq >= 160:                                          # sa_big80_ok, :1397-1400 (:1569)
-        return "sa_big80_kernel_w10"                                                                           # FMC_SA_BIG80_WAVES default 10, :1403
-    if bf and D == 160 and Skv <= 160:                                                                         # sa_small_ok, :1412-1415 (:1574)
-        return "sa_small160_kernel<3>" if Skv <= 96 else "sa_small160_kernel<5>"                               # launch_sa_small, :1424-1425
-    if bf and D == 40 and Skv % SA_BK == 0 and Skv >= 2 * SA_BK and Sq % 256 == 0:                             # sa40_ok, :1432-1435 (:1579); krs * 2 * Skv < 2^31
+    if bf and D == 80 and Skv % 32 == 0 and Skv >= 256 and Sq >= 160:                                          # sa_big80_ok (second)
+        return "sa_big80_kernel_w10"                                                                           # launch_sa_big80: SASwitches::big80_waves, default 10
+    if bf and D == 160 and Skv <= 160:                                                                         # sa_small_ok (third)
+        return "sa_small160_kernel<3>" if Skv <= 96 else "sa_small160_kernel<5>"                               # launch_sa_small
+    if bf and D == 40 and Skv % SA_BK == 0 and Skv >= 2 * SA_BK and Sq % 256 == 0:                             # sa40_ok (fourth); krs * 2 * Skv < 2^31
         return "sa40d_kernel"                                                                                  # holds at every size here
-    nks = (D + 15) // 16                                                                                       # dispatch_sa, :1522
+    nks = (D + 15) // 16                                                                                       # fmc_pick_nks (attn_common.h)
     assert nks in (1, 2, 3, 4, 5, 6, 8, 10), D
-    short = Skv <= 2 * SA_BK                                                                                   # launch_sa, :1484
+    short = Skv <= 2 * SA_BK                                                                                   # launch_sa
     pf, nq, mk, vr = False, 1, False, False
-    if bf and nks <= 6 and (Skv > SA_BK if short else True):                                                   # :1485-1486 / :1501-1503 (SA_PREFETCH_DEFAULT)
+    if bf and nks <= 6 and (Skv > SA_BK if short else True):                                                   # launch_sa_forms: `prefetch` (SA_PREFETCH_DEFAULT)
         pf = True
-        if nks <= 3 and Sq >= 2 * SA_BQ:                                                                       # :1487-1488 / :1504-1505 (FMC_SA_NQ default 2)
-            nq, vr = 2, True                                                                                   # FMC_SA_VR default 1, :1489 / :1506
-            mk = D % 16 == 8                                                                                   # FMC_SA_MK default 1, :1490 / :1507
+        if nks <= 3 and Sq >= 2 * SA_BQ:                                                                       # launch_sa_forms: SASwitches::nq, default 2
+            nq, vr = 2, True                                                                                   # SASwitches::vr, default 1
+            mk = D % 16 == 8                                                                                   # SASwitches::mk, default 1
     return tiled_name(dtype, nks, short, pf, nq, mk, vr)
 
 
@@ -70,19 +70,19 @@ def tiled_name(dtype, nks, short, pf, nq, mk, vr):
 
 
 def default_tiled_instantiations():
-    """Every `spatial_attn_kernel` instantiation that `launch_sa` (:1482-1518) can reach with the switches at their defaults, listed from the template
+    """Every `spatial_attn_kernel` instantiation that `launch_sa` (through `launch_sa_forms`, once per SHORT_KV) can reach with the switches at their defaults, listed from the template
     arguments of its `launch_sa_v` calls -- NOT from `expected_kernel`."""
     names = set()
     for nks in (1, 2, 3, 4, 5, 6, 8, 10):
         for short in (True, False):
-            names.add(tiled_name("fp32", nks, short, False, 1, False, False))           # sizeof(T) == 4: :1499 / :1516 only
-            if short or nks > 6:                                                         # :1499 (Skv <= SA_BK); :1516 only for NKS > 6
+            names.add(tiled_name("fp32", nks, short, False, 1, False, False))           # sizeof(T) == 4: the last line of launch_sa_forms only
+            if short or nks > 6:                                                         # the last line: short, Skv <= SA_BK; long only for NKS > 6
                 names.add(tiled_name("bf16", nks, short, False, 1, False, False))
             if nks <= 6:
-                names.add(tiled_name("bf16", nks, short, True, 1, False, False))        # :1496 / :1513
+                names.add(tiled_name("bf16", nks, short, True, 1, False, False))        # `launch_sa_v<T, NKS, SHORT_KV, true>`
             if nks <= 3:
-                names.add(tiled_name("bf16", nks, short, True, 2, True, True))          # :1490 / :1507  (D % 16 == 8)
-                names.add(tiled_name("bf16", nks, short, True, 2, False, True))         # :1491 / :1508
+                names.add(tiled_name("bf16", nks, short, True, 2, True, True))          # `<.., true, 2, true, true>`  (D % 16 == 8)
+                names.add(tiled_name("bf16", nks, short, True, 2, False, True))         # `<.., true, 2, false, true>`
     return names
 
 
@@ -90,13 +90,13 @@ SPECIAL_KERNELS = {"xattn40_kernel", "sa_big80_kernel_w10", "sa_small160_kernel<
 
 
 def temporal_kernel(dtype, F, H, D, fp8=False):
-    """temporal_attn.hip:804-837 (and :916-934 for fp8): tiles, k-steps, waves, partial flag."""
+    """temporal_attn.hip, `launch_ta` (and `launch_ta8` for fp8) through `ta_dispatch`: tiles, k-steps, waves, partial flag."""
     gh = 1
-    for g in range(1, H + 1):                                                                                  # :862-865 / :959-963
+    for g in range(1, H + 1):                                                                                  # ta_head_group, with the fp8 forward's `extra`
         if H % g == 0 and g * D <= 320 and (not fp8 or (g * D) % 16 == 0):
             gh = g
-    nw = 4 if gh >= 4 else (2 if gh >= 2 else 1)                                                               # :813-815
-    ft, part = (1 if F <= 16 else 2), F not in (16, 32)                                                        # :834-836
+    nw = 4 if gh >= 4 else (2 if gh >= 2 else 1)                                                               # ta_waves
+    ft, part = (1 if F <= 16 else 2), F not in (16, 32)                                                        # ta_tiles
     return f"temporal_attn_{'fp8_' if fp8 else ''}kernel<{dtype},{ft},{(D + 31) // 32},{nw},{int(part)}>", gh, nw
 
 
@@ -218,7 +218,7 @@ TEMPORAL_DH = [(8, 6), (40, 5), (80, 3), (160, 3)]
 TEMPORAL = [ta(dtype, 2 if (i + j) % 2 == 0 else 1, 3 if (i + j) % 2 == 0 else 5, F, H, D, "native" if (i + j) % 2 == 0 else "nfc")
             for dtype in ("bf16", "fp32") for i, F in enumerate((1, 7, 16, 17, 24, 32)) for j, (D, H) in enumerate(TEMPORAL_DH)]
 FP8 = [ta("bf16", 2, 3, F, H, D, "native", fp8=True) for F, (D, H) in zip((1, 7, 16, 17, 24, 32), ((8, 6), (40, 4), (80, 3), (160, 2), (40, 4), (8, 6)))]
-# fmc_attention_fwd takes D in {32, 64, 128, 256, 512} only (attn_generic.hip:254): 128 stands where the issue names 160
+# fmc_attention_fwd takes D in {32, 64, 128, 256, 512} only (`fmc_attention_supported`): 128 stands where the issue names 160
 GENERIC = [c for dtype in ("bf16", "fp32") for c in (
     ag(dtype, 2, 2, 70, 77, 64), ag(dtype, 2, 2, 77, 77, 64, causal=True, layout="fused"), ag(dtype, 2, 2, 50, 65, 64, keep=True),
     ag(dtype, 1, 2, 33, 130, 128, causal=True, keep=True), ag(dtype, 1, 2, 130, 33, 128), ag(dtype, 1, 1, 65, 40, 512), ag(dtype, 1, 1, 40, 65, 512, causal=True))]
